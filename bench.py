@@ -2,6 +2,11 @@
 """bench.py -- training rays/s of the NAF hot path on chest_50 (BASELINE.json configs[1]).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                             (also the profiled pass, rooflines, sustained rate, sub-records,
+                                                            PSNR races, full schedule and CPU baseline)
+    python bench.py ... --dump-outputs DIR                 (what the last timed step computed, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the headline; everything else is behind --full.
 
 A step = what `Trainer.train_step` of the reference does for one batch (src/trainer.py:134-142 around train.py:48-135,
 data side src/dataset/tigre.py:354-372), all of it inside the timed region and none of it touching the host:
@@ -29,12 +34,14 @@ sys.path.insert(0, REPO)
 
 CHEST = dict(n_voxel=256, n_proj=50, n_samples=192, num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_size=19,
              bound=0.3, lr=1e-3, yaml_rays=1024)
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X HBM3E: 8.0 TB/s spec
 RAYS_PER_PROJECTION = 16384    # a step of n rays draws from n / 16384 consecutive projections (the YAML step: 1024 from one)
 # PSNR races run with every N = 1 bench (time / rays / steps to 30, 35, 38 dB volume PSNR from scratch): the reference's operating
 # point (config/chest_50.yaml:29-30: 1024 rays, lr 1e-3) as the control, the same step at the learning rate that wins the grid of
 # profiles/round3_psnr_race_grid.jsonl (an extension: the reference never changes lr), and the large batch at ITS best rate.
 RACES = {"yaml_step_reference_lr": (1024, 1e-3), "yaml_step_lr_4e-3": (1024, 4e-3), "large_batch_16384_lr_4e-3": (16384, 4e-3)}
+# --dump-outputs writes a fixed, seeded sample of the updated table: all of it (16 x 2^19 x 2 entries in fp32) is 64 MiB on its own
+DUMP_TABLE_ENTRIES = 1 << 21
 
 
 def algorithmic_bytes_per_point(kernel, table_bytes, feat_bytes, L=16, C=2, D=3):
@@ -236,6 +243,23 @@ def step_weights(n, device, world=1):
     return torch.full((n,), 1.0 / (n * world), device=device), "global mean"
 
 
+def dump_outputs(out_dir, engine, n):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files -- the loss, the step's projections
+    (one line integral per ray), the updated MLP parameters, and the updated fp32 master table and the 16-bit table the kernels
+    read (bf16 mode) at DUMP_TABLE_ENTRIES entries drawn with a fixed seed.  Same arguments, same inputs: two builds compare
+    file for file."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    flat = engine.emb.reshape(-1)
+    pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_TABLE_ENTRIES].sort().values
+    pick = pick.to(flat.device)
+    arrays = {"loss": engine.loss, "projection": engine.acc[:n], "mlp_params": engine.mlp, "table_sample": flat[pick]}
+    if engine.emb_lp is not None:
+        arrays["table_lowp_sample"] = engine.emb_lp.reshape(-1)[pick]
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def psnr_race(scan, n_rays, lr, precision="bf16", thresholds=(30.0, 35.0, 38.0), max_train_s=12.0, burst_s=0.1, seed=0):
     """The PSNR half of the metric as a race: train chest_50 from scratch with steps of `n_rays` rays at learning rate `lr`
     and record the TRAINING time (seconds inside train steps: pixel draw + ray generation + forward + backward + Adam, evaluation
@@ -366,6 +390,12 @@ def main():
     ap.add_argument("--rays", type=int, default=CHEST["yaml_rays"],
                     help="rays per GPU per step (default: chest_50.yaml's n_rays = 1024, the step that reconstructs fastest)")
     ap.add_argument("--precision", choices=["bf16", "fp32"], default="bf16", help="table storage / MLP operand type")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline: the profiled pass (per-kernel times, rooflines, "
+                         "exchange times), the sustained rate, the sub-records, the PSNR races, the full schedule and the CPU baseline; "
+                         "the options from --cpu-seconds to --full-schedule-epochs act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=60.0, help="budget of the cpu_baseline leg (0 disables it)")
     ap.add_argument("--sub-records", type=int, default=1, help="0: skip the fp32-parity-mode and 1024-ray sub-records (N = 1 only)")
     ap.add_argument("--seed", type=int, default=0)
@@ -444,7 +474,7 @@ def main():
             print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
     # ---- chest_50 scan, resident in HBM: geometry, poses, all 50 x 512 x 512 measured values -----------------------
-    scan = ChestScan(device, 1234 + rank, with_volume=(rank == 0))    # each rank draws its own shard
+    scan = ChestScan(device, 1234 + rank, with_volume=(rank == 0 and args.full))    # each rank draws its own shard; the volume: PSNR only
     sampler = scan.sampler
     log(f"scan resident: {scan.raygen.n_projections} projections, {min(v.numel() for v in sampler.valid)}.."
         f"{max(v.numel() for v in sampler.valid)} valid pixels each")
@@ -523,25 +553,29 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- per-kernel times: a second pass over the same kind of steps with a HIP-event pair around every kernel, on its launch
-    # stream (naf_profile_*).  The events cost ~10 % at this step size, which is why this pass is not the timed region. ----------
-    prof_steps = min(max(args.steps, 50 if n <= 4096 else 10), 200 if n <= 4096 else 20)
-    engine.comm_timing(True)
-    _abi.profile_enable(True)
-    t0 = time.perf_counter()
-    for i in range(total_steps, total_steps + prof_steps):
-        step(i)
-    barrier()
-    prof_elapsed = time.perf_counter() - t0
-    prof = _abi.profile_collect()
-    _abi.profile_enable(False)
-    comm = engine.comm_report()
-    engine.comm_timing(False)
-    n_scatter = n * world if levels_mode else n               # a level-parallel rank scatters every rank's points (its levels)
-    overflow = engine.scatter_overflow(n_scatter)
-    overflow_levels = engine.scatter_overflow_levels(n_scatter)     # read HERE: the sub-records below re-lay the workspace out
-    if overflow_levels is not None and overflow is not None and sum(overflow_levels) != overflow:
-        raise SystemExit(f"scatter overflow counters disagree: total {overflow}, per level {overflow_levels}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine, n)
+
+    if args.full:
+        # ---- per-kernel times: a second pass over the same kind of steps with a HIP-event pair around every kernel, on its launch
+        # stream (naf_profile_*).  The events cost ~10 % at this step size, which is why this pass is not the timed region. ----------
+        prof_steps = min(max(args.steps, 50 if n <= 4096 else 10), 200 if n <= 4096 else 20)
+        engine.comm_timing(True)
+        _abi.profile_enable(True)
+        t0 = time.perf_counter()
+        for i in range(total_steps, total_steps + prof_steps):
+            step(i)
+        barrier()
+        prof_elapsed = time.perf_counter() - t0
+        prof = _abi.profile_collect()
+        _abi.profile_enable(False)
+        comm = engine.comm_report()
+        engine.comm_timing(False)
+        n_scatter = n * world if levels_mode else n               # a level-parallel rank scatters every rank's points (its levels)
+        overflow = engine.scatter_overflow(n_scatter)
+        overflow_levels = engine.scatter_overflow_levels(n_scatter)     # read HERE: the sub-records below re-lay the workspace out
+        if overflow_levels is not None and overflow is not None and sum(overflow_levels) != overflow:
+            raise SystemExit(f"scatter overflow counters disagree: total {overflow}, per level {overflow_levels}")
 
     def timed(fn, steps, warm):
         for i in range(warm):
@@ -554,14 +588,14 @@ def main():
         return (time.perf_counter() - t) / steps
 
     sustained = None
-    if world == 1 and not args.force_dp:
+    if args.full and world == 1 and not args.force_dp:
         k = max(args.steps, int(2.2 / (elapsed / args.steps)))           # >= 2 s of back-to-back steps
         dt = timed(lambda i: step(total_steps + prof_steps + i), k, 0)
         sustained = {"steps": k, "seconds": round(dt * k, 3), "ms_per_step": round(dt * 1e3, 4), "rays_per_s": n / dt}
         log(f"sustained: {k} steps in {dt * k:.2f} s")
 
     sub_records = None
-    if rank == 0 and world == 1 and args.sub_records and not args.force_dp:
+    if args.full and rank == 0 and world == 1 and args.sub_records and not args.force_dp:
         log("sub-records: the large batch, the fp32 parity mode")
         # (a) the throughput end of the batch curve (the headline of rounds 1-2): 65 536 rays from 4 projections per step
         sub_records = {}
@@ -585,7 +619,7 @@ def main():
 
     # ---- the PSNR half of the metric: time / rays / steps to 30, 35, 38 dB volume PSNR, from scratch, per operating point -------
     psnr = None
-    if rank == 0 and world == 1 and args.psnr_seconds > 0 and not args.force_dp:
+    if args.full and rank == 0 and world == 1 and args.psnr_seconds > 0 and not args.force_dp:
         psnr = {}
         for name, (m, lr) in RACES.items():
             log(f"PSNR race {name}: {m} rays/step, lr {lr}")
@@ -594,7 +628,7 @@ def main():
 
     # ---- ... and the same half on the reference's own schedule, in both precisions ------------------------------------------------
     schedule = None
-    if rank == 0 and world == 1 and args.full_schedule and not args.force_dp:
+    if args.full and rank == 0 and world == 1 and args.full_schedule and not args.force_dp:
         schedule = {}
         for prec in ("bf16", "fp32"):
             log(f"full schedule ({prec}): chest_50.yaml's epochs x projections x 1024 rays, from scratch")
@@ -604,70 +638,6 @@ def main():
 
     if rank == 0:
         rays_total = world * n * args.steps
-        points_per_launch = n * CHEST["n_samples"]
-        n_params = engine.emb.numel()
-        tb, fb = {"bf16": (2, 2), "fp32": (4, 4)}[args.precision]
-        kernels = {k: {"launches": c, "total_ms": ms, "avg_ms": ms / max(c, 1)} for k, (c, ms) in prof.items()}
-        mfma_peak = 2500.0 if args.precision == "bf16" else 157.3      # TFLOP/s dense, MI355X_MICROARCH.md
-        # pair record of the binned scatter: 8 bytes in bf16 mode (scatter_v2.h; 12 with the round-3 kernels, --cfg-flags 2048), 20 in fp32 mode
-        rec_bytes = (12 if args.cfg_flags & 2048 else 8) if args.precision == "bf16" else 20
-        fused_adam = engine.fuse_table_adam and engine._dp is None
-        # Algorithmic bytes / flops of ONE launch of each kernel.  encode: SURVEY 8(d)'s hash-forward figure.
-        # The gradient scatter is two kernels here, each priced on what it must move: bin reads the feature gradients and writes
-        # one pair record per x-neighbour corner pair; reduce reads the records and -- with the Adam tail -- reads and writes
-        # parameter, both moments (fp32) and writes the 16-bit shadow of every table element (otherwise read + write of the gradient).
-        algo = {
-            "encode_kernel": ("hbm", algorithmic_bytes_per_point("encode_kernel", tb, fb) * points_per_launch),
-            "scatter_bin_kernel": ("hbm", (32 * fb + 16 * 4 * rec_bytes) * points_per_launch),
-            "scatter_reduce_kernel": ("hbm", 16 * 4 * rec_bytes * points_per_launch
-                                      + n_params * ((24 + (2 if args.precision == "bf16" else 0)) if fused_adam else 8)),
-            "hash_backward_kernel": ("hbm", algorithmic_bytes_per_point("hash_backward_kernel", tb, fb) * points_per_launch),
-            "mlp_forward_kernel": ("mfma", 8256 * points_per_launch),
-            "mlp_backward_kernel": ("mfma", 3 * 8256 * points_per_launch),
-            "adam_kernel": ("hbm", None),
-        }
-
-        # HBM bytes by PMC counters come from separate rocprofv3 --pmc passes (tools/collect_profiles.sh); they are printed only
-        # while the kernel sources are the ones those passes ran on
-        traffic_table, traffic_note = {}, "profiles/pmc_traffic.json absent"
-        tf = os.path.join(REPO, "profiles", "pmc_traffic.json")
-        if os.path.exists(tf):
-            doc = json.load(open(tf))
-            if doc.get("csrc_fingerprint") != source_fingerprint():
-                traffic_note = (f"stale: the PMC passes ran on kernel sources {doc.get('csrc_fingerprint')}, this build is "
-                                f"{source_fingerprint()} -- rerun tools/collect_profiles.sh + tools/install_profiles.py")
-            elif str(n) not in doc.get("by_rays", {}) or world != 1:
-                traffic_note = f"the PMC passes were taken at {sorted(doc.get('by_rays', {}))} rays/step on one GPU"
-            else:
-                traffic_table = doc["by_rays"][str(n)].get(args.precision, {})
-                traffic_note = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at commit {doc.get('collected_at_commit')}, "
-                                f"kernel sources {doc.get('csrc_fingerprint')}, {n} rays/step")
-
-        def roof(kernel):
-            """Roofline of ONE kernel: algorithmic bytes (or flops) of a launch / its average launch duration (HIP events on the
-            launch stream, profiled pass); `traffic` = HBM bytes per launch by PMC; `real_frac` = traffic / time / peak."""
-            v = kernels[kernel]
-            t = v["avg_ms"] * 1e-3
-            bound, work = algo.get(kernel, ("hbm", None))
-            base = {"kernel": kernel, "avg_launch_ms": round(v["avg_ms"], 5), "launches_per_step": round(v["launches"] / prof_steps, 2),
-                    "points_per_launch": points_per_launch, "bound": bound}
-            if work is None:
-                return base
-            if bound == "hbm":
-                ach = work / t / 1e9
-                traffic = traffic_table.get(kernel)
-                base.update({"achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                             "traffic": traffic, "algorithmic_bytes_per_launch": work,
-                             "real_frac": None if not traffic else round(traffic / t / 1e9 / HBM_PEAK_GBS, 4)})
-            else:
-                ach = work / t / 1e12
-                base.update({"achieved": round(ach, 2), "peak": mfma_peak, "unit": "TFLOP/s", "frac": round(ach / mfma_peak, 4),
-                             "traffic": None, "algorithmic_flops_per_launch": work})
-            return base
-
-        per_step = {k: v["total_ms"] / prof_steps for k, v in kernels.items()}
-        dominant = max((k for k in per_step if k in algo and algo[k][1] is not None), key=lambda k: per_step[k])
-        kernel_ms = sum(per_step.values())
         out = {
             "metric": "train rays/sec, chest 256^3 / 50 proj", "value": rays_total / elapsed, "unit": "rays/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -681,44 +651,112 @@ def main():
                                    + ("; the operating point that reaches 35 dB volume PSNR soonest (psnr.*, profiles/round3_psnr_race_grid.jsonl)"
                                       if n == CHEST["yaml_rays"] else ""),
                        "rays_per_step_per_gpu": n, "n_samples": CHEST["n_samples"], "lr": engine.lr, "parallelism": (f"lp{world}" if levels_mode else f"dp{world}")},
-            "final_loss": final_loss, "sustained": sustained, "psnr": psnr, "full_schedule": schedule,
-            "scatter_overflow_last_step": overflow, "scatter_overflow_levels": overflow_levels,
-            "library_kernels_ms_per_step": round(kernel_ms, 4),
-            "profiled_pass": {"steps": prof_steps, "ms_per_step": round(prof_elapsed / prof_steps * 1e3, 4),
-                              "note": "per-kernel HIP-event pairs switched on; not the timed region"},
-            "allreduce_ms_per_step": None, "allreduce_exposed_ms_per_step": None, "allreduce_buckets": dp_buckets,
-            "allreduce_bytes": allreduce_bytes, "rays_per_s_per_gpu": rays_total / elapsed / world,
+            "final_loss": final_loss, "allreduce_buckets": dp_buckets, "allreduce_bytes": allreduce_bytes,
+            "rays_per_s_per_gpu": rays_total / elapsed / world,
             "grad_exchange": ("level-parallel: rank k owns levels [k L/N, (k+1) L/N) -- all-to-all of the features, all-to-all of the feature "
                               "gradients, Adam on the owned rows; MLP gradient + loss all-reduced (allreduce_bytes = bytes a rank sends per step)")
             if levels_mode else None if engine._dp is None else (
                 "reduce-scatter of the table gradient -> Adam on this rank's 1/N slice -> all-gather of the table the kernels read; "
                 "MLP gradient + loss all-reduced" if engine.dp_mode == "sharded" else "all-reduce per level bucket, Adam replicated"),
-            "roofline": roof(dominant),
-            "roofline_hash_forward": roof("encode_kernel") if "encode_kernel" in kernels else None,
-            "roofline_all": {k: roof(k) for k in sorted(kernels) if k in algo},
-            "traffic_source": traffic_note,
-            "kernels_ms_per_step": {k: round(v, 4) for k, v in sorted(per_step.items())},
         }
-        if comm is not None:
-            # in flight: the collectives on the side stream, measured by events inside the profiled steps.  exposed: what the main
-            # stream waited after its own compute = tail (end of compute -> last Adam launched) minus the Adam kernels themselves
-            out["allreduce_ms_per_step"] = round(comm["allreduce_ms_per_step"], 4)
-            if levels_mode:                              # both all-to-alls sit on the critical path; the phases of a step by HIP events
-                out["allreduce_exposed_ms_per_step"] = round(comm["tail_ms_per_step"], 4)
-                out["level_parallel_phases_ms"] = {k: round(v, 4) for k, v in comm.items() if k.endswith("_ms")}
-            else:
-                out["allreduce_exposed_ms_per_step"] = round(max(0.0, comm["tail_ms_per_step"] - per_step.get("adam_kernel", 0.0)), 4)
-        if sub_records is not None:
-            out["sub_records"] = sub_records
-            par = sub_records.get(f"fp32_parity_mode_{CHEST['yaml_rays']}_rays")
-            if par is not None:
-                # the mode that meets BOTH parity bars of the north star (projection rel. L2 1e-4 and PSNR +-0.1 dB): the reference's own
-                # arithmetic (fp32 table, fp32 MFMA = an fmaf chain, fp32 scatter records), same YAML step, same box, same run
-                out["parity_mode"] = {"value": par["rays_per_s"], "unit": "rays/s", "ms_per_step": par["ms_per_step"], "dtype": "f32",
-                                      "rays_per_step": par["rays_per_step"], "loss": par["loss"]}
-        if world == 1 and args.cpu_seconds > 0 and not args.force_dp:
-            log("cpu_baseline leg (oracle, host cores)")
-            out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.seed)
+        if args.full:
+            points_per_launch = n * CHEST["n_samples"]
+            n_params = engine.emb.numel()
+            tb, fb = {"bf16": (2, 2), "fp32": (4, 4)}[args.precision]
+            kernels = {k: {"launches": c, "total_ms": ms, "avg_ms": ms / max(c, 1)} for k, (c, ms) in prof.items()}
+            mfma_peak = 2500.0 if args.precision == "bf16" else 157.3      # TFLOP/s dense, MI355X spec
+            # pair record of the binned scatter: 8 bytes in bf16 mode (scatter_v2.h; 12 with the round-3 kernels, --cfg-flags 2048), 20 in fp32 mode
+            rec_bytes = (12 if args.cfg_flags & 2048 else 8) if args.precision == "bf16" else 20
+            fused_adam = engine.fuse_table_adam and engine._dp is None
+            # Algorithmic bytes / flops of ONE launch of each kernel.  encode: SURVEY 8(d)'s hash-forward figure.
+            # The gradient scatter is two kernels here, each priced on what it must move: bin reads the feature gradients and writes
+            # one pair record per x-neighbour corner pair; reduce reads the records and -- with the Adam tail -- reads and writes
+            # parameter, both moments (fp32) and writes the 16-bit shadow of every table element (otherwise read + write of the gradient).
+            algo = {
+                "encode_kernel": ("hbm", algorithmic_bytes_per_point("encode_kernel", tb, fb) * points_per_launch),
+                "scatter_bin_kernel": ("hbm", (32 * fb + 16 * 4 * rec_bytes) * points_per_launch),
+                "scatter_reduce_kernel": ("hbm", 16 * 4 * rec_bytes * points_per_launch
+                                          + n_params * ((24 + (2 if args.precision == "bf16" else 0)) if fused_adam else 8)),
+                "hash_backward_kernel": ("hbm", algorithmic_bytes_per_point("hash_backward_kernel", tb, fb) * points_per_launch),
+                "mlp_forward_kernel": ("mfma", 8256 * points_per_launch),
+                "mlp_backward_kernel": ("mfma", 3 * 8256 * points_per_launch),
+                "adam_kernel": ("hbm", None),
+            }
+
+            # HBM bytes by PMC counters come from separate rocprofv3 --pmc passes (tools/collect_profiles.sh); they are printed only
+            # while the kernel sources are the ones those passes ran on
+            traffic_table, traffic_note = {}, "profiles/pmc_traffic.json absent"
+            tf = os.path.join(REPO, "profiles", "pmc_traffic.json")
+            if os.path.exists(tf):
+                doc = json.load(open(tf))
+                if doc.get("csrc_fingerprint") != source_fingerprint():
+                    traffic_note = (f"stale: the PMC passes ran on kernel sources {doc.get('csrc_fingerprint')}, this build is "
+                                    f"{source_fingerprint()} -- rerun tools/collect_profiles.sh + tools/install_profiles.py")
+                elif str(n) not in doc.get("by_rays", {}) or world != 1:
+                    traffic_note = f"the PMC passes were taken at {sorted(doc.get('by_rays', {}))} rays/step on one GPU"
+                else:
+                    traffic_table = doc["by_rays"][str(n)].get(args.precision, {})
+                    traffic_note = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at commit {doc.get('collected_at_commit')}, "
+                                    f"kernel sources {doc.get('csrc_fingerprint')}, {n} rays/step")
+
+            def roof(kernel):
+                """Roofline of ONE kernel: algorithmic bytes (or flops) of a launch / its average launch duration (HIP events on the
+                launch stream, profiled pass); `traffic` = HBM bytes per launch by PMC; `real_frac` = traffic / time / peak."""
+                v = kernels[kernel]
+                t = v["avg_ms"] * 1e-3
+                bound, work = algo.get(kernel, ("hbm", None))
+                base = {"kernel": kernel, "avg_launch_ms": round(v["avg_ms"], 5), "launches_per_step": round(v["launches"] / prof_steps, 2),
+                        "points_per_launch": points_per_launch, "bound": bound}
+                if work is None:
+                    return base
+                if bound == "hbm":
+                    ach = work / t / 1e9
+                    traffic = traffic_table.get(kernel)
+                    base.update({"achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                                 "traffic": traffic, "algorithmic_bytes_per_launch": work,
+                                 "real_frac": None if not traffic else round(traffic / t / 1e9 / HBM_PEAK_GBS, 4)})
+                else:
+                    ach = work / t / 1e12
+                    base.update({"achieved": round(ach, 2), "peak": mfma_peak, "unit": "TFLOP/s", "frac": round(ach / mfma_peak, 4),
+                                 "traffic": None, "algorithmic_flops_per_launch": work})
+                return base
+
+            per_step = {k: v["total_ms"] / prof_steps for k, v in kernels.items()}
+            dominant = max((k for k in per_step if k in algo and algo[k][1] is not None), key=lambda k: per_step[k])
+            kernel_ms = sum(per_step.values())
+            out.update({
+                "sustained": sustained, "psnr": psnr, "full_schedule": schedule,
+                "scatter_overflow_last_step": overflow, "scatter_overflow_levels": overflow_levels,
+                "library_kernels_ms_per_step": round(kernel_ms, 4),
+                "profiled_pass": {"steps": prof_steps, "ms_per_step": round(prof_elapsed / prof_steps * 1e3, 4),
+                                  "note": "per-kernel HIP-event pairs switched on; not the timed region"},
+                "allreduce_ms_per_step": None, "allreduce_exposed_ms_per_step": None,
+                "roofline": roof(dominant),
+                "roofline_hash_forward": roof("encode_kernel") if "encode_kernel" in kernels else None,
+                "roofline_all": {k: roof(k) for k in sorted(kernels) if k in algo},
+                "traffic_source": traffic_note,
+                "kernels_ms_per_step": {k: round(v, 4) for k, v in sorted(per_step.items())},
+            })
+            if comm is not None:
+                # in flight: the collectives on the side stream, measured by events inside the profiled steps.  exposed: what the main
+                # stream waited after its own compute = tail (end of compute -> last Adam launched) minus the Adam kernels themselves
+                out["allreduce_ms_per_step"] = round(comm["allreduce_ms_per_step"], 4)
+                if levels_mode:                              # both all-to-alls sit on the critical path; the phases of a step by HIP events
+                    out["allreduce_exposed_ms_per_step"] = round(comm["tail_ms_per_step"], 4)
+                    out["level_parallel_phases_ms"] = {k: round(v, 4) for k, v in comm.items() if k.endswith("_ms")}
+                else:
+                    out["allreduce_exposed_ms_per_step"] = round(max(0.0, comm["tail_ms_per_step"] - per_step.get("adam_kernel", 0.0)), 4)
+            if sub_records is not None:
+                out["sub_records"] = sub_records
+                par = sub_records.get(f"fp32_parity_mode_{CHEST['yaml_rays']}_rays")
+                if par is not None:
+                    # the mode that meets BOTH parity bars of the north star (projection rel. L2 1e-4 and PSNR +-0.1 dB): the reference's own
+                    # arithmetic (fp32 table, fp32 MFMA = an fmaf chain, fp32 scatter records), same YAML step, same box, same run
+                    out["parity_mode"] = {"value": par["rays_per_s"], "unit": "rays/s", "ms_per_step": par["ms_per_step"], "dtype": "f32",
+                                          "rays_per_step": par["rays_per_step"], "loss": par["loss"]}
+            if world == 1 and args.cpu_seconds > 0 and not args.force_dp:
+                log("cpu_baseline leg (oracle, host cores)")
+                out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.seed)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if pg is not None:
         torch.distributed.destroy_process_group()

@@ -242,7 +242,7 @@ def test_bench_two_rank_launch_rehearsal(rays, dp_mode, direct):
     """`bench.py --gpus 2` as the driver may launch it -- bare (`python bench.py --gpus 2`: bench.py starts torch.distributed.run
     itself, as a child process) or already under torch.distributed.run -- except that the two ranks share the one GPU of the test
     box and talk through gloo (NAF_BENCH_BACKEND / NAF_BENCH_SHARE_GPU rehearsal hooks): one JSON line from rank 0 with the
-    whole-job rate, the MAX-over-ranks time and the all-reduce probe."""
+    whole-job rate, the MAX-over-ranks time and the all-reduce probe (exchange times come from the profiled pass: --full)."""
     import json
     import socket
     import subprocess
@@ -251,7 +251,7 @@ def test_bench_two_rank_launch_rehearsal(rays, dp_mode, direct):
     env = dict(os.environ, NAF_BENCH_BACKEND="gloo", NAF_BENCH_SHARE_GPU="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    tail = [os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", str(rays)]
+    tail = [os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rays", str(rays), "--full"]
     if dp_mode != "sharded":                                          # sharded is the default: the driver's command carries no such flag
         tail += ["--dp-mode", dp_mode]
     if direct:

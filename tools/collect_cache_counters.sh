@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/cache
 mkdir -p $OUT
 rocprofv3 -L > $OUT/counters_available.txt 2>&1 || echo "rocprofv3 -L failed"
-ARGS="--steps 3 --warmup 1 --rays 65536 --cpu-seconds 0 --sub-records 0 --psnr-seconds 0"
+ARGS="--steps 3 --warmup 1 --rays 65536 --full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0"
 pass() {   # name, counters...
   name=$1; shift
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -o $name -- python3 bench.py $ARGS > $OUT/bench_$name.json 2> $OUT/$name.err \

@@ -11,7 +11,7 @@ PART=${1:-A}
 OUT=gpurun_out/prof
 mkdir -p $OUT
 if [ "$PART" = A ]; then
-COMMON="--cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
+COMMON="--full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
 # the bench's default workload (chest_50.yaml's own step: 1 024 rays) and the throughput end of the batch curve (65 536 rays)
 for R in 1024 65536; do
   if [ $R = 1024 ]; then ARGS="--steps 200 --warmup 20 --rays $R $COMMON"; PMC="--steps 50 --warmup 10 --rays $R $COMMON"; else ARGS="--steps 10 --warmup 2 --rays $R $COMMON"; PMC="--steps 3 --warmup 1 --rays $R $COMMON"; fi
@@ -32,7 +32,7 @@ echo sq done
 # the counter passes are in: derive profiles/pmc_traffic.json now, so that the default line below carries `roofline.traffic`
 NAF_PROFILES_DST=gpurun_out/profiles_staged python tools/install_profiles.py ${NAF_TAG:-round4} > $OUT/install_a.log 2>&1
 cp gpurun_out/profiles_staged/pmc_traffic.json profiles/pmc_traffic.json
-timeout -k 10 700 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 700 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo default done
 for r in 128 256 512 1024 2048 4096 16384 65536 262144 1048576; do
   timeout -k 10 300 python bench.py --steps 20 --warmup 5 --rays $r $COMMON >> $OUT/batch_sweep.jsonl 2>> $OUT/batch_sweep.err
@@ -40,7 +40,7 @@ done
 echo sweep done
 timeout -k 10 300 python bench.py --steps 5 --warmup 2 --rays 16384 --precision fp32 $COMMON > $OUT/bench_fp32_16384.json 2> $OUT/fp32.err
 timeout -k 10 300 python bench.py --per-level --steps 5 --warmup 2 --rays 16384 $COMMON > $OUT/bench_per_level_16384.json 2> $OUT/per_level.err
-timeout -k 10 300 python bench.py --force-dp --steps 200 --warmup 20 --cpu-seconds 0 --psnr-seconds 0 --full-schedule 0 > $OUT/bench_force_dp.json 2> $OUT/force_dp.err
+timeout -k 10 300 python bench.py --full --force-dp --steps 200 --warmup 20 --cpu-seconds 0 --psnr-seconds 0 --full-schedule 0 > $OUT/bench_force_dp.json 2> $OUT/force_dp.err
 # the encoder with all levels of a point tile in flight at once (what a single fused gather+MLP kernel would do to the caches)
 timeout -k 10 300 python bench.py --interleaved-levels --rays 65536 --steps 10 --warmup 3 $COMMON > $OUT/bench_interleaved.json 2> $OUT/interleaved.err
 echo modes done
@@ -63,7 +63,7 @@ for n in 2 4 8; do
   timeout -k 10 200 python tools/levels_emulate.py --ranks $n 2>> $OUT/levels.err | tail -n 1 >> $OUT/levels_emulation.jsonl
 done
 timeout -k 10 300 python tools/levels_emulate.py --ranks 8 --rays 1024 --log2T 22 --samples 320 --table fp16 2>> $OUT/levels.err | tail -n 1 >> $OUT/levels_emulation.jsonl
-timeout -k 10 200 python bench.py --force-dp --dp-mode levels --steps 1000 --psnr-seconds 0 --cpu-seconds 0 --sub-records 0 --full-schedule 0 2> $OUT/levels_one_rank.err | tail -n 1 > $OUT/bench_level_parallel_one_rank.json
+timeout -k 10 200 python bench.py --full --force-dp --dp-mode levels --steps 1000 --psnr-seconds 0 --cpu-seconds 0 --sub-records 0 --full-schedule 0 2> $OUT/levels_one_rank.err | tail -n 1 > $OUT/bench_level_parallel_one_rank.json
 NAF_PROFILES_DST=gpurun_out/profiles_staged python tools/install_profiles.py ${NAF_TAG:-round4}
 ls gpurun_out/profiles_staged
 exit 0
@@ -88,7 +88,7 @@ timeout -k 10 200 python tools/levels_emulate.py --ranks 8 --precision fp32 2>> 
 for r in 1024 4096; do      # foot_50 shapes
   timeout -k 10 300 python tools/levels_emulate.py --ranks 8 --rays $r --log2T 22 --samples 320 --table fp16 2>> $OUT/levels.err | tail -n 1 >> $OUT/levels_emulation.jsonl
 done
-timeout -k 10 200 python bench.py --force-dp --dp-mode levels --steps 1000 --psnr-seconds 0 --cpu-seconds 0 --sub-records 0 --full-schedule 0 2> $OUT/levels_one_rank.err | tail -n 1 > $OUT/bench_level_parallel_one_rank.json
+timeout -k 10 200 python bench.py --full --force-dp --dp-mode levels --steps 1000 --psnr-seconds 0 --cpu-seconds 0 --sub-records 0 --full-schedule 0 2> $OUT/levels_one_rank.err | tail -n 1 > $OUT/bench_level_parallel_one_rank.json
 echo level-parallel emulation done
 # T = 2^22 (foot_50 shapes, the table is larger than every cache level below the Infinity Cache): HBM bytes fetched by the
 # encoder of the FUSED forward, quoted against the north star's 60 % bar in DESIGN.md section 4.1

@@ -2,7 +2,7 @@
 # round-3 A/B runs of the training step (diagnostic flags); output: $OUT/ab.jsonl (one line per variant)
 OUT=${OUT:-gpurun_out/r3c}
 mkdir -p $OUT
-B="--cpu-seconds 0 --sub-records 0 --psnr-seconds 0"
+B="--full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0"
 run() {  # rays steps warm flags...
   rays=$1; steps=$2; warm=$3; shift 3
   python bench.py --rays $rays --steps $steps --warmup $warm $B "$@" 2>> $OUT/ab.err | python -c "

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/r3p
 mkdir -p $OUT
-B="--cpu-seconds 0 --sub-records 0 --psnr-seconds 0"
+B="--full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1k -o stats -- python3 bench.py --steps 200 --warmup 20 $B > $OUT/bench_1024_under_rocprof.json 2> $OUT/stats1k.err
 cp $(find $OUT/stats1k -name "*kernel_stats.csv" | head -n 1) $OUT/kernel_stats_bf16_1024rays.csv; rm -rf $OUT/stats1k
 echo stats 1024 done

@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/r4b
 mkdir -p $OUT
-B="--cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
+B="--full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
 for F in 0 2048; do
   timeout -k 10 120 python bench.py --rays 65536 --steps 5 --warmup 2 $B --cfg-flags $F --per-level > $OUT/per_level_65536_f$F.json 2>> $OUT/err.log || exit 1
   timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA \

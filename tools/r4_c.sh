@@ -10,7 +10,7 @@ tail -4 $OUT/tests.log
 rm -f gpurun_out/ab_libs.jsonl
 RAYS="1024 16384 65536" bash tools/ab_libs.sh "$@" | tee $OUT/ab.txt
 cp $OUT/../.current.so $L/libnaf_hip.so
-B="--cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
+B="--full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA \
   --output-format csv -d $OUT/p -o p -- python3 bench.py --steps 3 --warmup 1 --rays 65536 $B > /dev/null 2>> $OUT/err.log \
   && python tools/pmc_summary.py $(find $OUT/p -name "*counter_collection.csv") --json $OUT/wave_state_65536.json > $OUT/wave_state_65536.txt 2>&1

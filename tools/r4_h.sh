@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r4h
 timeout -k 10 500 python -m pytest tests/test_hip_render_ops.py tests/test_abi_symbols.py -x -q -m gpu > gpurun_out/r4h/tests.log 2>&1; rc=$?; tail -15 gpurun_out/r4h/tests.log
 [ $rc = 0 ] || exit $rc
-C="--cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0 --steps 3000 --warmup 200"
+C="--full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0 --steps 3000 --warmup 200"
 rm -f gpurun_out/r4h/ab.jsonl
 for v in none 8-16 none 8-16 4-12 0-8 12-16 none; do
   if [ $v = none ]; then A=""; else A="--pipeline-levels $v"; fi

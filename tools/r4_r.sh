@@ -1,7 +1,7 @@
 #!/bin/bash
 # how many warm-up steps the 20-step timed region of the driver's command needs to reach the sustained rate (same box, alternating)
 mkdir -p gpurun_out/r4r; : > gpurun_out/r4r/warmup.jsonl
-C="--cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
+C="--full --cpu-seconds 0 --sub-records 0 --psnr-seconds 0 --full-schedule 0"
 for rep in 1 2; do
   for w in 5 50 500 5000; do
     timeout -k 10 200 python3 bench.py --gpus 1 --steps 20 --warmup $w $C 2>> gpurun_out/r4r/err | tail -n 1 >> gpurun_out/r4r/warmup.jsonl || exit 1
