@@ -430,6 +430,29 @@ int naf_adam_step(float *param, float *exp_avg, float *exp_avg_sq, float *grad, 
  */
 int naf_normalize_inputs(const float *x, uint64_t n, float size, float *out01, int32_t *flag, void *stream);
 
+/* P1  forward projector: line integrals of a voxel volume (the job of TIGRE's `Ax` in the reference's
+ * dataGenerator/generateData.py:178,189; bit-parity with TIGRE is not pinned).
+ *   volume  f32 [n1, n2, n3], axis 0 = x, C-contiguous; voxel centres on the get_voxels grid (tigre.py:388-400), the box
+ *           |p_a| <= h_a = fp32(n_a * dvoxel[a] / 2) centred at the origin (no origin offset)
+ *   dvoxel  HOST f32 [3] voxel size in metres (> 0);  dims  HOST u32 [3] = n1, n2, n3 (naf_project_scan)
+ *   step    target sample spacing in metres (> 0): accuracy * min(dvoxel), accuracy = 0.5 like TIGRE's geo.accuracy
+ * Value at p: trilinear, clamp-to-edge inside the box, zero outside.  u_a = (p_a + h_a) / dvoxel_a - 1/2 clamped to
+ * [0, n_a - 1], i_a = min(floor(u_a), n_a - 2), w_a = u_a - i_a; an axis with n_a == 1 is constant.
+ * Line integral of a ray (o, d, near, far) of the [n, 8] ray format (d un-normalised for cone beams), all in fp32:
+ *   [t0, t1] = slab intersection of the ray with the box, clipped to [near, far]; empty -> 0
+ *   len = (t1 - t0) * |d|,  n = max(1, ceil(len / step)),  seg = (t1 - t0) / n
+ *   result = (sum_{k < n} f(o + (t0 + (k + 1/2) * seg) * d)) * (len / n), summed in k order (bit-reproducible, no atomics);
+ *   sample k is evaluated as fma(s_k, d, fma(t0, d, o)) with s_k = (k + 1/2) * seg, straight from k
+ * naf_project_rays: rays f32 [n_rays, 8] (16-byte aligned) -> out f32 [n_rays].
+ * naf_project_scan: out f32 [n_projections, det_h, det_w]; pixel (p, row, col) integrates the ray naf_generate_rays makes for
+ *   flat pixel p*H*W + row*W + col (same poses / detector arguments), generated in the kernel and never stored.
+ * Empty batches (n_rays == 0, n_projections == 0) return NAF_OK without examining the pointers. */
+int naf_project_rays(const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, const float *rays,
+                     uint64_t n_rays, float step, float *out, void *stream);
+int naf_project_scan(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_projections,
+                     uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
+                     int parallel, float step, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

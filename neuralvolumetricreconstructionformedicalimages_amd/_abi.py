@@ -137,6 +137,9 @@ SIGNATURES = {
                                       ctypes.c_size_t, _vp]),
     "naf_adam_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _u64, _f32, _f32, _f32, _f32, _u32, _f32, _i32, _vp]),
     "naf_normalize_inputs": (_i32, [_vp, _u64, _f32, _vp, _vp, _vp]),
+    "naf_project_rays": (_i32, [_vp, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _u64, _f32, _vp, _vp]),
+    "naf_project_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
+                                _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),
 }
 
 

@@ -225,3 +225,56 @@ def _rays_cpu(geo, angle):
     near, far = get_near_far(geo)
     nf = torch.tensor([near, far], dtype=torch.float32).expand(H, W, 2)
     return torch.cat([o, d, nf], -1).reshape(-1, 8)
+
+
+NOISE_I0 = 1e5          # photons per pixel of the noise model of scan_from_volume (CTnoise.add(Poisson=1e5) in generateData.py:181)
+
+
+def scan_from_volume(image, geometry, n_train, n_val, total_angle=180, start_angle=0, random_angle=False, noise=0, seed=0,
+                     device="cuda"):
+    """A complete scan with the pickle schema, projected from a CT volume by the HIP forward projector (projector.py): the
+    step dataGenerator/generateData.py:153-211 of the reference does with TIGRE's `Ax`.
+
+    `image` [n1, n2, n3] (axis 0 = x, voxel centres on the get_voxels grid) and the scanner dict `geometry` (pickle schema,
+    millimetres) -> the dict `synthetic_scan` returns, which `TIGREDataset` loads unchanged; `image` is stored as given.
+    Train angles: linspace(0, total_angle, n_train + 1)[:-1] or, with `random_angle`, n_train sorted uniform draws in
+    [0, total_angle); val angles: n_val sorted uniform draws in [0, 180) degrees; both shifted by `start_angle`
+    (generateData.py:174-177,187).  The draws come from numpy RandomState(seed), train first.
+
+    `noise > 0` adds a seeded transmission noise model to both splits: counts I = Poisson(I0 exp(-p)) + Normal(0, noise) with
+    I0 = 1e5, then p = -ln(max(I, 1) / I0); negative training values are set to 0 (generateData.py:182).  Parity with
+    TIGRE's CTnoise is not pinned."""
+    from .projector import project_scan
+
+    data = dict(geometry)
+    geo = ConeGeometry(data)
+    rng = np.random.RandomState(seed)
+    total, start = float(total_angle) / 180 * np.pi, float(start_angle) / 180 * np.pi
+    if random_angle:
+        train_angles = np.sort(rng.rand(int(n_train)) * total) + start
+    else:
+        train_angles = np.linspace(0, total, int(n_train) + 1)[:-1] + start
+    val_angles = np.sort(rng.rand(int(n_val)) * np.pi) + start
+    dev = torch.device(device)
+    volume = torch.as_tensor(np.asarray(image), dtype=torch.float32).to(dev).contiguous()
+    gen = None
+    if noise > 0:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+    for name, angles in (("train", train_angles), ("val", val_angles)):
+        projs = project_scan(volume, geo, angles)
+        if noise > 0:
+            projs = add_noise(projs, noise, gen)
+            if name == "train":
+                projs = projs.clamp(min=0.0)
+        data[name] = {"angles": angles, "projections": projs.cpu().numpy()}
+    data["numTrain"], data["numVal"] = int(n_train), int(n_val)
+    data["image"] = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else image
+    return data
+
+
+def add_noise(projs, noise, generator, i0=NOISE_I0):
+    """Transmission noise on line integrals `projs`: I = Poisson(i0 exp(-p)) + Normal(0, noise), p' = -ln(max(I, 1) / i0)."""
+    counts = torch.poisson(i0 * torch.exp(-projs.double()), generator=generator)
+    counts = counts + float(noise) * torch.randn(counts.shape, generator=generator, device=counts.device, dtype=counts.dtype)
+    return (-torch.log(counts.clamp(min=1.0) / i0)).float()

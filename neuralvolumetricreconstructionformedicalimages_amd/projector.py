@@ -1,0 +1,103 @@
+"""Forward projector: line integrals of a voxel volume through libnaf_hip.so (`naf_project_rays`, `naf_project_scan`).
+
+This is what TIGRE's `tigre.Ax` does for the reference's dataGenerator/generateData.py:178,189: it turns a CT volume into the
+projections of a scan.  The projection is defined in include/naf_hip.h (P1) and DESIGN.md section 10: trilinear interpolation,
+clamp-to-edge inside the box and zero outside, midpoint rule with `n = max(1, ceil(len / (accuracy * min(dVoxel))))` samples
+over the part of the ray inside the box.  Pixel (p, row, col) of `project_scan` integrates the very ray `RayGenerator` makes for
+that pixel, so projections and training rays agree by construction (no TIGRE axis flips).  Bit-parity with TIGRE is not pinned.
+
+There is no CPU fallback, like the rest of the hot path.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _abi
+from .geometry import RayGenerator
+
+# pixels per launch of naf_project_scan: keeps one launch of a 720 x 1024^2 scan to a bounded grid
+MAX_PIXELS_PER_CALL = 1 << 26
+
+
+def _check_volume(volume):
+    if not isinstance(volume, torch.Tensor) or not volume.is_cuda:
+        raise RuntimeError("projector: volume must be a CUDA/HIP tensor (no CPU path)")
+    if volume.dtype != torch.float32:
+        raise TypeError(f"projector: volume must be float32, got {volume.dtype}")
+    if volume.dim() != 3:
+        raise ValueError(f"projector: volume must be [n1, n2, n3], got shape {tuple(volume.shape)}")
+    if not volume.is_contiguous():
+        raise ValueError("projector: volume must be contiguous")
+
+
+def sample_step(dvoxel, accuracy=0.5):
+    """Target sample spacing in metres: accuracy * min(dVoxel) (TIGRE's geo.accuracy is in voxels per sample)."""
+    step = float(accuracy) * float(np.min(np.asarray(dvoxel, dtype=np.float64)))
+    if not step > 0:
+        raise ValueError(f"projector: accuracy * min(dVoxel) must be > 0, got {step}")
+    return step
+
+
+def _dvoxel(dvoxel):
+    d = np.asarray(dvoxel, dtype=np.float64).reshape(-1)
+    if d.size != 3 or not np.all(d > 0):
+        raise ValueError(f"projector: dVoxel must be three positive sizes, got {dvoxel}")
+    return (ctypes.c_float * 3)(*[float(v) for v in d])
+
+
+def project_rays(volume, dvoxel, rays, accuracy=0.5, out=None):
+    """Line integrals of `volume` [n1, n2, n3] (voxel size `dvoxel` in metres) along `rays` [n, 8] -> float32 [n]."""
+    _check_volume(volume)
+    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device != volume.device:
+        raise RuntimeError("project_rays: rays must be a CUDA/HIP tensor on the volume's device")
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError(f"project_rays: rays must be float32 [n, 8], got {rays.dtype} {tuple(rays.shape)}")
+    if not rays.is_contiguous():
+        raise ValueError("project_rays: rays must be contiguous")
+    n = rays.shape[0]
+    if out is None:
+        out = torch.empty(n, device=volume.device, dtype=torch.float32)
+    elif out.shape != (n,) or out.dtype != torch.float32 or out.device != volume.device or not out.is_contiguous():
+        raise ValueError("project_rays: out must be a contiguous float32 [n] tensor on the volume's device")
+    n1, n2, n3 = volume.shape
+    _abi.check(_abi.lib().naf_project_rays(_abi.ptr(volume), n1, n2, n3, ctypes.byref(_dvoxel(dvoxel)), _abi.ptr(rays), n,
+                                           sample_step(dvoxel, accuracy), _abi.ptr(out), _abi.stream_ptr()), "project_rays")
+    return out
+
+
+def check_geometry(volume, geo):
+    """`volume` must sit on the voxel grid of `geo` (get_voxels): same dims, no origin offset."""
+    if np.any(np.asarray(geo.offOrigin, dtype=np.float64) != 0):
+        raise ValueError(f"projector: offOrigin must be zero (the voxel grid of get_voxels is centred), got {geo.offOrigin}")
+    want = tuple(int(v) for v in geo.nVoxel)
+    if tuple(volume.shape) != want:
+        raise ValueError(f"projector: volume shape {tuple(volume.shape)} does not match nVoxel {want}")
+
+
+def project_scan(volume, geo, angles, views_per_call=None):
+    """Projections of `volume` for the scan geometry `geo` (ConeGeometry) at `angles` (radians) -> float32 [N, H, W] on the
+    volume's device.  Views go to the kernel in groups of `views_per_call` (default: as many as fit MAX_PIXELS_PER_CALL)."""
+    _check_volume(volume)
+    check_geometry(volume, geo)
+    angles = np.asarray(angles, dtype=np.float64).reshape(-1)
+    raygen = RayGenerator(geo, angles, volume.device)
+    N, H, W = len(angles), raygen.H, raygen.W
+    out = torch.empty(N, H, W, device=volume.device, dtype=torch.float32)
+    if N == 0:
+        return out
+    per_call = views_per_call or max(1, MAX_PIXELS_PER_CALL // (H * W))
+    dims = (ctypes.c_uint32 * 3)(*[int(v) for v in volume.shape])
+    dv = _dvoxel(geo.dVoxel)
+    step = sample_step(geo.dVoxel, geo.accuracy)
+    lib = _abi.lib()
+    for first in range(0, N, per_call):
+        count = min(per_call, N - first)
+        _abi.check(lib.naf_project_scan(
+            _abi.ptr(volume), ctypes.byref(dims), ctypes.byref(dv), _abi.ptr(raygen.poses[first:first + count]), count, W, H,
+            float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]), float(geo.DSD),
+            float(raygen.near), float(raygen.far), int(geo.mode == "parallel"), step, _abi.ptr(out[first:first + count]),
+            _abi.stream_ptr()), "project_scan")
+    return out

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Make a training scan from a CT volume of your own -- the job of the reference's dataGenerator/generateData.py, with the
+HIP forward projector (projector.py) in place of TIGRE's `Ax`:
+
+    python tools/make_scan_from_volume.py --volume img.npy --config config.yml --out data/NAME.pickle
+    python train.py --config config/NAME.yaml          # exp.datadir: ./data/NAME.pickle
+
+`config.yml` has the keys of generateData.py's config: the scanner (DSD, DSO, nDetector, dDetector, nVoxel, dVoxel,
+offOrigin, offDetector, accuracy, mode, filter; optional tilt_angle), the volume preparation (convert, rescale_slope,
+rescale_intercept, normalize) and the scan (numTrain, numVal, totalAngle, startAngle, randomAngle, noise).
+
+`--volume` is a `.npy` array [n1, n2, n3] (axis 0 = x) or a MATLAB `.mat` file holding `img`.  Reading `.mat` files and
+resizing a volume to nVoxel (scipy.ndimage.zoom, order 3, no prefilter, like loadImage) need scipy; a `.npy` volume that
+already has nVoxel's shape needs numpy only.
+"""
+import argparse
+import os
+import pickle
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+GEOMETRY_KEYS = ("DSD", "DSO", "nDetector", "dDetector", "nVoxel", "dVoxel", "offOrigin", "offDetector", "accuracy", "mode", "filter")
+VOLUME_KEYS = ("convert", "rescale_slope", "rescale_intercept", "normalize")
+SCAN_KEYS = ("numTrain", "numVal", "totalAngle", "startAngle", "randomAngle", "noise")
+
+
+def read_config(path):
+    """config.yml -> dict; refuses a file that lacks any key generateData.py reads (tilt_angle is optional)."""
+    import yaml
+    with open(path, "r") as handle:
+        data = yaml.safe_load(handle) or {}
+    missing = [k for k in GEOMETRY_KEYS + VOLUME_KEYS + SCAN_KEYS if k not in data]
+    if missing:
+        raise KeyError(f"{path}: missing config keys {missing}")
+    return data
+
+
+def geometry_of(config):
+    """The scanner part of a config: the geometry dict of the pickle schema (millimetres, like the config)."""
+    geo = {k: config[k] for k in GEOMETRY_KEYS}
+    if config.get("tilt_angle"):
+        geo["tilt_angle"] = config["tilt_angle"]
+    return geo
+
+
+def convert_to_attenuation(data, rescale_slope, rescale_intercept):
+    """HU = slope * data + intercept, mu = mu_water + (mu_water - mu_air) / 1000 * HU (generateData.py:77-103)."""
+    HU = data * rescale_slope + rescale_intercept
+    mu_water, mu_air = 0.206, 0.0004
+    return mu_water + (mu_water - mu_air) / 1000 * HU
+
+
+def _scipy(what):
+    try:
+        import scipy.io
+        import scipy.ndimage
+    except ImportError:
+        raise RuntimeError(f"{what} needs scipy, which is not installed; save the volume as a .npy array of shape nVoxel "
+                           "instead") from None
+    return scipy
+
+
+def read_volume(path):
+    if path.endswith(".npy"):
+        return np.load(path, allow_pickle=False)
+    if path.endswith(".mat"):
+        return _scipy("reading a .mat volume").io.loadmat(path)["img"]
+    raise ValueError(f"{path}: the volume must be a .npy or .mat file")
+
+
+def prepare_volume(image, n_voxel, convert, rescale_slope, rescale_intercept, normalize=True):
+    """loadImage of generateData.py:106-150: HU -> attenuation, resize to n_voxel, normalise to [0, 1]."""
+    image = np.asarray(image).astype(np.float32)
+    if convert:
+        image = convert_to_attenuation(image, rescale_slope, rescale_intercept)
+    n_voxel = [int(v) for v in (n_voxel if n_voxel is not None else (256, 256, 256))]
+    zoom = [n / s for n, s in zip(n_voxel, image.shape)]
+    if any(z != 1.0 for z in zoom):
+        image = _scipy("resizing the volume to nVoxel").ndimage.zoom(image, zoom, order=3, prefilter=False)
+    lo, hi = np.min(image), np.max(image)
+    if normalize and lo != 0 and hi != 1:            # the reference's condition, kept as written
+        image = (image - lo) / (hi - lo)
+    return np.ascontiguousarray(image, dtype=np.float32)
+
+
+def make_scan(volume_path, config_path, device="cuda", seed=0):
+    from neuralvolumetricreconstructionformedicalimages_amd.dataset import scan_from_volume
+    config = read_config(config_path)
+    image = prepare_volume(read_volume(volume_path), config["nVoxel"], config["convert"], config["rescale_slope"],
+                           config["rescale_intercept"], config["normalize"])
+    data = scan_from_volume(image, geometry_of(config), config["numTrain"], config["numVal"], total_angle=config["totalAngle"],
+                            start_angle=config["startAngle"], random_angle=bool(config["randomAngle"]),
+                            noise=float(config["noise"] or 0), seed=seed, device=device)
+    for k in VOLUME_KEYS + ("totalAngle", "startAngle", "randomAngle", "noise"):
+        data[k] = config[k]                      # the reference's pickle keeps the whole config
+    return data
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--volume", required=True, help="CT volume: .npy [n1, n2, n3] or .mat with `img`")
+    ap.add_argument("--config", required=True, help="config.yml with the keys of generateData.py")
+    ap.add_argument("--out", required=True, help="output pickle")
+    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--seed", type=int, default=0, help="seeds the random angles and the noise")
+    args = ap.parse_args(argv)
+    data = make_scan(args.volume, args.config, args.device, args.seed)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "wb") as handle:
+        pickle.dump(data, handle, pickle.HIGHEST_PROTOCOL)
+    print(f"{args.out}: image {data['image'].shape}, train {data['train']['projections'].shape}, "
+          f"val {data['val']['projections'].shape}")
+
+
+if __name__ == "__main__":
+    main()
