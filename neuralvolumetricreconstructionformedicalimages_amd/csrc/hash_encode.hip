@@ -112,53 +112,19 @@ static bool ws_plan(uint32_t B, uint32_t C, uint32_t L, uint32_t log2T, int dtyp
     plan->levels_per_pass = (uint32_t)std::min<size_t>(plan->levels_per_pass, std::max<size_t>(1, kWsBudgetBytes / per_level));
     return true;
 }
-struct WsLayout { unsigned char *regions; uint32_t *counts, *overflow, *gmax; size_t bytes; };
-static WsLayout ws_carve(void *base, const naf_render_cfg *cfg, const BinPlan &plan) {
-    const size_t n_runs = ((size_t)plan.levels_per_pass << plan.log2_nb) * plan.n_tiles;
-    const size_t block_bytes = ((size_t)plan.levels_per_pass * plan.n_tiles * plan.slots * record_bytes(cfg) + 255) & ~(size_t)255;
-    WsLayout w;
-    w.regions = (unsigned char *)base;
-    w.counts = (uint32_t *)(w.regions + block_bytes);
-    w.overflow = w.counts + n_runs;                              // [0] total, [1 + level] per level
-    w.gmax = w.overflow + 33;
-    w.bytes = block_bytes + (((n_runs + 33 + 1) * 4 + 255) & ~(size_t)255);
-    return w;
-}
 
 template <typename T, uint32_t C>
-static int launch_backward_ws(const void *grad, const float *inputs, const int32_t *offsets, float *gtab, uint32_t B, uint32_t L, uint32_t H,
-                              bool blc, const naf_render_cfg *cfg, const BinPlan &plan, const WsLayout &w, hipStream_t s) {
-    using S = typename T::store_t;
-    using Rec = typename std::conditional<std::is_same<T, F32>::value, PairF32<C>, PairBF16<C>>::type;
-    constexpr uint32_t NT = BinShape<Rec>::kThreads, PTS = BinShape<Rec>::kPoints, LV = 4u;
-    constexpr bool kHasBig = sizeof(Rec) <= 12;
-    const bool big = kHasBig && plan.tile_points == 2u * NT * PTS;
-    if (!big && plan.tile_points != NT * PTS) return fail(NAF_ERR_LAUNCH, "hash_encode_backward_ws: plan / kernel tile mismatch");
-    const SrcUnit<3> src{inputs, B};
+static int binned_backward(const void *grad, const float *inputs, const int32_t *offsets, float *gtab, uint32_t B, bool blc,
+                           const naf_render_cfg *cfg, const BinPlan &plan, const BinRegions &w, hipStream_t s) {
+    // overflow counters and gmax to zero, then gmax = max |grad|: what the MLP backward of a training step hands the reducer
     if (hipMemsetAsync(w.overflow, 0, 34 * sizeof(uint32_t), s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "hash_encode_backward_ws: memset failed");
-    const uint64_t n = (uint64_t)B * L * C;
+    const uint64_t n = (uint64_t)B * cfg->L * C;
     { ProfScope prof_("grad_absmax_kernel", s); hipLaunchKernelGGL((grad_absmax_kernel<T>), dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, s,
-                       (const S *)grad, n, w.gmax); }
-    auto bin = scatter_bin_kernel<T, C, SrcUnit<3>, Rec, NT, PTS, LV>;
-    if constexpr (kHasBig) { if (big) bin = scatter_bin_kernel<T, C, SrcUnit<3>, Rec, 2u * NT, PTS, LV>; }
-    auto red = scatter_reduce_kernel<C, Rec, false>;
-    const uint32_t NB = 1u << plan.log2_nb, threads = big ? 2u * NT : NT;
-    const uint32_t red_lds = plan.max_local_rows * C * 8u, bin_lds = (2u * NB + 4u) * 4u + plan.slots * (uint32_t)sizeof(Rec);
-    if (hipFuncSetAttribute((const void *)red, hipFuncAttributeMaxDynamicSharedMemorySize, (int)red_lds) != hipSuccess ||
-        hipFuncSetAttribute((const void *)bin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds) != hipSuccess)
-        return fail(NAF_ERR_LAUNCH, "hash_encode_backward_ws: cannot raise the dynamic LDS limit");
-    const uint32_t sl = blc ? 1u : B, sb = blc ? L : 1u;
-    for (uint32_t l0 = 0; l0 < L; l0 += plan.levels_per_pass) {
-        const uint32_t nl = std::min(plan.levels_per_pass, L - l0);
-        { ProfScope prof_("scatter_bin_kernel", s); hipLaunchKernelGGL(bin, dim3(plan.n_tiles, (nl + LV - 1u) / LV), dim3(threads), bin_lds, s, src, (const S *)grad, offsets, gtab,
-                           (Rec *)w.regions, w.counts, w.overflow, B, H, l0, nl, plan, SlabReduce{}, sl, sb); }
-        if (int rc = check_launch("scatter_bin_kernel")) return rc;
-        { ProfScope prof_("scatter_reduce_kernel", s); hipLaunchKernelGGL(red, dim3(NB, nl, reducer_split(NB, nl)), dim3(1024), red_lds, s, (const Rec *)w.regions, w.counts, offsets, gtab,
-                           w.gmax, l0, 0u, H, plan, AdamTail{}); }
-        if (int rc = check_launch("scatter_reduce_kernel")) return rc;
-    }
-    (void)cfg;
-    return NAF_OK;
+                       (const typename T::store_t *)grad, n, w.gmax); }
+    // 12-byte / fp32 records, four levels per bin workgroup at every batch size, no Adam tail
+    using Rec = typename std::conditional<std::is_same<T, F32>::value, PairF32<C>, PairBF16<C>>::type;
+    PairRecords<T, C, SrcUnit<3>, Rec, 4u, false> fam{SrcUnit<3>{inputs, B}, grad, B, blc ? 1u : B, blc ? cfg->L : 1u};
+    return launch_binned_scatter(fam, cfg, plan, w, offsets, gtab, 0u, cfg->L, nullptr, s);
 }
 
 }  // namespace naf
@@ -220,7 +186,7 @@ extern "C" size_t naf_hash_encode_workspace_bytes(uint32_t B, uint32_t D, uint32
     naf_render_cfg cfg;
     BinPlan plan;
     if (D != 3u || B < kBinMinPoints || L == 0u || L > 32u || !ws_plan(B, C, L, log2_hashmap_size, dtype, &cfg, &plan)) return 0;
-    return ws_carve(nullptr, &cfg, plan).bytes;
+    return carve_bin_regions(nullptr, &cfg, plan).bytes;
 }
 
 extern "C" int naf_hash_encode_backward_ws(const void *grad, const float *inputs, const void *embeddings, const int32_t *offsets,
@@ -239,15 +205,16 @@ extern "C" int naf_hash_encode_backward_ws(const void *grad, const float *inputs
     if (((uintptr_t)workspace & 255u) != 0u) return fail(NAF_ERR_INVALID_ARGUMENT, "hash_encode_backward_ws: the workspace must be 256-byte aligned");
     const bool blc = grad_layout == NAF_LAYOUT_BLC;
     hipStream_t s = (hipStream_t)stream;
-    const WsLayout w = ws_carve(workspace, &cfg, plan);
+    cfg.H = H;
+    const BinRegions w = carve_bin_regions((unsigned char *)workspace, &cfg, plan);
     int rc = NAF_ERR_UNSUPPORTED;
     switch (dtype * 16 + (int)C) {
-        case NAF_F32 * 16 + 2: rc = launch_backward_ws<F32, 2>(grad, inputs, offsets, grad_embeddings, B, L, H, blc, &cfg, plan, w, s); break;
-        case NAF_F32 * 16 + 4: rc = launch_backward_ws<F32, 4>(grad, inputs, offsets, grad_embeddings, B, L, H, blc, &cfg, plan, w, s); break;
-        case NAF_F16 * 16 + 2: rc = launch_backward_ws<F16, 2>(grad, inputs, offsets, grad_embeddings, B, L, H, blc, &cfg, plan, w, s); break;
-        case NAF_F16 * 16 + 4: rc = launch_backward_ws<F16, 4>(grad, inputs, offsets, grad_embeddings, B, L, H, blc, &cfg, plan, w, s); break;
-        case NAF_BF16 * 16 + 2: rc = launch_backward_ws<BF16, 2>(grad, inputs, offsets, grad_embeddings, B, L, H, blc, &cfg, plan, w, s); break;
-        case NAF_BF16 * 16 + 4: rc = launch_backward_ws<BF16, 4>(grad, inputs, offsets, grad_embeddings, B, L, H, blc, &cfg, plan, w, s); break;
+        case NAF_F32 * 16 + 2: rc = binned_backward<F32, 2>(grad, inputs, offsets, grad_embeddings, B, blc, &cfg, plan, w, s); break;
+        case NAF_F32 * 16 + 4: rc = binned_backward<F32, 4>(grad, inputs, offsets, grad_embeddings, B, blc, &cfg, plan, w, s); break;
+        case NAF_F16 * 16 + 2: rc = binned_backward<F16, 2>(grad, inputs, offsets, grad_embeddings, B, blc, &cfg, plan, w, s); break;
+        case NAF_F16 * 16 + 4: rc = binned_backward<F16, 4>(grad, inputs, offsets, grad_embeddings, B, blc, &cfg, plan, w, s); break;
+        case NAF_BF16 * 16 + 2: rc = binned_backward<BF16, 2>(grad, inputs, offsets, grad_embeddings, B, blc, &cfg, plan, w, s); break;
+        case NAF_BF16 * 16 + 4: rc = binned_backward<BF16, 4>(grad, inputs, offsets, grad_embeddings, B, blc, &cfg, plan, w, s); break;
         default: return fail(NAF_ERR_UNSUPPORTED, "hash_encode_backward_ws: dtype must be NAF_F32, NAF_F16 or NAF_BF16");
     }
     if (rc != NAF_OK || !calc_grad_inputs) return rc;

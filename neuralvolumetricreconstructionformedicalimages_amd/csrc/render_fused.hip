@@ -16,6 +16,7 @@
 //     below 2^13 points per call, with mlp_grad_reduce_kernel as a launch of its own (also on data-parallel steps).
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <type_traits>
 
@@ -926,7 +927,7 @@ mlp16_backward_kernel(const uint16_t *__restrict__ feat, const float *__restrict
 }
 
 // ---- 5: slabs -> grad_mlp (+=), loss, gradient maximum: slab_reduce_block (mlp_slabs.h), as a launch of its own ----------------
-// (training steps on the binned scatter let spare workgroups of scatter_bin_kernel do it instead: run_binned_scatter)
+// (training steps on the binned scatter let spare workgroups of scatter_bin_kernel do it instead: launch_binned_scatter)
 __global__ void __launch_bounds__(1024)
 mlp_grad_reduce_kernel(SlabReduce sr) {
     __shared__ float part[kReduceGroups][kReduceParams];
@@ -936,16 +937,6 @@ mlp_grad_reduce_kernel(SlabReduce sr) {
 // ---- host side ----------------------------------------------------------------------------------------------
 constexpr uint32_t kBackwardBlocks = 512;   // 2 workgroups of 4 waves per CU; also the number of dW slabs
 constexpr uint32_t kBackwardBlocks16 = 768; // the 16-point bf16 kernel fits three workgroups per CU (0.89 -> 0.835 ms at 65 536 rays)
-
-// Raise a kernel's dynamic-LDS limit.  The attribute is per device and the call is a cheap host-side table update, so it
-// is simply made before every launch of a kernel that may need more than the default: no cached flag to go stale when the
-// same process drives a second GPU or a second thread (the ABI takes a stream per call and keeps no state of its own).
-template <typename K>
-static int raise_lds_limit(K kernel, uint32_t bytes, const char *who) {
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return fail(NAF_ERR_LAUNCH, who);
-    return NAF_OK;
-}
 
 template <typename P>
 static uint32_t forward_lds_bytes() { return ((MlpShared<P>::kBytes + 15u) & ~15u) + 4u * kMaxSamplesLds * 4u; }
@@ -959,10 +950,7 @@ static uint32_t backward_lds_bytes() {
 struct Workspace {
     unsigned char *feat, *dfeat;
     float *slabs, *grad_acc;
-    unsigned char *regions;      // binned scatter: record blocks [level slot][tile][slots], bucket-sorted per tile
-    uint32_t *counts;            //                 run words [level slot][bucket][tile] = start | length << 16
-    uint32_t *overflow;          //                 contributions that fell back to atomics (diagnostic counter)
-    uint32_t *gmax;              //                 bit pattern of max |feature gradient| of the step (fixed-point scale)
+    BinRegions bin;              // binned scatter only (scatter_host.h)
     BinPlan plan;
     bool binned;
     size_t bytes;
@@ -980,18 +968,10 @@ static Workspace carve(void *base, const naf_render_cfg *cfg, uint64_t n_points)
     w.grad_acc = (float *)((unsigned char *)w.slabs + slab_bytes);
     w.bytes = 2 * feat_bytes + slab_bytes + ((n_rays_max * 4 + 255) & ~(size_t)255) + 512;      // + partial sums of the loss
     w.binned = make_bin_plan(cfg, n_points, &w.plan);
-    w.regions = nullptr;
-    w.counts = nullptr;
-    w.overflow = nullptr;
-    w.gmax = nullptr;
+    w.bin = BinRegions{};
     if (w.binned) {
-        const size_t n_runs = ((size_t)w.plan.levels_per_pass << w.plan.log2_nb) * w.plan.n_tiles;
-        const size_t block_bytes = ((size_t)w.plan.levels_per_pass * w.plan.n_tiles * w.plan.slots * record_bytes(cfg) + 255) & ~(size_t)255;
-        w.regions = (unsigned char *)base + w.bytes;
-        w.counts = (uint32_t *)(w.regions + block_bytes);
-        w.overflow = w.counts + n_runs;                      // [0] total, [1 + level] per level
-        w.gmax = w.overflow + 33;
-        w.bytes += block_bytes + (((n_runs + 33 + 1) * 4 + 255) & ~(size_t)255);
+        w.bin = carve_bin_regions((unsigned char *)base + w.bytes, cfg, w.plan);
+        w.bytes += w.bin.bytes;
     }
     return w;
 }
@@ -1123,164 +1103,61 @@ static int run_mlp_backward(const void *feat, const float *mlp, const SrcRays &s
     return run_mlp_grad_reduce(slabs, grid, grad_mlp, loss_out, with_loss, madam, gmax_bits, ex, s);
 }
 
-// The Adam tail (naf_render_train_adam) needs every reducer launch of the step unsplit, the binned scatter and level-major launches.
-static bool adam_tail_possible(const naf_render_cfg *cfg, const Workspace &w) {
+// The Adam tail (naf_render_train_adam, naf_levels_scatter) needs the binned scatter, level-major launches and every reducer launch
+// over the levels [lv_begin, lv_end) unsplit.
+static bool adam_tail_possible(const naf_render_cfg *cfg, const Workspace &w, uint32_t lv_begin, uint32_t lv_end) {
     if (!w.binned || per_level_launches(cfg)) return false;
     const uint32_t NB = 1u << w.plan.log2_nb;
-    for (uint32_t l0 = 0; l0 < cfg->L; l0 += w.plan.levels_per_pass)
-        if (reducer_split(NB, std::min(w.plan.levels_per_pass, cfg->L - l0)) != 1u) return false;
+    for (uint32_t l0 = lv_begin; l0 < lv_end; l0 += w.plan.levels_per_pass)
+        if (reducer_split(NB, std::min(w.plan.levels_per_pass, lv_end - l0)) != 1u) return false;
     return true;
 }
 
-template <typename P, uint32_t C, typename Rec>
-static int run_binned_scatter(const SrcRays &src, const void *dfeat, const int32_t *offsets, float *grad_table, uint32_t B,
-                              const naf_render_cfg *cfg, const Workspace &w, uint32_t lv_begin, uint32_t lv_end,
-                              const naf_grad_buckets *buckets, hipStream_t s, const AdamTail *adam = nullptr, const SlabReduce *slab_job = nullptr) {
-    using FT = typename P::feat_t;
-    constexpr uint32_t NT = BinShape<Rec>::kThreads, PTS = BinShape<Rec>::kPoints;
-    // levels per bin workgroup: all of them when there are enough tiles to fill the chip several times over (the sample
-    // position is evaluated once per point, and stores drain behind the next level: 3.85 -> 3.53 ms at 65 536 rays),
-    // four when tiles are scarce (1 024-ray steps: 0.093 -> 0.071 ms)
-    constexpr uint32_t kLvMany = 16u, kLvFew = 4u;
-    const BinPlan &plan = w.plan;
-    constexpr bool kHasBig = sizeof(Rec) <= 12;                 // the 1024-thread shape of pass 1 (make_bin_plan)
-    const bool big = kHasBig && plan.tile_points == 2u * NT * PTS;
-    if (!big && plan.tile_points != NT * PTS) return fail(NAF_ERR_LAUNCH, "binned scatter: plan / kernel tile mismatch");
-    const uint32_t threads = big ? 2u * NT : NT;
-    const bool many = plan.n_tiles >= (big ? 768u : 1536u);
-    const uint32_t LV = many ? kLvMany : kLvFew;
-    auto bin = many ? scatter_bin_kernel<FT, C, SrcRays, Rec, NT, PTS, kLvMany> : scatter_bin_kernel<FT, C, SrcRays, Rec, NT, PTS, kLvFew>;
-    if constexpr (kHasBig) {
-        if (big) bin = many ? scatter_bin_kernel<FT, C, SrcRays, Rec, 2u * NT, PTS, kLvMany> : scatter_bin_kernel<FT, C, SrcRays, Rec, 2u * NT, PTS, kLvFew>;
-    }
-    auto red = adam != nullptr ? scatter_reduce_kernel<C, Rec, true> : scatter_reduce_kernel<C, Rec, false>;
-    const AdamTail tail = adam != nullptr ? *adam : AdamTail{};
-    const uint32_t NB = 1u << plan.log2_nb;
-    const uint32_t red_lds = plan.max_local_rows * C * 8u;
-    const uint32_t bin_lds = (2u * NB + 4u) * 4u + plan.slots * (uint32_t)sizeof(Rec);
-    if (int rc = raise_lds_limit(red, red_lds, "binned scatter: cannot raise dynamic LDS limit (reduce)")) return rc;
-    if (int rc = raise_lds_limit(bin, bin_lds, "binned scatter: cannot raise dynamic LDS limit (bin)")) return rc;
-    static const char *const bin_names[32] = NAF_LEVEL_NAMES("scatter_bin_kernel_L");
-    static const char *const red_names[32] = NAF_LEVEL_NAMES("scatter_reduce_kernel_L");
-    const bool per_level = per_level_launches(cfg);
-    // pass 1 over the levels [l0, l0 + nl): their records fill the region buffer from level slot 0.  The first launch carries the
-    // reduction of the MLP backward's slabs when the caller deferred it (StepExtras): kSlabReduceBlocks workgroups behind the tiles.
-    SlabReduce job{};
-    if (slab_job != nullptr) job = *slab_job;
-    auto launch_bin = [&](uint32_t l0, uint32_t nl) -> int {
-        ProfScope prof_(per_level ? level_name(bin_names, l0) : "scatter_bin_kernel", s);
-        const uint32_t spare = job.slabs != nullptr ? kSlabReduceBlocks : 0u;
-        hipLaunchKernelGGL(bin, dim3(plan.n_tiles + spare, (nl + LV - 1u) / LV), dim3(threads), bin_lds, s, src, (const typename FT::store_t *)dfeat,
-                           offsets, grad_table, (Rec *)w.regions, w.counts, w.overflow, B, cfg->H, l0, nl, plan, job, B, 1u);
-        job = SlabReduce{};
-        return check_launch("scatter_bin_kernel");
-    };
-    // pass 2 over the level slots [ly0, ly0 + nl) of a bin pass that started at level l0
-    auto launch_reduce = [&](uint32_t l0, uint32_t ly0, uint32_t nl) -> int {
-        ProfScope prof_(per_level ? level_name(red_names, l0 + ly0) : "scatter_reduce_kernel", s);
-        // keep >= ~1024 reducer workgroups in flight: with one or two levels per pass split each bucket's tiles.
-        // (A reducer workgroup owns a CU's LDS, so 256 run at a time: 512 or more unsplit ones already come in full rounds.)
-        const uint32_t n_split = reducer_split(NB, nl);
-        if (adam != nullptr && n_split != 1u) return fail(NAF_ERR_LAUNCH, "binned scatter: the Adam tail needs unsplit reducer launches");
-        hipLaunchKernelGGL(red, dim3(NB, nl, n_split), dim3(1024), red_lds, s, (const Rec *)w.regions, w.counts, offsets,
-                           grad_table, w.gmax, l0, ly0, cfg->H, plan, tail);
-        return check_launch("scatter_reduce_kernel");
-    };
-    if (buckets != nullptr && !per_level && plan.levels_per_pass >= cfg->L && lv_begin == 0u && lv_end == cfg->L) {
-        // data parallel, and the records of all levels fit one pass: bin ONCE (the sample position is evaluated once per
-        // point and the stores of a level drain behind the next, exactly as in the single-GPU step), then finish the table
-        // bucket by bucket -- each bucket's event fires as soon as its rows are final, and its all-reduce overlaps the
-        // reduction of the buckets that follow.
-        if (int rc = launch_bin(0u, cfg->L)) return rc;
-        for (uint32_t b = 0; b < buckets->n_buckets; ++b) {
-            if (int rc = launch_reduce(0u, buckets->level_begin[b], buckets->level_end[b] - buckets->level_begin[b])) return rc;
-            if (buckets->ready[b] != nullptr && hipEventRecord((hipEvent_t)buckets->ready[b], s) != hipSuccess)
-                return fail(NAF_ERR_LAUNCH, "render_train: cannot record a bucket event");
-        }
-        return NAF_OK;
-    }
-    for (uint32_t l0 = lv_begin; l0 < lv_end; l0 += plan.levels_per_pass) {
-        const uint32_t nl = std::min(plan.levels_per_pass, lv_end - l0);
-        if (int rc = launch_bin(l0, nl)) return rc;
-        if (int rc = launch_reduce(l0, 0u, nl)) return rc;
-    }
-    return NAF_OK;
-}
-
-// The same launch plan with the kernels of scatter_v2.h (8-byte records; the canonical two-channel bf16 shape).
-static int run_binned_scatter2(const SrcRays &src, const void *dfeat, const int32_t *offsets, float *grad_table, uint32_t B,
-                               const naf_render_cfg *cfg, const Workspace &w, uint32_t lv_begin, uint32_t lv_end,
-                               const naf_grad_buckets *buckets, hipStream_t s, const AdamTail *adam = nullptr, const SlabReduce *slab_job = nullptr,
-                               DrawJob *next_draw = nullptr, const GradBlocks *from_blocks = nullptr) {
+// The record family of scatter_v2.h (launch_binned_scatter, scatter_host.h): 8-byte records, the canonical two-channel bf16 shape.  Pass 1 also runs the next step's pixel draw
+// when the caller hands one over, and on the level-parallel path reads the all-to-all's gradient blocks in place (`from_blocks`).
 #ifndef NAF_V2_LV_FEW
 #define NAF_V2_LV_FEW 4u      // levels per bin workgroup when tiles are scarce.  A/B builds (tools/build_variant.sh) override it: 2 gains 2 us at
                               // 512 rays and loses 9 at 4 096, 8 the other way round (profiles/round4_ab_reducer_nt_loads_and_levels_per_bin_workgroup.jsonl)
 #endif
-    constexpr uint32_t NT = 512u, PTS = 2u, kLvMany = 16u, kLvFew = NAF_V2_LV_FEW;
-    const BinPlan &plan = w.plan;
-    const bool big = plan.tile_points == 2u * NT * PTS;
-    if (!big && plan.tile_points != NT * PTS) return fail(NAF_ERR_LAUNCH, "binned scatter: plan / kernel tile mismatch");
-    const uint32_t threads = big ? 2u * NT : NT;
-    const bool many = plan.n_tiles >= (big ? 768u : 1536u);
-    const uint32_t LV = many ? kLvMany : kLvFew;
-    // 64 buckets per level (every table up to 2^19 rows per level): the variant whose waves scan the bucket counters themselves
-    const bool nb64 = plan.log2_nb == 6u;
-    auto bin = big ? (many ? scatter_bin2_kernel<2u * NT, kLvMany, 0u> : scatter_bin2_kernel<2u * NT, kLvFew, 0u>)
-                   : nb64 ? (many ? scatter_bin2_kernel<NT, kLvMany, 6u> : scatter_bin2_kernel<NT, kLvFew, 6u>)
-                          : (many ? scatter_bin2_kernel<NT, kLvMany, 0u> : scatter_bin2_kernel<NT, kLvFew, 0u>);
-    if (from_blocks != nullptr)      // level-parallel: `dfeat` = the all-to-all's blocks, read in place (scatter_v2.h, GradBlocks)
-        bin = big ? (many ? scatter_bin2_kernel<2u * NT, kLvMany, 0u, true> : scatter_bin2_kernel<2u * NT, kLvFew, 0u, true>)
-                  : nb64 ? (many ? scatter_bin2_kernel<NT, kLvMany, 6u, true> : scatter_bin2_kernel<NT, kLvFew, 6u, true>)
-                         : (many ? scatter_bin2_kernel<NT, kLvMany, 0u, true> : scatter_bin2_kernel<NT, kLvFew, 0u, true>);
-    const GradBlocks gb = from_blocks != nullptr ? *from_blocks : GradBlocks{};
-    const bool fast = adam != nullptr && adam->lp != nullptr;        // tables with a 16-bit shadow: adam_math.h
-    auto red = adam == nullptr ? scatter_reduce2_kernel<false, false> : fast ? scatter_reduce2_kernel<true, true> : scatter_reduce2_kernel<true, false>;
-    const AdamTail tail = adam != nullptr ? *adam : AdamTail{};
-    const uint32_t NB = 1u << plan.log2_nb;
-    const uint32_t red_lds = plan.max_local_rows * 2u * 8u;
-    const uint32_t bin_lds = (3u * NB + 4u) * 4u + (plan.slots + 1u) * (uint32_t)sizeof(PairFx) + side_list_capacity(plan.slots) * 12u;      // counters, staging, side list
-    if (int rc = raise_lds_limit(red, red_lds, "binned scatter: cannot raise dynamic LDS limit (reduce)")) return rc;
-    if (int rc = raise_lds_limit(bin, bin_lds, "binned scatter: cannot raise dynamic LDS limit (bin)")) return rc;
-    static const char *const bin_names[32] = NAF_LEVEL_NAMES("scatter_bin_kernel_L");
-    static const char *const red_names[32] = NAF_LEVEL_NAMES("scatter_reduce_kernel_L");
-    const bool per_level = per_level_launches(cfg);
-    SlabReduce job{};
-    if (slab_job != nullptr) job = *slab_job;
-    auto launch_bin = [&](uint32_t l0, uint32_t nl) -> int {
-        ProfScope prof_(per_level ? level_name(bin_names, l0) : "scatter_bin_kernel", s);
-        // the first launch of the step also carries the next step's pixel draw when the caller handed one over (spare workgroups)
+struct FxRecords {
+    using Rec = PairFx;
+    static constexpr uint32_t kThreads = 512u, kPoints = 2u, kLvMany = 16u, kLvFew = NAF_V2_LV_FEW;
+    static constexpr bool kHasBig = true;
+    const SrcRays &src;
+    const void *dfeat;
+    uint32_t B;
+    DrawJob *next_draw;                  // taken along by the first launch, which sets its count to 0
+    const GradBlocks *from_blocks;
+
+    template <bool kFromBlocks>
+    static auto bin_kernel_of(bool big, bool nb64, bool many) {
+        constexpr uint32_t NT = kThreads;
+        return big ? (many ? scatter_bin2_kernel<2u * NT, kLvMany, 0u, kFromBlocks> : scatter_bin2_kernel<2u * NT, kLvFew, 0u, kFromBlocks>)
+                   : nb64 ? (many ? scatter_bin2_kernel<NT, kLvMany, 6u, kFromBlocks> : scatter_bin2_kernel<NT, kLvFew, 6u, kFromBlocks>)
+                          : (many ? scatter_bin2_kernel<NT, kLvMany, 0u, kFromBlocks> : scatter_bin2_kernel<NT, kLvFew, 0u, kFromBlocks>);
+    }
+    auto bin_kernel(const BinPlan &plan, bool big, bool many) const {
+        // 64 buckets per level (every table up to 2^19 rows per level): the variant whose waves scan the bucket counters themselves
+        const bool nb64 = plan.log2_nb == 6u;
+        return from_blocks != nullptr ? bin_kernel_of<true>(big, nb64, many) : bin_kernel_of<false>(big, nb64, many);
+    }
+    auto reduce_kernel(const AdamTail *adam) const {
+        const bool fast = adam != nullptr && adam->lp != nullptr;        // tables with a 16-bit shadow: adam_math.h
+        return adam == nullptr ? scatter_reduce2_kernel<false, false> : fast ? scatter_reduce2_kernel<true, true> : scatter_reduce2_kernel<true, false>;
+    }
+    uint32_t bin_lds(const BinPlan &plan) const {      // counters, staging, side list
+        return (3u * (1u << plan.log2_nb) + 4u) * 4u + (plan.slots + 1u) * (uint32_t)sizeof(PairFx) + side_list_capacity(plan.slots) * 12u;
+    }
+    template <typename K>
+    void launch_bin(K bin, dim3 grid, uint32_t threads, uint32_t lds, hipStream_t s, const BinPass &p) const {
         DrawJob dj{};
-        if (next_draw != nullptr && next_draw->count != 0u) { dj = *next_draw; next_draw->count = 0u; }      // consumed
-        const uint32_t spare = (job.slabs != nullptr ? kSlabReduceBlocks : 0u) + (dj.count + threads - 1u) / threads;
-        hipLaunchKernelGGL(bin, dim3(plan.n_tiles + spare, (nl + LV - 1u) / LV), dim3(threads), bin_lds, s, src, (const uint16_t *)dfeat,
-                           offsets, grad_table, (PairFx *)w.regions, w.counts, w.overflow, B, cfg->H, l0, nl, plan, job, dj, gb);
-        job = SlabReduce{};
-        return check_launch("scatter_bin_kernel");
-    };
-    auto launch_reduce = [&](uint32_t l0, uint32_t ly0, uint32_t nl) -> int {
-        ProfScope prof_(per_level ? level_name(red_names, l0 + ly0) : "scatter_reduce_kernel", s);
-        const uint32_t n_split = reducer_split(NB, nl);
-        if (adam != nullptr && n_split != 1u) return fail(NAF_ERR_LAUNCH, "binned scatter: the Adam tail needs unsplit reducer launches");
-        hipLaunchKernelGGL(red, dim3(NB, nl, n_split), dim3(1024), red_lds, s, (const PairFx *)w.regions, w.counts, offsets,
-                           grad_table, w.gmax, l0, ly0, cfg->H, plan, tail);
-        return check_launch("scatter_reduce_kernel");
-    };
-    if (buckets != nullptr && !per_level && plan.levels_per_pass >= cfg->L && lv_begin == 0u && lv_end == cfg->L) {
-        if (int rc = launch_bin(0u, cfg->L)) return rc;              // data parallel: bin once, finish the table bucket by bucket (see above)
-        for (uint32_t b = 0; b < buckets->n_buckets; ++b) {
-            if (int rc = launch_reduce(0u, buckets->level_begin[b], buckets->level_end[b] - buckets->level_begin[b])) return rc;
-            if (buckets->ready[b] != nullptr && hipEventRecord((hipEvent_t)buckets->ready[b], s) != hipSuccess)
-                return fail(NAF_ERR_LAUNCH, "render_train: cannot record a bucket event");
-        }
-        return NAF_OK;
+        if (next_draw != nullptr && next_draw->count != 0u) { dj = *next_draw; next_draw->count = 0u; }
+        grid.x += (dj.count + threads - 1u) / threads;                    // the draw's spare workgroups
+        const GradBlocks gb = from_blocks != nullptr ? *from_blocks : GradBlocks{};
+        hipLaunchKernelGGL(bin, grid, dim3(threads), lds, s, src, (const uint16_t *)dfeat, p.offsets, p.grad_table, (PairFx *)p.w.regions,
+                           p.w.counts, p.w.overflow, B, p.H, p.l0, p.nl, p.plan, p.job, dj, gb);
     }
-    for (uint32_t l0 = lv_begin; l0 < lv_end; l0 += plan.levels_per_pass) {
-        const uint32_t nl = std::min(plan.levels_per_pass, lv_end - l0);
-        if (int rc = launch_bin(l0, nl)) return rc;
-        if (int rc = launch_reduce(l0, 0u, nl)) return rc;
-    }
-    return NAF_OK;
-}
+};
 
 // Table-gradient scatter of the levels [lv_begin, lv_end).
 template <typename P, uint32_t C>
@@ -1291,9 +1168,17 @@ static int run_hash_backward_levels(const SrcRays &src, const void *dfeat, const
     using FT = typename P::feat_t;
     if (from_blocks != nullptr && !(w.binned && scatter_v2(cfg))) return fail(NAF_ERR_LAUNCH, "hash backward: only the 8-byte-record scatter reads gradient blocks in place");
     if (w.binned) {
-        if (scatter_v2(cfg)) return run_binned_scatter2(src, dfeat, offsets, grad_table, B, cfg, w, lv_begin, lv_end, buckets, s, adam, slab_job, next_draw, from_blocks);
-        if (cfg->mlp_precision == NAF_F32) return run_binned_scatter<P, C, PairF32<C>>(src, dfeat, offsets, grad_table, B, cfg, w, lv_begin, lv_end, buckets, s, adam, slab_job);
-        return run_binned_scatter<P, C, PairBF16<C>>(src, dfeat, offsets, grad_table, B, cfg, w, lv_begin, lv_end, buckets, s, adam, slab_job);
+        if (scatter_v2(cfg)) {
+            FxRecords fam{src, dfeat, B, next_draw, from_blocks};
+            return launch_binned_scatter(fam, cfg, w.plan, w.bin, offsets, grad_table, lv_begin, lv_end, buckets, s, adam, slab_job);
+        }
+        // fp32 records in parity mode, bf16 ones packed in pairs otherwise; the features are [L, B, C]: strides (B, 1)
+        if (cfg->mlp_precision == NAF_F32) {
+            PairRecords<FT, C, SrcRays, PairF32<C>, 16u, true> fam{src, dfeat, B, B, 1u};
+            return launch_binned_scatter(fam, cfg, w.plan, w.bin, offsets, grad_table, lv_begin, lv_end, buckets, s, adam, slab_job);
+        }
+        PairRecords<FT, C, SrcRays, PairBF16<C>, 16u, true> fam{src, dfeat, B, B, 1u};
+        return launch_binned_scatter(fam, cfg, w.plan, w.bin, offsets, grad_table, lv_begin, lv_end, buckets, s, adam, slab_job);
     }
     if (adam != nullptr) return fail(NAF_ERR_LAUNCH, "hash backward: the Adam tail needs the binned scatter");
     if (per_level_launches(cfg)) {
@@ -1402,7 +1287,7 @@ static int render_backward_impl(const float *rays, const float *t_rand, const fl
     AdamTail tail;
     if (adam != nullptr) {                                   // the overflow counters live in this call's workspace
         tail = *adam;
-        tail.overflow = w.overflow;
+        tail.overflow = w.bin.overflow;
         adam = &tail;
     }
     // (a fused forward of the same cfg left no features behind unless it was asked to store them)
@@ -1413,8 +1298,8 @@ static int render_backward_impl(const float *rays, const float *t_rand, const fl
     // `mlp_ready`), per-level diagnostics keep their launches apart.
     SlabReduce job{};
     const bool defer = w.binned && buckets == nullptr && !per_level_launches(cfg);
-    const StepExtras ex{w.binned ? w.overflow : nullptr, loss_assign, defer ? &job : nullptr};
-    if (int rc = run_mlp_backward<P, C>(w.feat, mlp, src, grad_acc, loss, w.dfeat, w.slabs, w.binned ? w.gmax : nullptr, grad_mlp, loss_out, madam, n_rays, B, cfg,
+    const StepExtras ex{w.bin.overflow, loss_assign, defer ? &job : nullptr};
+    if (int rc = run_mlp_backward<P, C>(w.feat, mlp, src, grad_acc, loss, w.dfeat, w.slabs, w.bin.gmax, grad_mlp, loss_out, madam, n_rays, B, cfg,
                                         ex, s)) return rc;
     // grad_mlp (and, in the training entry point, the loss) are final here, before the table scatter starts
     if (buckets != nullptr && buckets->mlp_ready != nullptr && hipEventRecord((hipEvent_t)buckets->mlp_ready, s) != hipSuccess)
@@ -1511,14 +1396,6 @@ levels_gather_kernel(const unsigned char *__restrict__ blocks, size_t block_stri
     }
 }
 
-static bool adam_tail_possible_levels(const naf_render_cfg *cfg, const Workspace &w, uint32_t lv_begin, uint32_t lv_end) {
-    if (!w.binned || per_level_launches(cfg)) return false;
-    const uint32_t NB = 1u << w.plan.log2_nb;
-    for (uint32_t l0 = lv_begin; l0 < lv_end; l0 += w.plan.levels_per_pass)
-        if (reducer_split(NB, std::min(w.plan.levels_per_pass, lv_end - l0)) != 1u) return false;
-    return true;
-}
-
 template <typename P, uint32_t C>
 static int levels_encode_impl(const float *rays, const float *t_rand, const void *emb, const int32_t *offsets, void *features, uint32_t n_rays,
                               const naf_render_cfg *cfg, uint32_t lv_begin, uint32_t lv_end, uint32_t n_ranks, hipStream_t s) {
@@ -1549,13 +1426,13 @@ static int levels_scatter_impl(const float *rays, const float *t_rand, const voi
     const Workspace w = carve(ws, cfg, B);
     const SrcRays src = make_src(rays, t_rand, cfg);
     const uint32_t run = B / n_ranks * C;                                        // elements of one (rank, level)
-    uint32_t *gmax = w.binned ? w.gmax : reinterpret_cast<uint32_t *>(w.grad_acc);      // (the atomic scatter has no use for it)
+    uint32_t *gmax = w.binned ? w.bin.gmax : reinterpret_cast<uint32_t *>(w.grad_acc);      // (the atomic scatter has no use for it)
     if (w.binned) {
-        if (hipMemsetAsync(w.overflow, 0, 34 * sizeof(uint32_t), s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "levels_scatter: memset failed");      // counters + maximum
+        if (hipMemsetAsync(w.bin.overflow, 0, 34 * sizeof(uint32_t), s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "levels_scatter: memset failed");      // counters + maximum
     } else if (hipMemsetAsync(gmax, 0, sizeof(uint32_t), s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "levels_scatter: memset failed");
     AdamTail tail;
-    const bool fuse = adam != nullptr && adam_tail_possible_levels(cfg, w, lv_begin, lv_end);
-    if (fuse) { tail = *adam; tail.overflow = w.overflow; }
+    const bool fuse = adam != nullptr && adam_tail_possible(cfg, w, lv_begin, lv_end);
+    if (fuse) { tail = *adam; tail.overflow = w.bin.overflow; }
     if (adam_applied != nullptr) *adam_applied = fuse ? 1 : 0;
     // The canonical shape (two bf16 channels, 8-byte records) reads the blocks in place: pass 1 finds a point's gradient inside its
     // rank's block and takes the maximum on its way (scatter_v2.h, GradBlocks).  Other shapes, the fp32 parity mode and
@@ -1615,7 +1492,7 @@ extern "C" int naf_scatter_overflow_count(const naf_render_cfg *cfg, uint64_t n_
     const Workspace w = carve(const_cast<void *>(workspace), cfg, n_points);
     *count_host = 0;
     if (!w.binned) return NAF_OK;
-    if (hipMemcpy(count_host, w.overflow, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(NAF_ERR_LAUNCH, "scatter_overflow_count: copy failed");
+    if (hipMemcpy(count_host, w.bin.overflow, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(NAF_ERR_LAUNCH, "scatter_overflow_count: copy failed");
     return NAF_OK;
 }
 
@@ -1624,7 +1501,7 @@ extern "C" int naf_scatter_overflow_levels(const naf_render_cfg *cfg, uint64_t n
     const Workspace w = carve(const_cast<void *>(workspace), cfg, n_points);
     std::memset(counts_host, 0, 32 * sizeof(uint32_t));
     if (!w.binned) return NAF_OK;
-    if (hipMemcpy(counts_host, w.overflow + 1, 32 * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(NAF_ERR_LAUNCH, "scatter_overflow_levels: copy failed");
+    if (hipMemcpy(counts_host, w.bin.overflow + 1, 32 * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(NAF_ERR_LAUNCH, "scatter_overflow_levels: copy failed");
     return NAF_OK;
 }
 
@@ -1648,15 +1525,49 @@ static int check_depths(const naf_render_cfg *cfg, const float *t_rand) {
         return fail(NAF_ERR_INVALID_ARGUMENT, "render: NAF_CFG_EXPLICIT_DEPTHS needs the depths in t_rand");
     return NAF_OK;
 }
+// fail() with the message "<who>: <what>"
+static int fail_in(int code, const char *who, const char *what) {
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return fail(code, msg);
+}
+
+struct LevelRange { uint32_t begin, end; };
+
+// The checks a ray entry point opens with, in the one order all of them keep: the cfg, the depths, the level range of a level-parallel
+// call (`levels`); then, for a batch that is not empty, the buffers (`missing`: one the call needs is null) and the rank count
+// (`n_ranks`, naf_levels_scatter); then n_samples >= 2 and the point count, which calls with `empty_ok` skip for an empty batch too.
+static int check_ray_call(const char *who, const naf_render_cfg *cfg, const float *t_rand, uint32_t n_rays, bool missing, bool empty_ok = false,
+                          const LevelRange *levels = nullptr, const uint32_t *n_ranks = nullptr) {
+    if (int rc = check_cfg(cfg, who)) return rc;
+    if (int rc = check_depths(cfg, t_rand)) return rc;
+    if (levels != nullptr && (levels->begin >= levels->end || levels->end > cfg->L))
+        return fail(NAF_ERR_INVALID_ARGUMENT, "levels: empty or out-of-range level range");
+    if (n_rays == 0 && empty_ok) return NAF_OK;
+    if (n_rays != 0 && missing) return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "null pointer");
+    if (n_ranks != nullptr && (*n_ranks == 0 || n_rays % *n_ranks != 0))
+        return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "every rank must contribute the same number of rays");
+    if (cfg->n_samples < 2) return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "n_samples must be >= 2");
+    return check_points((uint64_t)n_rays * cfg->n_samples);
+}
+
+// naf_table_adam -> the reducer's Adam tail, after the checks every entry point that takes one makes (`who` names it)
+static int make_adam_tail(const char *who, const naf_table_adam *adam, const float *grad_embeddings, AdamTail *tail) {
+    if (adam->step == 0) return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "step is 1-based");
+    if (adam->param_lp != nullptr && adam->lp_dtype != NAF_F16 && adam->lp_dtype != NAF_BF16)
+        return fail_in(NAF_ERR_UNSUPPORTED, who, "lp_dtype must be NAF_F16 or NAF_BF16 when param_lp is given");
+    if (((uintptr_t)adam->param | (uintptr_t)adam->exp_avg | (uintptr_t)adam->exp_avg_sq | (uintptr_t)grad_embeddings) & 15u)
+        return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "buffers must be 16-byte aligned");
+    tail->param = adam->param; tail->m = adam->exp_avg; tail->v = adam->exp_avg_sq;
+    tail->lp = adam->param_lp; tail->lp_dtype = adam->lp_dtype; tail->overflow = nullptr;
+    tail->a = make_adam_args(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, adam->grad_scale);
+    return NAF_OK;
+}
 
 extern "C" int naf_render_forward(const float *rays, const float *t_rand, const void *embeddings, const int32_t *offsets,
                                   const float *mlp, float *acc, uint32_t n_rays, const naf_render_cfg *cfg, void *workspace,
                                   void *stream) {
-    if (int rc = check_cfg(cfg, "render_forward")) return rc;
-    if (int rc = check_depths(cfg, t_rand)) return rc;
-    if (n_rays != 0 && (!rays || !embeddings || !offsets || !mlp || !acc || !workspace)) return fail(NAF_ERR_INVALID_ARGUMENT, "render_forward: null pointer");
-    if (cfg->n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "render_forward: n_samples must be >= 2");
-    if (int rc = check_points((uint64_t)n_rays * cfg->n_samples)) return rc;
+    if (int rc = check_ray_call("render_forward", cfg, t_rand, n_rays, !rays || !embeddings || !offsets || !mlp || !acc || !workspace)) return rc;
     if (n_rays == 0) return NAF_OK;
     NAF_DISPATCH_PC(render_forward_impl, rays, t_rand, embeddings, offsets, mlp, acc, n_rays, cfg, workspace, (hipStream_t)stream);
 }
@@ -1664,11 +1575,7 @@ extern "C" int naf_render_forward(const float *rays, const float *t_rand, const 
 extern "C" int naf_render_forward_samples(const float *rays, const float *t_rand, const void *embeddings, const int32_t *offsets,
                                           const float *mlp, float *acc, float *sigma, float *optical_depth, uint32_t n_rays,
                                           const naf_render_cfg *cfg, void *workspace, void *stream) {
-    if (int rc = check_cfg(cfg, "render_forward_samples")) return rc;
-    if (int rc = check_depths(cfg, t_rand)) return rc;
-    if (n_rays != 0 && (!rays || !embeddings || !offsets || !mlp || !acc || !workspace)) return fail(NAF_ERR_INVALID_ARGUMENT, "render_forward_samples: null pointer");
-    if (cfg->n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "render_forward_samples: n_samples must be >= 2");
-    if (int rc = check_points((uint64_t)n_rays * cfg->n_samples)) return rc;
+    if (int rc = check_ray_call("render_forward_samples", cfg, t_rand, n_rays, !rays || !embeddings || !offsets || !mlp || !acc || !workspace)) return rc;
     if (n_rays == 0) return NAF_OK;
     NAF_DISPATCH_PC(render_forward_impl, rays, t_rand, embeddings, offsets, mlp, acc, n_rays, cfg, workspace, (hipStream_t)stream, sigma,
                     optical_depth);
@@ -1677,12 +1584,8 @@ extern "C" int naf_render_forward_samples(const float *rays, const float *t_rand
 extern "C" int naf_render_backward(const float *rays, const float *t_rand, const float *grad_acc, const void *embeddings,
                                    const int32_t *offsets, const float *mlp, float *grad_embeddings, float *grad_mlp,
                                    uint32_t n_rays, const naf_render_cfg *cfg, void *workspace, int features_valid, void *stream) {
-    if (int rc = check_cfg(cfg, "render_backward")) return rc;
-    if (int rc = check_depths(cfg, t_rand)) return rc;
-    if (n_rays != 0 && (!rays || !grad_acc || !embeddings || !offsets || !mlp || !grad_embeddings || !grad_mlp || !workspace))
-        return fail(NAF_ERR_INVALID_ARGUMENT, "render_backward: null pointer");
-    if (cfg->n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "render_backward: n_samples must be >= 2");
-    if (int rc = check_points((uint64_t)n_rays * cfg->n_samples)) return rc;
+    if (int rc = check_ray_call("render_backward", cfg, t_rand, n_rays,
+                                !rays || !grad_acc || !embeddings || !offsets || !mlp || !grad_embeddings || !grad_mlp || !workspace)) return rc;
     if (n_rays == 0) return NAF_OK;
     NAF_DISPATCH_PC(render_backward_impl, rays, t_rand, grad_acc, embeddings, offsets, mlp, grad_embeddings, grad_mlp, n_rays, cfg,
                     workspace, features_valid, nullptr, (hipStream_t)stream);
@@ -1707,12 +1610,9 @@ static int render_train_entry(const float *rays, const float *t_rand, const floa
                               float *grad_embeddings, float *grad_mlp, float *loss_out, uint32_t n_rays,
                               const naf_render_cfg *cfg, void *workspace, const naf_grad_buckets *buckets, void *stream,
                               const AdamTail *adam = nullptr, const MlpAdam *madam = nullptr, bool loss_assign = false, DrawJob *next_draw = nullptr) {
-    if (int rc = check_cfg(cfg, "render_train")) return rc;
-    if (int rc = check_depths(cfg, t_rand)) return rc;
-    if (n_rays != 0 && (!rays || !target || !ray_weight || !embeddings || !offsets || !mlp || !acc || !grad_embeddings || !grad_mlp || !workspace))
-        return fail(NAF_ERR_INVALID_ARGUMENT, "render_train: null pointer");
-    if (cfg->n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "render_train: n_samples must be >= 2");
-    if (int rc = check_points((uint64_t)n_rays * cfg->n_samples)) return rc;
+    if (int rc = check_ray_call("render_train", cfg, t_rand, n_rays,
+                                !rays || !target || !ray_weight || !embeddings || !offsets || !mlp || !acc || !grad_embeddings || !grad_mlp || !workspace))
+        return rc;
     if (buckets != nullptr)
         if (int rc = check_buckets(buckets, cfg->L)) return rc;
     if (n_rays == 0) {                                       // an empty shard still has to signal its (zero) gradients as final
@@ -1753,16 +1653,9 @@ static int render_train_adam_impl(const float *rays, const float *t_rand, const 
                                   const naf_render_cfg *cfg, void *workspace, const naf_table_adam *adam, void *stream, DrawJob *next_draw) {
     if (!adam) return fail(NAF_ERR_INVALID_ARGUMENT, "render_train_adam: null adam");
     if (!adam->param || !adam->exp_avg || !adam->exp_avg_sq || !grad_embeddings) return fail(NAF_ERR_INVALID_ARGUMENT, "render_train_adam: null pointer");
-    if (adam->step == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "render_train_adam: step is 1-based");
-    if (adam->param_lp != nullptr && adam->lp_dtype != NAF_F16 && adam->lp_dtype != NAF_BF16)
-        return fail(NAF_ERR_UNSUPPORTED, "render_train_adam: lp_dtype must be NAF_F16 or NAF_BF16 when param_lp is given");
-    if (((uintptr_t)adam->param | (uintptr_t)adam->exp_avg | (uintptr_t)adam->exp_avg_sq | (uintptr_t)grad_embeddings) & 15u)
-        return fail(NAF_ERR_INVALID_ARGUMENT, "render_train_adam: buffers must be 16-byte aligned");
-    if (int rc = check_cfg(cfg, "render_train_adam")) return rc;
     AdamTail tail;
-    tail.param = adam->param; tail.m = adam->exp_avg; tail.v = adam->exp_avg_sq;
-    tail.lp = adam->param_lp; tail.lp_dtype = adam->lp_dtype; tail.overflow = nullptr;
-    tail.a = make_adam_args(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, adam->grad_scale);
+    if (int rc = make_adam_tail("render_train_adam", adam, grad_embeddings, &tail)) return rc;
+    if (int rc = check_cfg(cfg, "render_train_adam")) return rc;
     // the MLP's own update rides on the slab reduction when the caller hands over its state (an empty batch still has to step it)
     MlpAdam madam{adam->mlp_param, adam->mlp_exp_avg, adam->mlp_exp_avg_sq, tail.a};
     const MlpAdam *mp = nullptr;
@@ -1773,7 +1666,7 @@ static int render_train_adam_impl(const float *rays, const float *t_rand, const 
         else if (int rc = launch_adam(adam->mlp_param, adam->mlp_exp_avg, adam->mlp_exp_avg_sq, grad_mlp, nullptr, 0, NAF_MLP_PARAMS, tail.a, true, (hipStream_t)stream)) return rc;
     }
     const uint64_t n_points = (uint64_t)n_rays * cfg->n_samples;
-    if (n_rays != 0 && workspace != nullptr && n_points < (1ull << 31) && adam_tail_possible(cfg, carve(workspace, cfg, n_points)))
+    if (n_rays != 0 && workspace != nullptr && n_points < (1ull << 31) && adam_tail_possible(cfg, carve(workspace, cfg, n_points), 0u, cfg->L))
         return render_train_entry(rays, t_rand, target, ray_weight, embeddings, offsets, mlp, acc, grad_embeddings, grad_mlp, loss_out,
                                   n_rays, cfg, workspace, nullptr, stream, &tail, mp, true, next_draw);
     // small batches (atomic scatter), split reducer launches, per-level diagnostics, empty batches: the two passes one after the other
@@ -1813,20 +1706,12 @@ extern "C" int naf_render_train_adam_draw(const float *rays, const float *t_rand
 }
 
 /* ---- level-parallel training (naf_hip.h) --------------------------------------------------------------------------------- */
-static int check_levels(const naf_render_cfg *cfg, uint32_t lv_begin, uint32_t lv_end, const char *who) {
-    if (lv_begin >= lv_end || lv_end > cfg->L) { (void)who; return fail(NAF_ERR_INVALID_ARGUMENT, "levels: empty or out-of-range level range"); }
-    return NAF_OK;
-}
 
 extern "C" int naf_levels_encode(const float *rays, const float *t_rand, const void *embeddings, const int32_t *offsets, void *features,
                                  uint32_t n_rays, uint32_t n_ranks, const naf_render_cfg *cfg, uint32_t level_begin, uint32_t level_end,
                                  void *stream) {
-    if (int rc = check_cfg(cfg, "levels_encode")) return rc;
-    if (int rc = check_depths(cfg, t_rand)) return rc;
-    if (int rc = check_levels(cfg, level_begin, level_end, "levels_encode")) return rc;
-    if (n_rays != 0 && (!rays || !embeddings || !offsets || !features)) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_encode: null pointer");
-    if (cfg->n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_encode: n_samples must be >= 2");
-    if (int rc = check_points((uint64_t)n_rays * cfg->n_samples)) return rc;
+    const LevelRange lv{level_begin, level_end};
+    if (int rc = check_ray_call("levels_encode", cfg, t_rand, n_rays, !rays || !embeddings || !offsets || !features, false, &lv)) return rc;
     if (n_rays == 0) return NAF_OK;
     if (n_ranks == 0 || n_rays % n_ranks != 0) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_encode: every rank must contribute the same number of rays");
     NAF_DISPATCH_PC(levels_encode_impl, rays, t_rand, embeddings, offsets, features, n_rays, cfg, level_begin, level_end, n_ranks, (hipStream_t)stream);
@@ -1835,16 +1720,13 @@ extern "C" int naf_levels_encode(const float *rays, const float *t_rand, const v
 extern "C" int naf_levels_field_step(const float *rays, const float *t_rand, const float *target, const float *ray_weight, const void *features,
                                      const float *mlp, float *acc, void *feature_grads, float *grad_mlp, float *loss_out, uint32_t n_rays,
                                      const naf_render_cfg *cfg, void *workspace, void *grads_ready, void *stream) {
-    if (int rc = check_cfg(cfg, "levels_field_step")) return rc;
-    if (int rc = check_depths(cfg, t_rand)) return rc;
+    if (int rc = check_ray_call("levels_field_step", cfg, t_rand, n_rays,
+                                !rays || !target || !ray_weight || !features || !mlp || !acc || !feature_grads || !grad_mlp || !loss_out || !workspace, true))
+        return rc;
     if (n_rays == 0) {
         if (grads_ready != nullptr && hipEventRecord((hipEvent_t)grads_ready, (hipStream_t)stream) != hipSuccess) return fail(NAF_ERR_LAUNCH, "levels_field_step: event");
         return NAF_OK;
     }
-    if (!rays || !target || !ray_weight || !features || !mlp || !acc || !feature_grads || !grad_mlp || !loss_out || !workspace)
-        return fail(NAF_ERR_INVALID_ARGUMENT, "levels_field_step: null pointer");
-    if (cfg->n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_field_step: n_samples must be >= 2");
-    if (int rc = check_points((uint64_t)n_rays * cfg->n_samples)) return rc;
     NAF_DISPATCH_PC(levels_field_impl, rays, t_rand, target, ray_weight, features, mlp, acc, feature_grads, grad_mlp, loss_out, n_rays, cfg,
                     workspace, (hipEvent_t)grads_ready, (hipStream_t)stream);
 }
@@ -1854,14 +1736,10 @@ extern "C" int naf_levels_scatter(const float *rays, const float *t_rand, const 
                                   uint32_t level_begin, uint32_t level_end, void *workspace, const naf_table_adam *adam, int *adam_applied,
                                   void *stream) {
     if (adam_applied != nullptr) *adam_applied = 0;
-    if (int rc = check_cfg(cfg, "levels_scatter")) return rc;
-    if (int rc = check_depths(cfg, t_rand)) return rc;
-    if (int rc = check_levels(cfg, level_begin, level_end, "levels_scatter")) return rc;
+    const LevelRange lv{level_begin, level_end};
+    if (int rc = check_ray_call("levels_scatter", cfg, t_rand, n_rays, !rays || !grad_blocks || !offsets || !grad_embeddings || !workspace, true, &lv,
+                                &n_ranks)) return rc;
     if (n_rays == 0) return NAF_OK;
-    if (!rays || !grad_blocks || !offsets || !grad_embeddings || !workspace) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: null pointer");
-    if (n_ranks == 0 || n_rays % n_ranks != 0) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: every rank must contribute the same number of rays");
-    if (cfg->n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: n_samples must be >= 2");
-    if (int rc = check_points((uint64_t)n_rays * cfg->n_samples)) return rc;
     const size_t esz = cfg->mlp_precision == NAF_F32 ? 4 : 2;
     if (block_stride_bytes < (size_t)(level_end - level_begin) * (n_rays / n_ranks) * cfg->n_samples * cfg->C * esz || block_stride_bytes % esz != 0)
         return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: block stride smaller than a rank's block");
@@ -1869,14 +1747,7 @@ extern "C" int naf_levels_scatter(const float *rays, const float *t_rand, const 
     const AdamTail *tp = nullptr;
     if (adam != nullptr) {
         if (!adam->param || !adam->exp_avg || !adam->exp_avg_sq) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: null optimiser state");
-        if (adam->step == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: step is 1-based");
-        if (adam->param_lp != nullptr && adam->lp_dtype != NAF_F16 && adam->lp_dtype != NAF_BF16)
-            return fail(NAF_ERR_UNSUPPORTED, "levels_scatter: lp_dtype must be NAF_F16 or NAF_BF16 when param_lp is given");
-        if (((uintptr_t)adam->param | (uintptr_t)adam->exp_avg | (uintptr_t)adam->exp_avg_sq | (uintptr_t)grad_embeddings) & 15u)
-            return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: buffers must be 16-byte aligned");
-        tail.param = adam->param; tail.m = adam->exp_avg; tail.v = adam->exp_avg_sq;
-        tail.lp = adam->param_lp; tail.lp_dtype = adam->lp_dtype; tail.overflow = nullptr;
-        tail.a = make_adam_args(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, adam->grad_scale);
+        if (int rc = make_adam_tail("levels_scatter", adam, grad_embeddings, &tail)) return rc;
         tp = &tail;
     }
     NAF_DISPATCH_PC(levels_scatter_impl, rays, t_rand, grad_blocks, block_stride_bytes, n_ranks, offsets, grad_embeddings, n_rays, cfg, level_begin,
