@@ -9,6 +9,7 @@ the concatenated batch.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -175,9 +176,26 @@ def sharded_exchange_slices(slices, world, padded_end):
     return out
 
 
+def padded_length(n, world):
+    """Length of a flat table buffer of `n` elements: the next multiple of lcm(64, 4 * world), so that every exchange range of a
+    data-parallel step (sharded_exchange_slices) splits into `world` equal shards that start on 16-byte boundaries."""
+    unit = math.lcm(64, 4 * int(world))
+    return (n + unit - 1) // unit * unit
+
+
+def shard_bounds(a, b, world, rank, n_valid):
+    """This rank's shard of the exchange range [a, b): (lo, end, hi) -- the shard is [lo, end), 1/world of the range, and hi is
+    `end` clipped to the `n_valid` elements of the table (the last shard of the last range reaches into the padding; hi == lo
+    when it lies there entirely)."""
+    sh = (b - a) // world
+    lo = a + rank * sh
+    return lo, lo + sh, max(lo, min(lo + sh, n_valid))
+
+
 def all_reduce_buckets_(flat, slices, group=None):
     """Sum each [begin, end) slice of the flat buffer over the group, one collective per slice, in list order (every rank
-    must use the same list).  The engine issues exactly these collectives, each as soon as its bucket's event has fired."""
+    must use the same list).  parallel.AllReduceExchange issues the same collectives on a side stream, each behind its bucket's
+    event (the MLP slice first)."""
     if group is None:
         return
     for a, b in slices:
@@ -193,7 +211,7 @@ def all_reduce_sum_(tensors, group=None):
 
 
 def broadcast_parameters(tensors, group=None, src=0):
-    """Make every rank start from rank `src`'s parameters."""
+    """Make every rank start from rank `src`'s parameters (NAFEngine.broadcast_parameters)."""
     if group is None:
         return
     for t in tensors:

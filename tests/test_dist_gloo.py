@@ -67,7 +67,7 @@ def test_dp_gradients_equal_single_process():
             np.testing.assert_allclose(a, b.numpy(), rtol=1e-4, atol=1e-6)
 
 
-# ---- bucketed exchange: the collectives the engine issues per level bucket ------------------------------------------
+# ---- bucketed exchange: the collectives parallel.AllReduceExchange issues per level bucket ------------------------------
 def _bucket_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     _, _, _, group = dist.init_from_env(device_type="cpu")
@@ -112,7 +112,7 @@ def test_bucketed_exchange_equals_single_all_reduce():
     assert dist.grad_bucket_slices([0, 10, 20, 30], 2, [(2, 3), (0, 2)]) == [(40, 60), (0, 40)]
 
 
-# ---- sharded optimiser: reduce-scatter -> Adam on the rank's slice -> all-gather (engine._exchange_and_step_sharded) -----------
+# ---- sharded optimiser: reduce-scatter -> Adam on the rank's slice -> all-gather (parallel.ShardedExchange) --------------------
 def _adam_ref(p, m, v, g, step, lr=1e-2, b1=0.9, b2=0.999, eps=1e-8):
     m.mul_(b1).add_(g, alpha=1 - b1)
     v.mul_(b2).addcmul_(g, g, value=1 - b2)
@@ -126,9 +126,7 @@ def _sharded_worker(rank, world, port, q):
     offs = level_offsets(3, 16, 16, 12)
     C = 2
     n_emb = int(offs[-1]) * C
-    import math
-    pad_to = 64 * 4 * world // math.gcd(64, 4 * world)              # the engine's padding rule: lcm(64, 4 * world)
-    n_pad = (n_emb + pad_to - 1) // pad_to * pad_to
+    n_pad = dist.padded_length(n_emb, world)                        # the engine's padding rule: lcm(64, 4 * world)
     slices = dist.grad_bucket_slices(offs, C, [(11, 16), (3, 11), (0, 3)])
     ranges = dist.sharded_exchange_slices(slices, world, n_pad)
     g0 = torch.Generator().manual_seed(7)
@@ -144,18 +142,16 @@ def _sharded_worker(rank, world, port, q):
         td.all_reduce(whole, group=group)
         _adam_ref(p_ref, m_ref, v_ref, whole[:n_emb], step)        # the all-reduce form, every rank the whole table
         for a, b in ranges:                                        # the sharded form
-            sh = (b - a) // world
-            out = torch.zeros(sh)
+            lo, end, hi = dist.shard_bounds(a, b, world, rank, n_emb)
+            out = torch.zeros(end - lo)
             td.reduce_scatter_tensor(out, grad[a:b].contiguous(), group=group)
-            lo = a + rank * sh
-            hi = min(lo + sh, n_emb)
             if hi > lo:
                 _adam_ref(p[lo:hi], m[lo:hi], v[lo:hi], out[:hi - lo], step)
-            td.all_gather_into_tensor(p[a:b], p[lo:lo + sh].clone(), group=group)
+            td.all_gather_into_tensor(p[a:b], p[lo:end].clone(), group=group)
     owned = torch.zeros(n_emb, dtype=torch.bool)
     for a, b in ranges:
-        sh = (b - a) // world
-        owned[a + rank * sh:min(a + (rank + 1) * sh, n_emb)] = True
+        lo, _, hi = dist.shard_bounds(a, b, world, rank, n_emb)
+        owned[lo:hi] = True
     exact = world == 2                                             # a sum of three addends depends on the order the backend takes them in
     same_p = torch.equal(p[:n_emb], p_ref) if exact else torch.allclose(p[:n_emb], p_ref, rtol=0, atol=2e-4)   # Adam steps of lr = 1e-2
     same_m = torch.equal(m[owned], m_ref[owned]) if exact else torch.allclose(m[owned], m_ref[owned], rtol=1e-5, atol=1e-6)
@@ -189,7 +185,7 @@ def test_sharded_optimizer_exchange_equals_all_reduce_then_adam():
             assert all((b - a) % (4 * world) == 0 and a % 4 == 0 for a, b in ranges)
 
 
-# ---- level-parallel exchange (engine._train_step_levels): the two all-to-alls, on CPU --------------------------------------------
+# ---- level-parallel exchange (parallel.LevelParallelStep): the two all-to-alls, on CPU -------------------------------------------
 def _levels_worker(rank, world, port, q):
     """A per-level linear 'encoder' stands in for the hash grid: feature(l, point) = table[l] * x(point).  Rank k owns L / world
     levels; the features of its levels for every rank's points go out in one block per destination, the gradients come back the

@@ -74,12 +74,7 @@ def _levels_step(eng, N, rays, target, weight, pad=0, halves=1):
             eng.loss.add_(part)                                   # (the all-reduce of the real step)
             grads.append(dfeat)
     eng.step_count += 1
-    st = _abi.TableAdam()
-    st.param, st.exp_avg, st.exp_avg_sq = eng.emb.data_ptr(), eng.emb_m.data_ptr(), eng.emb_v.data_ptr()
-    st.param_lp = None if eng.emb_lp is None else eng.emb_lp.data_ptr()
-    st.lp_dtype = 0 if eng.emb_lp is None else _abi.dtype_code(eng.table_dtype)
-    b1, b2 = eng.betas
-    st.n, st.lr, st.beta1, st.beta2, st.eps, st.step, st.grad_scale = eng.emb.numel(), eng.lr, b1, b2, eng.eps, eng.step_count, 1.0
+    st = eng._table_adam()
     offs = eng.offsets.tolist()
     fused_tail = []
     V = halves * N                                                # blocks the owner receives

@@ -72,12 +72,7 @@ def levels_step(eng, N, rays, target, weight, timers=None, halves=1):
             eng.loss.add_(part)
             grads.append(dfeat)
     eng.step_count += 1
-    st = _abi.TableAdam()
-    st.param, st.exp_avg, st.exp_avg_sq = eng.emb.data_ptr(), eng.emb_m.data_ptr(), eng.emb_v.data_ptr()
-    st.param_lp = None if eng.emb_lp is None else eng.emb_lp.data_ptr()
-    st.lp_dtype = 0 if eng.emb_lp is None else _abi.dtype_code(eng.table_dtype)
-    b1, b2 = eng.betas
-    st.n, st.lr, st.beta1, st.beta2, st.eps, st.step, st.grad_scale = eng.emb.numel(), eng.lr, b1, b2, eng.eps, eng.step_count, 1.0
+    st = eng._table_adam()
     offs = eng.offsets.tolist()
     fused_tail = []
     V = halves * N
@@ -132,7 +127,7 @@ def main():
         ref, lev = engine(), engine()
         gen = torch.Generator(device=dev).manual_seed(7)
     if not args.default_buckets:
-        lev._levels_flags = {1: 2, 2: 2}.get(16 // N, 0) << _abi.CFG_MIN_BUCKETS_SHIFT      # what engine._init_level_parallel sets
+        lev._levels_flags = {1: 2, 2: 2}.get(16 // N, 0) << _abi.CFG_MIN_BUCKETS_SHIFT      # what parallel.LevelParallelStep sets
     if args.gather_pass:
         lev._levels_flags |= _abi.CFG_LEVELS_GATHER_PASS
     ref_step_ms = []
