@@ -453,6 +453,21 @@ int naf_project_scan(const float *volume, const uint32_t *dims, const float *dvo
                      uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
                      int parallel, float step, float *out, void *stream);
 
+/* M1  3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
+ * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
+ * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.
+ *   x, y  f32 [n1, n2, n3] C-contiguous, converted to fp64 on load; all arithmetic in fp64
+ *   7 x 7 x 7 uniform window, N_P = 343, cov_norm = 343 / 342, R = 2 (data_range of float input), C1 = (0.01 R)^2, C2 = (0.03 R)^2
+ *   box means ux, uy, uxx, uyy, uxy;  vx = cov_norm (uxx - ux^2), vy = cov_norm (uyy - uy^2), vxy = cov_norm (uxy - ux uy)
+ *   S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2))
+ *   out[0] (fp64, DEVICE) = mean of S over the interior [3, n - 4] of every axis, (n1 - 6)(n2 - 6)(n3 - 6) windows
+ * Every extent must be >= 7.  A NaN in any interior window gives NaN.  No full-size intermediate; the per-workgroup partial sums
+ * go to `workspace` (naf_ssim_3d_workspace_bytes(n1, n2, n3) bytes, 8-byte aligned; 0 for an extent < 7) and are added in a
+ * fixed order: two calls on the same inputs return the same bits.  No host synchronisation inside the call. */
+size_t naf_ssim_3d_workspace_bytes(uint32_t n1, uint32_t n2, uint32_t n3);
+int naf_ssim_3d(const float *x, const float *y, uint32_t n1, uint32_t n2, uint32_t n3, double *out, void *workspace,
+                size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

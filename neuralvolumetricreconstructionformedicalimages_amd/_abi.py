@@ -140,6 +140,8 @@ SIGNATURES = {
     "naf_project_rays": (_i32, [_vp, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _u64, _f32, _vp, _vp]),
     "naf_project_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
                                 _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),
+    "naf_ssim_3d_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32]),
+    "naf_ssim_3d": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 
@@ -192,6 +194,18 @@ def ptr(t):
     if not t.is_contiguous():
         raise RuntimeError("libnaf_hip: tensor must be contiguous")
     return ctypes.c_void_p(t.data_ptr())
+
+
+def check_volume(t, who, name="volume"):
+    """A volume argument of the library: a contiguous float32 [n1, n2, n3] CUDA/HIP tensor (no CPU path)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{who}: {name} must be a CUDA/HIP tensor (no CPU path)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: {name} must be float32, got {t.dtype}")
+    if t.dim() != 3:
+        raise ValueError(f"{who}: {name} must be [n1, n2, n3], got shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
 
 
 def stream_ptr():

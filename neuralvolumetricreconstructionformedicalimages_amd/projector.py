@@ -23,14 +23,7 @@ MAX_PIXELS_PER_CALL = 1 << 26
 
 
 def _check_volume(volume):
-    if not isinstance(volume, torch.Tensor) or not volume.is_cuda:
-        raise RuntimeError("projector: volume must be a CUDA/HIP tensor (no CPU path)")
-    if volume.dtype != torch.float32:
-        raise TypeError(f"projector: volume must be float32, got {volume.dtype}")
-    if volume.dim() != 3:
-        raise ValueError(f"projector: volume must be [n1, n2, n3], got shape {tuple(volume.shape)}")
-    if not volume.is_contiguous():
-        raise ValueError("projector: volume must be contiguous")
+    _abi.check_volume(volume, "projector")
 
 
 def sample_step(dvoxel, accuracy=0.5):

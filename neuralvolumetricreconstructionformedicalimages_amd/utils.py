@@ -46,7 +46,9 @@ def get_psnr_3d(arr1, arr2, size_average=True, PIXEL_MAX=1.0):
 
 
 def get_ssim_3d(arr1, arr2, size_average=True, PIXEL_MAX=1.0):
-    """Mean of the slice-wise SSIM along the three axes (util.py:87-139); needs scikit-image."""
+    """3-D SSIM averaged over three transposed views of the volume (util.py:87-139): each view is one 3-D
+    structural_similarity call on the whole volume, not a slice-wise SSIM; needs scikit-image.  metrics.ssim_3d computes the
+    same definition on the device."""
     try:
         from skimage.metrics import structural_similarity
     except ImportError as e:                                   # not installed in this image
