@@ -210,7 +210,7 @@ typedef struct naf_render_cfg {
                                          need no workspace (naf_forward_workspace_bytes).  Bit-identical to the two-kernel path. */
 #define NAF_CFG_ENCODE_TWO_GATHERS 32u /* diagnostics: the encoder fetches the two x-neighbour corners of a cell with two gathers
                                          at every batch size instead of one 16-byte window (same results; A/B timing only) */
-#define NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD 128u /* diagnostics: the MLP backward splits rays into tile ranges only up to one wave per SIMD (rounds 1-2) instead of three, and the bf16 MLP forward keeps one wave per ray at small batches (no mlp16_forward_split_kernel) */
+#define NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD 128u /* diagnostics: the MLP backward splits rays into tile ranges only up to one wave per SIMD (rounds 1-2) instead of three, and the bf16 MLP forward keeps one wave per ray at small batches (no mlp16_forward_split_kernel, no mlp16_train_kernel) */
 #define NAF_CFG_ENCODE_LEVEL_MAJOR 256u /* diagnostics: the encoder never splits the XCDs into groups (see NAF_CFG_ENCODE_GROUPS_*)       */
 #define NAF_CFG_ENCODE_WINDOWS 64u     /* diagnostics: the 16-byte window form at every batch size (default: below 600 000 points per
                                           call and for fp32 tables; two gathers with four points per lane in flight above)        */
@@ -229,6 +229,9 @@ typedef struct naf_render_cfg {
 #define NAF_CFG_LEVELS_GATHER_PASS 32768u /* diagnostics: naf_levels_scatter re-orders the gradient blocks into [level][point][C] with a pass of
                                             its own (rounds 3-4) even where pass 1 of the scatter can read them in place (two bf16
                                             channels) -- same results bit for bit; A/B timing and tests                              */
+#define NAF_CFG_MLP_TWO_KERNELS 65536u    /* diagnostics: small bf16 training steps keep the MLP forward / backward kernel pair instead of
+                                            the one launch that does both (mlp16_train_kernel) -- same results bit for bit; A/B timing
+                                            and tests.  NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD describes that pair and selects it as well  */
 #define NAF_CFG_TEST_TINY_BLOCKS 4096u   /* tests: the record blocks of pass 1 hold a quarter of a tile's records, so that most
                                             records take the overflow route (counted global atomics) and the reducer's Adam tail has
                                             spilled contributions to fold in                                                        */

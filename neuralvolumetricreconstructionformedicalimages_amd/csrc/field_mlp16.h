@@ -83,15 +83,17 @@ struct Mlp16Shared {
     // on the LDS.  Same values, same conversion: the fragments are bit-identical.  `stage`: kStageFloats floats of LDS that nothing
     // else uses until the barrier at the end (the kernels lend the depth buffers / transpose images, which they fill later).
     static constexpr uint32_t kStW0 = 0u, kStW1 = 32u * 33u, kStW2 = 2u * 32u * 33u, kStageFloats = 2u * 32u * 33u + 32u * 65u;
-    template <uint32_t kFrags>
+    // kWaves: waves of the workgroup (blockDim.x == 64 kWaves).  The first four stage the weights; all of them build fragments.
+    template <uint32_t kFrags, uint32_t kWaves = 4u>
     static __device__ __forceinline__ void build_staged(unsigned char *lds, const float *__restrict__ mlp, float *stage) {
-        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;          // blockDim.x == 256 (four waves)
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
         const uint32_t r = lane & 15u, g = lane >> 4;
+        const bool stager = kWaves == 4u || threadIdx.x < 256u;
         float w[16];
 #pragma unroll
         for (uint32_t u = 0; u < 16; ++u) {                                        // u < 4: W0, u < 8: W1, else W2 (256 threads x 4 = a matrix of 1 024)
             const uint32_t i = threadIdx.x + 256u * (u & 3u) + (u >= 8u ? 1024u * ((u - 8u) >> 2) : 0u);
-            w[u] = mlp[(u < 4u ? kW0 : u < 8u ? kW1 : kW2) + i];
+            w[u] = stager ? mlp[(u < 4u ? kW0 : u < 8u ? kW1 : kW2) + i] : 0.0f;
         }
         float *bias = reinterpret_cast<float *>(lds + kBiasOff);
         float bv = 0.0f;
@@ -102,15 +104,17 @@ struct Mlp16Shared {
 #pragma unroll
         for (uint32_t u = 0; u < 16; ++u) {
             const uint32_t i = threadIdx.x + 256u * (u & 3u) + (u >= 8u ? 1024u * ((u - 8u) >> 2) : 0u);
+            if (!stager) break;
             if (u < 8u) stage[(u < 4u ? kStW0 : kStW1) + (i >> 5) * 33u + (i & 31u)] = w[u];
             else stage[kStW2 + (i >> 6) * 65u + (i & 63u)] = w[u];
         }
         if (threadIdx.x < 129u) bias[threadIdx.x] = bv;
         __syncthreads();
-        constexpr uint32_t kIter = 2u * kFrags / 4u;
+        constexpr uint32_t kIter = (2u * kFrags + kWaves - 1u) / kWaves;
 #pragma unroll
         for (uint32_t it = 0; it < kIter; ++it) {
-            const uint32_t fo = wave + 4u * it, f = fo >> 1, o = fo & 1u;
+            const uint32_t fo = wave + kWaves * it, f = fo >> 1, o = fo & 1u;
+            if (kWaves != 4u && fo >= 2u * kFrags) break;
             const uint32_t layer = f & 3u;                                         // 0: W0, 1: W1, 2: W2[:, :32], 3: W2[:, 32:]
             const uint32_t base = layer == 0u ? kStW0 : layer == 1u ? kStW1 : layer == 2u ? kStW2 : kStW2 + 32u;
             const uint32_t pitch = layer >= 2u ? 65u : 33u;

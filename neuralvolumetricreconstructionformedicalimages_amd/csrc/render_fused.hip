@@ -645,8 +645,229 @@ mlp_backward_kernel(const typename P::feat_t::store_t *__restrict__ feat, const 
 }
 
 // ---- 3b: MLP backward on 16-point tiles (bf16 mode, C = 2; field_mlp16.h) ----------------------------------------
-// Same outputs as mlp_backward_kernel (dfeat, one dW slab per workgroup, max |dfeat|) at two or more waves per SIMD.
-__global__ void __launch_bounds__(256, 3)                     // 168 VGPRs (11 spilled dwords): three waves per SIMD
+// Same outputs as mlp_backward_kernel (dfeat, one dW slab per workgroup, max |dfeat|) at two or more waves per SIMD.  The sums of a
+// wave, the backward of one tile and the fold of four waves into a slab are shared with mlp16_train_kernel (3c).
+struct Mlp16Sums {
+    // weight-gradient accumulators: tile (o, q) covers outputs 16o.. and inputs 16q..; lane (col, grp), register i
+    // <-> dW[out = 16 o + 4 grp + i][in = 16 q + col]
+    f32x4v dW0[2][2], dW1[2][2], dW2[2][4];
+    float db[3][2];                                          // per lane: output 16o + (lane & 15), its 4 points
+    float db3, loss_part;
+    uint32_t dmax;                                           // see mlp_backward_kernel
+    f32x4v dw3lo, dw3hi;
+    __device__ __forceinline__ void clear() {
+        const f32x4v zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) { dW0[o][q] = zero4; dW1[o][q] = zero4; }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) dW2[o][q] = zero4;
+        }
+#pragma unroll
+        for (int l = 0; l < 3; ++l) db[l][0] = db[l][1] = 0.0f;
+        db3 = 0.0f; loss_part = 0.0f;
+        dmax = 0u;
+        dw3lo = zero4; dw3hi = zero4;
+    }
+};
+constexpr uint32_t kImg16 = 16u * 64u;                       // bytes per transpose image; a wave owns three (G, X0, H) in a row
+
+// Backward of one tile: forward recomputed from the features `now`, gsig = d loss / d sigma of the lane's point (0 past the ray's
+// end), feature gradients of point p stored when `valid`.  `imgs`: the wave's three transpose images.
+__device__ __forceinline__ void mlp16_backward_tile(Mlp16Sums &sm, const unsigned char *smem, unsigned char *imgs, uint32_t lane, const Feat16Raw &now,
+                                                    float gsig, int act, bool valid, uint16_t *__restrict__ dfeat, uint32_t B, uint32_t p) {
+    const uint32_t c = lane & 15u, g = lane >> 4;
+    const f32x4v zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    unsigned char *imgG = imgs, *imgX = imgs + kImg16, *imgH = imgs + 2u * kImg16;      // gradient tile G3 / G2 / G1, input tile X0, hidden tile H2 / H1
+    const bf16x8 x0f = feat16_operand(now);
+    // Weight fragments and biases are re-read from LDS for every tile: hoisted out of the loop (which the compiler
+    // does when it can prove the addresses loop-invariant) they would pin ~90 registers and halve the occupancy.
+    uint32_t tile_tag = 0;
+    asm volatile("" : "+v"(tile_tag));
+    const unsigned char *wsh = smem + tile_tag;
+    Act16 a;
+    const float z4 = mlp16_tile_forward(wsh, lane, x0f, a);
+    const float sigma = last_act16(act, z4);
+    const float g4 = gsig * last_act_grad(act, z4, sigma);
+
+    // output layer: dw3 += g4 * h3, db3 += g4 ; G3 = (w3 g4) * lrelu'(z3)
+    f32x4v glo, ghi;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        sm.dw3lo[j] = __fmaf_rn(g4, a.h3lo[j], sm.dw3lo[j]);
+        sm.dw3hi[j] = __fmaf_rn(g4, a.h3hi[j], sm.dw3hi[j]);
+        glo[j] = a.w3lo[j] * g4 * (a.h3lo[j] > 0.0f ? 1.0f : kLeaky);
+        ghi[j] = a.w3hi[j] * g4 * (a.h3hi[j] > 0.0f ? 1.0f : kLeaky);
+    }
+    if (g == 0u) sm.db3 += g4;
+
+    // layer 2: dW2 = G3 . [X0; H2]^T over the 16 points of the tile
+    bf16x8 gf = pack16(glo, ghi);
+    tr16_put(imgG, c, g, gf);
+    tr16_put(imgX, c, g, x0f);
+    tr16_put(imgH, c, g, a.h2f);
+    wave_lds_fence<PrecBF16>();
+    i16x4v gA[2], xB[2], hB[2];
+#pragma unroll
+    for (uint32_t o = 0; o < 2; ++o) { gA[o] = tr16_get(imgG, lane, o); xB[o] = tr16_get(imgX, lane, o); hB[o] = tr16_get(imgH, lane, o); }
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        sm.dW2[o][0] = mma16k16(gA[o], xB[0], sm.dW2[o][0]);
+        sm.dW2[o][1] = mma16k16(gA[o], xB[1], sm.dW2[o][1]);
+        sm.dW2[o][2] = mma16k16(gA[o], hB[0], sm.dW2[o][2]);
+        sm.dW2[o][3] = mma16k16(gA[o], hB[1], sm.dW2[o][3]);
+        sm.db[2][o] = add_bf16x4(sm.db[2][o], gA[o]);
+    }
+    wave_lds_fence<PrecBF16>();
+
+    // back through layer 2 (skip layer): d[input] and d[h2]
+    f32x4v dxlo = mma16(Mlp16Shared::frag(wsh, kFW2aT, 0, lane), gf, zero4);
+    f32x4v dxhi = mma16(Mlp16Shared::frag(wsh, kFW2aT, 1, lane), gf, zero4);
+    f32x4v dhlo = mma16(Mlp16Shared::frag(wsh, kFW2bT, 0, lane), gf, zero4);
+    f32x4v dhhi = mma16(Mlp16Shared::frag(wsh, kFW2bT, 1, lane), gf, zero4);
+    glo = leaky_grad4_packed(dhlo, a.h2f, 0);                              // G2
+    ghi = leaky_grad4_packed(dhhi, a.h2f, 1);
+    gf = pack16(glo, ghi);
+    tr16_put(imgG, c, g, gf);
+    tr16_put(imgH, c, g, a.h1f);
+    wave_lds_fence<PrecBF16>();
+#pragma unroll
+    for (uint32_t o = 0; o < 2; ++o) { gA[o] = tr16_get(imgG, lane, o); hB[o] = tr16_get(imgH, lane, o); }
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        sm.dW1[o][0] = mma16k16(gA[o], hB[0], sm.dW1[o][0]);
+        sm.dW1[o][1] = mma16k16(gA[o], hB[1], sm.dW1[o][1]);
+        sm.db[1][o] = add_bf16x4(sm.db[1][o], gA[o]);
+    }
+    wave_lds_fence<PrecBF16>();
+
+    dhlo = mma16(Mlp16Shared::frag(wsh, kFW1T, 0, lane), gf, zero4);
+    dhhi = mma16(Mlp16Shared::frag(wsh, kFW1T, 1, lane), gf, zero4);
+    glo = leaky_grad4_packed(dhlo, a.h1f, 0);                              // G1
+    ghi = leaky_grad4_packed(dhhi, a.h1f, 1);
+    gf = pack16(glo, ghi);
+    tr16_put(imgG, c, g, gf);
+    wave_lds_fence<PrecBF16>();
+#pragma unroll
+    for (uint32_t o = 0; o < 2; ++o) { gA[o] = tr16_get(imgG, lane, o); xB[o] = tr16_get(imgX, lane, o); }   // X0 again: cheaper than keeping it
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        sm.dW0[o][0] = mma16k16(gA[o], xB[0], sm.dW0[o][0]);
+        sm.dW0[o][1] = mma16k16(gA[o], xB[1], sm.dW0[o][1]);
+        sm.db[0][o] = add_bf16x4(sm.db[0][o], gA[o]);
+    }
+    wave_lds_fence<PrecBF16>();
+
+    dxlo = mma16(Mlp16Shared::frag(wsh, kFW0T, 0, lane), gf, dxlo);
+    dxhi = mma16(Mlp16Shared::frag(wsh, kFW0T, 1, lane), gf, dxhi);
+    if (valid) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sm.dmax = max(sm.dmax, max(__float_as_uint(dxlo[j]) & 0x7fffffffu, __float_as_uint(dxhi[j]) & 0x7fffffffu));
+        store_feat16(dfeat, B, p, g, __builtin_bit_cast(uint4, pack16(dxlo, dxhi)));
+    }
+}
+
+// ---- fold four waves into one slab (wave order -> deterministic), then one store ---------------------------------------------
+// Called by every wave of the workgroup (it holds workgroup barriers): wave `wig` of a group of four, `tid` = thread of the group,
+// imgA / imgB = the group's two slab images, `slab` = where the group's sums go (nullptr: nowhere).  The first barrier ends every
+// other use of the LDS.
+__device__ __forceinline__ void mlp16_fold_slab(Mlp16Sums &sm, float *imgA, float *imgB, uint32_t tid, uint32_t wig, float *__restrict__ slab) {
+    const uint32_t lane = tid & 63u, c = lane & 15u, g = lane >> 4;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sm.dmax = max(sm.dmax, (uint32_t)__shfl_xor((int)sm.dmax, off, 64));     // non-negative floats order like uints
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {                                               // over the four point groups of an output
+            sm.db[l][o] += __shfl_xor(sm.db[l][o], 16, 64);
+            sm.db[l][o] += __shfl_xor(sm.db[l][o], 32, 64);
+        }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) {                                         // over the 16 points of a lane group
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { sm.dw3lo[j] += __shfl_xor(sm.dw3lo[j], off, 64); sm.dw3hi[j] += __shfl_xor(sm.dw3hi[j], off, 64); }
+        sm.db3 += __shfl_xor(sm.db3, off, 64);
+    }
+    __syncthreads();                                                                // images / depth buffers are dead
+    // ---- in wave order: ((0 + a0) + a1) + a2) + a3 per entry, as ever --------------
+    // tools/mlp_stamps.py put the fold of rounds 2-4 -- the waves took turns adding their 64 + 17 values to one LDS image, `red[i] += x`,
+    // a dependent read-add-write round trip each -- at 14 000 of the kernel's 52 900 cycles at the reference's batch (with the pass
+    // that cleared the image); batching a turn's reads did not help (the turns stay dependent and three workgroups per CU take them at
+    // once), an XOR swizzle against the 4-way bank conflict of the lane groups neither.  Now nobody reads what it has just written: a wave
+    // STORES its values into an image of its own (no waits), and all 256 threads add two images entry by entry, coalesced.  There is
+    // room for two images -- A over the weight fragments, which are dead too, B over the transpose images -- so waves 0 and 1 write
+    // together and waves 2 and 3 follow one by one.  Same operands in the same order: the slab has the same bits.
+    auto put = [&](float *img) {
+#pragma unroll
+        for (uint32_t o = 0; o < 2; ++o)
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i) {
+                const uint32_t out = 16u * o + 4u * g + i;
+#pragma unroll
+                for (uint32_t q = 0; q < 2; ++q) {
+                    img[kW0 + out * 32u + 16u * q + c] = sm.dW0[o][q][i];
+                    img[kW1 + out * 32u + 16u * q + c] = sm.dW1[o][q][i];
+                }
+#pragma unroll
+                for (uint32_t q = 0; q < 4; ++q) img[kW2 + out * 64u + 16u * q + c] = sm.dW2[o][q][i];
+            }
+        if (g == 0u) {
+#pragma unroll
+            for (uint32_t o = 0; o < 2; ++o) {
+                img[kB0 + 16u * o + c] = sm.db[0][o];
+                img[kB1 + 16u * o + c] = sm.db[1][o];
+                img[kB2 + 16u * o + c] = sm.db[2][o];
+            }
+        }
+        if (c == 0u) {
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                img[kW3 + 4u * g + j] = sm.dw3lo[j];
+                img[kW3 + 16u + 4u * g + j] = sm.dw3hi[j];
+            }
+        }
+        if (lane == 0u) {
+            img[kB3] = sm.db3;
+            img[kSlabLoss] = sm.loss_part;
+            img[kSlabGmax] = __uint_as_float(sm.dmax);
+        }
+    };
+    // A (+)= B, entry by entry; the first time A's entries are a wave's raw values and stand for 0 + a0 (the cleared image of old: -0.0
+    // becomes +0.0), the last time the sums go to the slab instead.  The maximum of the gradient bit patterns rides along.
+    auto combine = [&](bool first_pair, bool last_pair) {
+        constexpr uint32_t kPer = (kSlabGmax + 1u + 255u) / 256u;
+        float x[kPer], y[kPer];
+#pragma unroll
+        for (uint32_t u = 0; u < kPer; ++u) {
+            const uint32_t i = min(tid + 256u * u, kSlabGmax);
+            x[u] = imgA[i];
+            y[u] = imgB[i];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kPer; ++u) {
+            const uint32_t i = tid + 256u * u;
+            if (i > kSlabGmax) break;
+            const float lhs = first_pair ? 0.0f + x[u] : x[u];
+            const float v = i == kSlabGmax ? __uint_as_float(max(__float_as_uint(x[u]), __float_as_uint(y[u]))) : lhs + y[u];
+            if (!last_pair) imgA[i] = v; else if (slab != nullptr) slab[i] = v;
+        }
+    };
+    if (wig == 0u) put(imgA);
+    if (wig == 1u) put(imgB);
+    __syncthreads();
+    combine(true, false);
+    __syncthreads();
+    if (wig == 2u) put(imgB);
+    __syncthreads();
+    combine(false, false);
+    __syncthreads();
+    if (wig == 3u) put(imgB);
+    __syncthreads();
+    combine(false, true);
+}
+
+__global__ void __launch_bounds__(256, 3)                     // three waves per SIMD
 mlp16_backward_kernel(const uint16_t *__restrict__ feat, const float *__restrict__ mlp, SrcRays src,
                       const float *__restrict__ grad_acc, LossInputs loss, uint16_t *__restrict__ dfeat, float *__restrict__ slabs,
                       uint32_t n_rays, uint32_t B, int act, uint32_t parts, uint32_t *__restrict__ clear_words) {
@@ -664,28 +885,11 @@ mlp16_backward_kernel(const uint16_t *__restrict__ feat, const float *__restrict
     // wave-uniform values are made scalar explicitly: the ray record, its depths range and d acc then live in SGPRs
     const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6), n_waves = (gridDim.x * blockDim.x) >> 6;
     constexpr uint32_t kShAligned = (Mlp16Shared::kBytes + 15u) & ~15u;
-    constexpr uint32_t kImg = 16u * 64u;                                           // bytes per transpose image
-    unsigned char *imgG = smem + kShAligned + wib * 3u * kImg;                     // gradient tile G3 / G2 / G1
-    unsigned char *imgX = imgG + kImg;                                             // input tile X0
-    unsigned char *imgH = imgX + kImg;                                             // hidden tile H2 / H1
-    float *zbuf = reinterpret_cast<float *>(smem + kShAligned + 4u * 3u * kImg) + wib * kMaxSamplesLds;
+    unsigned char *imgs = smem + kShAligned + wib * 3u * kImg16;
+    float *zbuf = reinterpret_cast<float *>(smem + kShAligned + 4u * 3u * kImg16) + wib * kMaxSamplesLds;
     const bool use_zbuf = src.S <= kMaxSamplesLds;
-
-    // weight-gradient accumulators: tile (o, q) covers outputs 16o.. and inputs 16q..; lane (col, grp), register i
-    // <-> dW[out = 16 o + 4 grp + i][in = 16 q + col]
-    const f32x4v zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-    f32x4v dW0[2][2], dW1[2][2], dW2[2][4];
-#pragma unroll
-    for (int o = 0; o < 2; ++o) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) { dW0[o][q] = zero4; dW1[o][q] = zero4; }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dW2[o][q] = zero4;
-    }
-    float db[3][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};                 // per lane: output 16o + (lane & 15), its 4 points
-    float db3 = 0.0f, loss_part = 0.0f;
-    uint32_t dmax = 0u;                                      // see mlp_backward_kernel
-    f32x4v dw3lo = zero4, dw3hi = zero4;
+    Mlp16Sums sums;
+    sums.clear();
 
     // A work item is one ray, or one of `parts` consecutive tile ranges of a ray when there are fewer rays than resident waves
     // (1 024-ray steps: three waves per ray, four tiles each; the backward of a sample needs nothing of its ray but d acc, so
@@ -709,7 +913,7 @@ mlp16_backward_kernel(const uint16_t *__restrict__ feat, const float *__restrict
         if (loss.target != nullptr) {                        // training step: the loss lives here (wave-uniform arithmetic)
             const float err = loss.acc[r] - loss.target[r], w = loss.weight[r];
             dacc = 2.0f * w * err;
-            if (part == 0u) loss_part += w * err * err;                    // once per ray, not once per tile range
+            if (part == 0u) sums.loss_part += w * err * err;               // once per ray, not once per tile range
         } else dacc = grad_acc[r];
         if (use_zbuf) fill_depths(src, r, near, far, zbuf, lane);
 
@@ -725,205 +929,131 @@ mlp16_backward_kernel(const uint16_t *__restrict__ feat, const float *__restrict
                 const uint32_t sn = more ? s + 16u : 16u * first_tile(next - ray_of(next) * parts) + c;
                 load_feat16(feat, B, rn * S + min(sn, S - 1u), g, ahead);
             }
-            const bf16x8 x0f = feat16_operand(now);
-            // Weight fragments and biases are re-read from LDS for every tile: hoisted out of the loop (which the compiler
-            // does when it can prove the addresses loop-invariant) they would pin ~90 registers and halve the occupancy.
-            uint32_t tile_tag = 0;
-            asm volatile("" : "+v"(tile_tag));
-            const unsigned char *wsh = smem + tile_tag;
-            Act16 a;
-            const float z4 = mlp16_tile_forward(wsh, lane, x0f, a);
-            const float sigma = last_act16(act, z4);
             const float gsig = !valid ? 0.0f
                              : dacc * (use_zbuf ? buffered_dist(zbuf, s, S, dnorm) : sample_dist(src, r, s, near, far, dnorm));
-            const float g4 = gsig * last_act_grad(act, z4, sigma);
-
-            // output layer: dw3 += g4 * h3, db3 += g4 ; G3 = (w3 g4) * lrelu'(z3)
-            f32x4v glo, ghi;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                dw3lo[j] = __fmaf_rn(g4, a.h3lo[j], dw3lo[j]);
-                dw3hi[j] = __fmaf_rn(g4, a.h3hi[j], dw3hi[j]);
-                glo[j] = a.w3lo[j] * g4 * (a.h3lo[j] > 0.0f ? 1.0f : kLeaky);
-                ghi[j] = a.w3hi[j] * g4 * (a.h3hi[j] > 0.0f ? 1.0f : kLeaky);
-            }
-            if (g == 0u) db3 += g4;
-
-            // layer 2: dW2 = G3 . [X0; H2]^T over the 16 points of the tile
-            bf16x8 gf = pack16(glo, ghi);
-            tr16_put(imgG, c, g, gf);
-            tr16_put(imgX, c, g, x0f);
-            tr16_put(imgH, c, g, a.h2f);
-            wave_lds_fence<PrecBF16>();
-            i16x4v gA[2], xB[2], hB[2];
-#pragma unroll
-            for (uint32_t o = 0; o < 2; ++o) { gA[o] = tr16_get(imgG, lane, o); xB[o] = tr16_get(imgX, lane, o); hB[o] = tr16_get(imgH, lane, o); }
-#pragma unroll
-            for (int o = 0; o < 2; ++o) {
-                dW2[o][0] = mma16k16(gA[o], xB[0], dW2[o][0]);
-                dW2[o][1] = mma16k16(gA[o], xB[1], dW2[o][1]);
-                dW2[o][2] = mma16k16(gA[o], hB[0], dW2[o][2]);
-                dW2[o][3] = mma16k16(gA[o], hB[1], dW2[o][3]);
-                db[2][o] = add_bf16x4(db[2][o], gA[o]);
-            }
-            wave_lds_fence<PrecBF16>();
-
-            // back through layer 2 (skip layer): d[input] and d[h2]
-            f32x4v dxlo = mma16(Mlp16Shared::frag(wsh, kFW2aT, 0, lane), gf, zero4);
-            f32x4v dxhi = mma16(Mlp16Shared::frag(wsh, kFW2aT, 1, lane), gf, zero4);
-            f32x4v dhlo = mma16(Mlp16Shared::frag(wsh, kFW2bT, 0, lane), gf, zero4);
-            f32x4v dhhi = mma16(Mlp16Shared::frag(wsh, kFW2bT, 1, lane), gf, zero4);
-            glo = leaky_grad4_packed(dhlo, a.h2f, 0);                              // G2
-            ghi = leaky_grad4_packed(dhhi, a.h2f, 1);
-            gf = pack16(glo, ghi);
-            tr16_put(imgG, c, g, gf);
-            tr16_put(imgH, c, g, a.h1f);
-            wave_lds_fence<PrecBF16>();
-#pragma unroll
-            for (uint32_t o = 0; o < 2; ++o) { gA[o] = tr16_get(imgG, lane, o); hB[o] = tr16_get(imgH, lane, o); }
-#pragma unroll
-            for (int o = 0; o < 2; ++o) {
-                dW1[o][0] = mma16k16(gA[o], hB[0], dW1[o][0]);
-                dW1[o][1] = mma16k16(gA[o], hB[1], dW1[o][1]);
-                db[1][o] = add_bf16x4(db[1][o], gA[o]);
-            }
-            wave_lds_fence<PrecBF16>();
-
-            dhlo = mma16(Mlp16Shared::frag(wsh, kFW1T, 0, lane), gf, zero4);
-            dhhi = mma16(Mlp16Shared::frag(wsh, kFW1T, 1, lane), gf, zero4);
-            glo = leaky_grad4_packed(dhlo, a.h1f, 0);                              // G1
-            ghi = leaky_grad4_packed(dhhi, a.h1f, 1);
-            gf = pack16(glo, ghi);
-            tr16_put(imgG, c, g, gf);
-            wave_lds_fence<PrecBF16>();
-#pragma unroll
-            for (uint32_t o = 0; o < 2; ++o) { gA[o] = tr16_get(imgG, lane, o); xB[o] = tr16_get(imgX, lane, o); }   // X0 again: cheaper than keeping it
-#pragma unroll
-            for (int o = 0; o < 2; ++o) {
-                dW0[o][0] = mma16k16(gA[o], xB[0], dW0[o][0]);
-                dW0[o][1] = mma16k16(gA[o], xB[1], dW0[o][1]);
-                db[0][o] = add_bf16x4(db[0][o], gA[o]);
-            }
-            wave_lds_fence<PrecBF16>();
-
-            dxlo = mma16(Mlp16Shared::frag(wsh, kFW0T, 0, lane), gf, dxlo);
-            dxhi = mma16(Mlp16Shared::frag(wsh, kFW0T, 1, lane), gf, dxhi);
-            if (valid) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dmax = max(dmax, max(__float_as_uint(dxlo[j]) & 0x7fffffffu, __float_as_uint(dxhi[j]) & 0x7fffffffu));
-                store_feat16(dfeat, B, p, g, __builtin_bit_cast(uint4, pack16(dxlo, dxhi)));
-            }
+            mlp16_backward_tile(sums, smem, imgs, lane, now, gsig, act, valid, dfeat, B, p);
         }
     }
 
     NAF_STAMP(2);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) dmax = max(dmax, (uint32_t)__shfl_xor((int)dmax, off, 64));     // non-negative floats order like uints
-
-    // ---- fold the 4 waves of the workgroup into one slab (wave order -> deterministic), then one store ---------------
-#pragma unroll
-    for (int l = 0; l < 3; ++l)
-#pragma unroll
-        for (int o = 0; o < 2; ++o) {                                               // over the four point groups of an output
-            db[l][o] += __shfl_xor(db[l][o], 16, 64);
-            db[l][o] += __shfl_xor(db[l][o], 32, 64);
-        }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {                                         // over the 16 points of a lane group
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { dw3lo[j] += __shfl_xor(dw3lo[j], off, 64); dw3hi[j] += __shfl_xor(dw3hi[j], off, 64); }
-        db3 += __shfl_xor(db3, off, 64);
-    }
-    __syncthreads();                                                                // images / depth buffers are dead
-    NAF_STAMP(3);
-    // ---- fold the 4 waves of the workgroup into one slab, in wave order: ((0 + a0) + a1) + a2) + a3 per entry, as ever --------------
-    // tools/mlp_stamps.py put the fold of rounds 2-4 -- the waves took turns adding their 64 + 17 values to one LDS image, `red[i] += x`,
-    // a dependent read-add-write round trip each -- at 14 000 of the kernel's 52 900 cycles at the reference's batch (with the pass
-    // that cleared the image); batching a turn's reads did not help (the turns stay dependent and three workgroups per CU take them at
-    // once), an XOR swizzle against the 4-way bank conflict of the lane groups neither.  Now nobody reads what it has just written: a wave
-    // STORES its values into an image of its own (no waits), and all 256 threads add two images entry by entry, coalesced.  There is
-    // room for two images -- A over the weight fragments, which are dead too, B over the transpose images -- so waves 0 and 1 write
-    // together and waves 2 and 3 follow one by one.  Same operands in the same order: the slab has the same bits.
-    float *imgA = reinterpret_cast<float *>(smem), *imgB = reinterpret_cast<float *>(smem + kShAligned);
-    static_assert(kShAligned >= (kSlabGmax + 1u) * 4u, "the fragment area holds one slab image");
-    auto put = [&](float *img) {
-#pragma unroll
-        for (uint32_t o = 0; o < 2; ++o)
-#pragma unroll
-            for (uint32_t i = 0; i < 4; ++i) {
-                const uint32_t out = 16u * o + 4u * g + i;
-#pragma unroll
-                for (uint32_t q = 0; q < 2; ++q) {
-                    img[kW0 + out * 32u + 16u * q + c] = dW0[o][q][i];
-                    img[kW1 + out * 32u + 16u * q + c] = dW1[o][q][i];
-                }
-#pragma unroll
-                for (uint32_t q = 0; q < 4; ++q) img[kW2 + out * 64u + 16u * q + c] = dW2[o][q][i];
-            }
-        if (g == 0u) {
-#pragma unroll
-            for (uint32_t o = 0; o < 2; ++o) {
-                img[kB0 + 16u * o + c] = db[0][o];
-                img[kB1 + 16u * o + c] = db[1][o];
-                img[kB2 + 16u * o + c] = db[2][o];
-            }
-        }
-        if (c == 0u) {
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                img[kW3 + 4u * g + j] = dw3lo[j];
-                img[kW3 + 16u + 4u * g + j] = dw3hi[j];
-            }
-        }
-        if (lane == 0u) {
-            img[kB3] = db3;
-            img[kSlabLoss] = loss_part;
-            img[kSlabGmax] = __uint_as_float(dmax);
-        }
-    };
-    // A (+)= B, entry by entry; the first time A's entries are a wave's raw values and stand for 0 + a0 (the cleared image of old: -0.0
-    // becomes +0.0), the last time the sums go to the slab instead.  The maximum of the gradient bit patterns rides along.
-    auto combine = [&](bool first_pair, float *to_slab) {
-        constexpr uint32_t kPer = (kSlabGmax + 1u + 255u) / 256u;
-        float x[kPer], y[kPer];
-#pragma unroll
-        for (uint32_t u = 0; u < kPer; ++u) {
-            const uint32_t i = min(threadIdx.x + 256u * u, kSlabGmax);
-            x[u] = imgA[i];
-            y[u] = imgB[i];
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < kPer; ++u) {
-            const uint32_t i = threadIdx.x + 256u * u;
-            if (i > kSlabGmax) break;
-            const float lhs = first_pair ? 0.0f + x[u] : x[u];
-            const float v = i == kSlabGmax ? __uint_as_float(max(__float_as_uint(x[u]), __float_as_uint(y[u]))) : lhs + y[u];
-            if (to_slab != nullptr) to_slab[i] = v; else imgA[i] = v;
-        }
-    };
     float *slab = slabs + (size_t)blockIdx.x * kSlabStride;
-    if (wib == 0u) put(imgA);
-    if (wib == 1u) put(imgB);
-    __syncthreads();
-    combine(true, nullptr);
-    __syncthreads();
-    if (wib == 2u) put(imgB);
-    __syncthreads();
-    combine(false, nullptr);
-    __syncthreads();
-    if (wib == 3u) put(imgB);
-    __syncthreads();
-    NAF_STAMP(4);
-    combine(false, slab);
+    static_assert(kShAligned >= (kSlabGmax + 1u) * 4u, "the fragment area holds one slab image");
+    mlp16_fold_slab(sums, reinterpret_cast<float *>(smem), reinterpret_cast<float *>(smem + kShAligned), threadIdx.x, wib, slab);
 #ifdef NAF_MLP_STAMPS
     NAF_STAMP(5);
     if (threadIdx.x == 0u) {
         uint32_t *dbg = reinterpret_cast<uint32_t *>(slab) + 4300u;
+        stamp_[3] = stamp_[4] = stamp_[5];                   // (the fold's inner phases are no longer stamped apart)
         for (int i = 0; i < 6; ++i) dbg[i] = (uint32_t)(stamp_[i] - stamp_[0]);
         dbg[6] = (uint32_t)wall0_; dbg[7] = (uint32_t)wall_clock64();
     }
 #endif
 #undef NAF_STAMP
+}
+
+// ---- 3c: MLP forward, loss and backward of a small training step in ONE launch (bf16 mode, C = 2, loss formed in the kernel) -----
+// Below ~3 000 rays the pair mlp16_forward_split_kernel / mlp16_backward_kernel is bound by latency, not throughput: each stages
+// the weights, each waits for its first features, the line integrals travel to HBM and back, and a launch boundary sits between.
+// Here a workgroup of kWaves waves (4 or 12) owns kWaves / parts whole rays and writes kWaves / 4 slabs.  Wave `w` of workgroup
+// `b` takes work item kWaves b + w of mlp16_backward_kernel's item list.  At these ray counts that kernel gives every wave one item
+// and folds items 4 i .. 4 i + 3 into slab i; so does this one (group of four waves by group), hence every slab is the fold of the
+// same four tile ranges in the same order and has the same bits as the pair's -- and so has everything downstream.
+//   phase A  forward of the wave's tiles (weights in registers, as in the split kernel); the terms sigma * dist meet in LDS;
+//            one workgroup barrier
+//   loss     EVERY wave of a ray adds the ray's terms in tile order, then across the 16 lanes -- the order of both forward
+//            kernels: same bits, and no second barrier; the wave of the ray's first range stores acc[r] and owns the loss share
+//   phase B  mlp16_backward_tile on the same tiles (features re-read: they are L2 hits), then the slab fold per group of four waves
+// The depths of the wave's tile range are evaluated once for both phases.  S <= kMaxSamplesLds / 2: the upper half of a wave's
+// depth buffer holds its terms.
+template <uint32_t kWaves>
+__global__ void __launch_bounds__(kWaves * 64u, 3)
+mlp16_train_kernel(const uint16_t *__restrict__ feat, const float *__restrict__ mlp, SrcRays src, LossInputs loss, float *__restrict__ acc_out,
+                   uint16_t *__restrict__ dfeat, float *__restrict__ slabs, uint32_t n_rays, uint32_t B, int act, uint32_t parts, uint32_t n_slabs,
+                   uint32_t *__restrict__ clear_words) {
+    static_assert(kWaves % 4u == 0u, "whole slabs per workgroup");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (clear_words != nullptr && blockIdx.x == 0u && threadIdx.x < kClearWords) clear_words[threadIdx.x] = 0u;      // see StepExtras
+    const uint32_t lane = threadIdx.x & 63u, c = lane & 15u, g = lane >> 4, wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr uint32_t kShAligned = (Mlp16Shared::kBytes + 15u) & ~15u;
+    constexpr uint32_t kTermOff = kMaxSamplesLds / 2u;
+    unsigned char *imgs = smem + kShAligned + wib * 3u * kImg16;
+    float *zall = reinterpret_cast<float *>(smem + kShAligned + kWaves * 3u * kImg16);
+    float *zbuf = zall + wib * kMaxSamplesLds;
+    static_assert(kWaves * 3u * kImg16 + kWaves * kMaxSamplesLds * 4u >= Mlp16Shared::kStageFloats * 4u, "images and depth buffers stage the weights");
+    static_assert(kShAligned + kWaves * (3u * kImg16 + kMaxSamplesLds * 4u) >= (kWaves / 2u) * kShAligned, "two slab images per group of four waves");
+
+    // (kWaves is a multiple of parts: the waves of a ray share a workgroup, and the ray's first range sits `part` waves below)
+    const uint32_t S = src.S, tiles = (S + 15u) / 16u;
+    auto first_tile = [&](uint32_t part) { return part * tiles / parts; };
+    const uint32_t item = blockIdx.x * kWaves + wib;
+    const bool has = item < n_rays * parts;                  // (a wave without an item still folds: zeros, like the pair's idle waves)
+    const uint32_t r = has ? item / parts : 0u, part = has ? item - r * parts : 0u;
+    const uint32_t k_begin = has ? first_tile(part) : 0u, k_end = has ? first_tile(part + 1u) : 0u;
+    Mlp16Sums sums;
+    sums.clear();
+
+    Feat16Raw ahead;
+    if (has) load_feat16(feat, B, r * S + min(16u * k_begin + c, S - 1u), g, ahead);
+    Mlp16Shared::build_staged<8, kWaves>(smem, mlp, reinterpret_cast<float *>(smem + kShAligned));
+    const float *ray = src.rays + (size_t)r * 8;
+    const float dnorm = sqrtf(ray[3] * ray[3] + ray[4] * ray[4] + ray[5] * ray[5]);
+    if (has) {
+        const float near = ray[6], far = ray[7];
+        for (uint32_t s = 16u * k_begin + lane; s < min(S, 16u * k_end + 1u); s += 64u) zbuf[s] = src.depth(r, s, near, far);
+    }
+    wave_lds_fence<PrecBF16>();
+    {   // ---- phase A (the tile loop of mlp16_forward_split_kernel) ----
+        Mlp16InRegs wt;
+        wt.load(smem, lane);
+        Act16 a;
+        float *T = zbuf + kTermOff;
+        for (uint32_t k0 = k_begin; k0 < k_end; k0 += 4u) {
+            float zsel = 0.0f;
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) {
+                const uint32_t k = k0 + j;
+                if (k >= k_end) break;                                   // uniform
+                const Feat16Raw now = ahead;
+                // next tile of this wave's range, else its first one again: phase B starts there
+                load_feat16(feat, B, r * S + min(16u * (k + 1u < k_end ? k + 1u : k_begin) + c, S - 1u), g, ahead);
+                const float z4 = mlp16_tile_forward(wt, feat16_operand(now), a);
+                zsel = g == j ? z4 : zsel;
+            }
+            const uint32_t s = 16u * (k0 + g) + c;
+            const float sigma = last_act16(act, zsel);
+            const float term = s >= S ? 0.0f : sigma * buffered_dist(zbuf, s, S, dnorm);
+            if (k0 + g < k_end) T[s] = term;
+        }
+    }
+    __syncthreads();
+    float dacc = 0.0f;
+    if (has) {
+        const float *T0 = zall + (wib - part) * kMaxSamplesLds + kTermOff;      // terms of the ray's first range; range q: + q depth buffers
+        float line = 0.0f;
+        if (g == 0u)
+            for (uint32_t q = 0; q < parts; ++q)
+                for (uint32_t k = first_tile(q); k < first_tile(q + 1u); ++k) line += T0[q * kMaxSamplesLds + 16u * k + c];
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) line += __shfl_xor(line, off, 64);     // the 16 points of lane group 0
+        if (part == 0u && lane == 0u) acc_out[r] = line;
+        const float acc = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, line)));
+        const float err = acc - loss.target[r], w = loss.weight[r];
+        dacc = 2.0f * w * err;
+        if (part == 0u) sums.loss_part += w * err * err;                   // once per ray, not once per tile range
+    }
+    // ---- phase B ----
+    for (uint32_t k = k_begin; k < k_end; ++k) {
+        const uint32_t s = 16u * k + c;
+        const bool valid = s < S;
+        const uint32_t p = r * S + (valid ? s : S - 1u);
+        const Feat16Raw now = ahead;
+        load_feat16(feat, B, r * S + min(k + 1u < k_end ? s + 16u : s, S - 1u), g, ahead);      // (a harmless reload at the very end)
+        const float gsig = !valid ? 0.0f : dacc * buffered_dist(zbuf, s, S, dnorm);
+        mlp16_backward_tile(sums, smem, imgs, lane, now, gsig, act, valid, dfeat, B, p);
+    }
+    const uint32_t grp = wib >> 2, slab_i = blockIdx.x * (kWaves / 4u) + grp;
+    mlp16_fold_slab(sums, reinterpret_cast<float *>(smem + 2u * grp * kShAligned), reinterpret_cast<float *>(smem + (2u * grp + 1u) * kShAligned),
+                    threadIdx.x & 255u, wib & 3u, slab_i < n_slabs ? slabs + (size_t)slab_i * kSlabStride : nullptr);
 }
 
 // ---- 5: slabs -> grad_mlp (+=), loss, gradient maximum: slab_reduce_block (mlp_slabs.h), as a launch of its own ----------------
@@ -986,7 +1116,7 @@ static int check_cfg(const naf_render_cfg *cfg, const char *who) {
     if (cfg->table_dtype < NAF_F32 || cfg->table_dtype > NAF_BF16) return fail(NAF_ERR_UNSUPPORTED, "fused field: bad table_dtype");
     if (cfg->last_activation < 0 || cfg->last_activation > 3) return fail(NAF_ERR_UNSUPPORTED, "fused field: bad last_activation");
     if (!(cfg->bound > 0.0f)) return fail(NAF_ERR_INVALID_ARGUMENT, "fused field: bound must be > 0");
-    if (cfg->flags & ~(NAF_CFG_PER_LEVEL_LAUNCHES | NAF_CFG_EXPLICIT_DEPTHS | NAF_CFG_LEVELS_INTERLEAVED | NAF_CFG_FORWARD_FUSED | NAF_CFG_FUSED_STORE_FEATURES | NAF_CFG_ENCODE_TWO_GATHERS | NAF_CFG_ENCODE_WINDOWS | NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD | NAF_CFG_ENCODE_LEVEL_MAJOR | NAF_CFG_TEST_TINY_BLOCKS | NAF_CFG_ENCODE_GROUPS_2 | NAF_CFG_ENCODE_GROUPS_4 | NAF_CFG_MIN_BUCKETS_MASK | NAF_CFG_SCATTER_PAIR12 | NAF_CFG_LEVELS_GATHER_PASS)) return fail(NAF_ERR_INVALID_ARGUMENT, "fused field: unknown cfg flag");
+    if (cfg->flags & ~(NAF_CFG_PER_LEVEL_LAUNCHES | NAF_CFG_EXPLICIT_DEPTHS | NAF_CFG_LEVELS_INTERLEAVED | NAF_CFG_FORWARD_FUSED | NAF_CFG_FUSED_STORE_FEATURES | NAF_CFG_ENCODE_TWO_GATHERS | NAF_CFG_ENCODE_WINDOWS | NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD | NAF_CFG_ENCODE_LEVEL_MAJOR | NAF_CFG_TEST_TINY_BLOCKS | NAF_CFG_ENCODE_GROUPS_2 | NAF_CFG_ENCODE_GROUPS_4 | NAF_CFG_MIN_BUCKETS_MASK | NAF_CFG_SCATTER_PAIR12 | NAF_CFG_LEVELS_GATHER_PASS | NAF_CFG_MLP_TWO_KERNELS)) return fail(NAF_ERR_INVALID_ARGUMENT, "fused field: unknown cfg flag");
     if (cfg->scatter_mode < NAF_SCATTER_AUTO || cfg->scatter_mode > NAF_SCATTER_BINNED)
         return fail(NAF_ERR_INVALID_ARGUMENT, "fused field: scatter_mode must be NAF_SCATTER_AUTO, _ATOMIC or _BINNED");
     (void)who;
@@ -1053,8 +1183,9 @@ static int run_mlp_forward(const void *feat, const float *mlp, const SrcRays &sr
 // launches of ~5 us each were 4 % of the reference-size step); `loss_assign` -- loss_out[0] = loss instead of +=; `deferred` --
 // where to leave the description of the slab reduction instead of launching it (the first scatter_bin launch then runs it in spare
 // workgroups, beside its own: one dependent launch of ~11 us less per step).
-struct StepExtras { uint32_t *clear_words; bool loss_assign; SlabReduce *deferred; hipEvent_t after_backward = nullptr; };      // after_backward: recorded once
-                                                                                      // the feature gradients are final, before the slab reduction
+struct StepExtras { uint32_t *clear_words; bool loss_assign; SlabReduce *deferred; hipEvent_t after_backward = nullptr;      // after_backward: recorded once
+                    float *acc_out = nullptr; };                                      // the feature gradients are final, before the slab reduction
+// acc_out: the forward has NOT run; mlp16_train_kernel does both passes and leaves the line integrals there (mlp_train_waves() != 0)
 
 static int run_mlp_grad_reduce(const float *slabs, uint32_t n_slabs, float *grad_mlp, float *loss_out, bool with_loss, const MlpAdam *madam,
                                uint32_t *gmax_bits, const StepExtras &ex, hipStream_t s) {
@@ -1065,6 +1196,34 @@ static int run_mlp_grad_reduce(const float *slabs, uint32_t n_slabs, float *grad
     ProfScope prof_("mlp_grad_reduce_kernel", s);
     hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3(kSlabReduceBlocks), dim3(kReduceParams * kReduceGroups), 0, s, sr);
     return check_launch("mlp_grad_reduce_kernel");
+}
+
+// Tile ranges per ray of the 16-point backward.  Fewer rays than the chip holds waves of that kernel (3 per SIMD = 3 072): `parts`
+// ranges per ray, never more ranges than tiles, so that the resident waves all get one item of equal length where the numbers allow
+// it (1 024 rays x 12 tiles: 3 parts of 4 tiles).  NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD (diagnostic): the old goal of one wave per SIMD.
+static uint32_t backward16_parts(const naf_render_cfg *cfg, uint32_t n_rays) {
+    const uint32_t tiles = (cfg->n_samples + 15u) / 16u;
+    const uint64_t wave_goal = (cfg->flags & NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD) != 0u ? 1024u : 4u * kBackwardBlocks16;
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(tiles, 12u), wave_goal / std::max<uint32_t>(n_rays, 1u)));
+}
+
+// Waves per workgroup of mlp16_train_kernel for a training step of n_rays rays, or 0: the step runs the forward / backward pair.
+// The kernel wants whole rays and whole slabs per workgroup -- a multiple of `parts` and of 4 waves, at most 12 (three waves per SIMD
+// of one CU; parts = 5, 7 .. 11, i.e. 257 .. 438 and 513 .. 614 rays at 12 tiles, keep the pair) -- and one work item per wave
+// (n_rays * parts <= 3 072, which kMlpTrainMaxRays implies).
+#ifndef NAF_MLP_TRAIN_MAX_RAYS
+#define NAF_MLP_TRAIN_MAX_RAYS 3072u      // the largest step with one work item per wave.  A/B builds may lower it; the one launch won
+                                          // at every size of the sweep (256 .. 3 072 rays: DESIGN.md section 4.3), so nothing smaller is set
+#endif
+constexpr uint32_t kMlpTrainMaxRays = NAF_MLP_TRAIN_MAX_RAYS;
+static_assert(kMlpTrainMaxRays <= 4u * kBackwardBlocks16, "one work item per wave");
+template <typename P, uint32_t C>
+static uint32_t mlp_train_waves(const naf_render_cfg *cfg, uint32_t n_rays) {
+    if (!(std::is_same<P, PrecBF16>::value && C == 2)) return 0u;
+    if ((cfg->flags & (NAF_CFG_MLP_TWO_KERNELS | NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD)) != 0u) return 0u;
+    if (n_rays == 0u || n_rays > kMlpTrainMaxRays || cfg->n_samples == 0u || cfg->n_samples > kMaxSamplesLds / 2u) return 0u;
+    const uint32_t parts = backward16_parts(cfg, n_rays);
+    return 4u % parts == 0u ? 4u : 12u % parts == 0u ? 12u : 0u;
 }
 
 // `loss.target` != nullptr: training step -- d loss / d acc is formed inside the kernel from (acc, target, weight), the loss itself
@@ -1078,13 +1237,20 @@ static int run_mlp_backward(const void *feat, const float *mlp, const SrcRays &s
         {
             const uint32_t sh16 = (Mlp16Shared::kBytes + 15u) & ~15u;
             const uint32_t lds16 = sh16 + std::max<uint32_t>(4u * 3u * 1024u + 4u * kMaxSamplesLds * 4u, (kMlpParams + 2u) * 4u);
-            // fewer rays than the chip holds waves of this kernel (3 per SIMD = 3 072): `parts` tile ranges per ray, never more
-            // ranges than tiles, so that the resident waves all get one item of equal length where the numbers allow it
-            // (1 024 rays x 12 tiles: 3 parts of 4 tiles).  NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD (diagnostic): the old goal of one wave per SIMD.
-            const uint32_t tiles = (cfg->n_samples + 15u) / 16u;
-            const uint64_t wave_goal = (cfg->flags & NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD) != 0u ? 1024u : 4u * kBackwardBlocks16;
-            const uint32_t parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(tiles, 12u), wave_goal / std::max<uint32_t>(n_rays, 1u)));
+            const uint32_t parts = backward16_parts(cfg, n_rays);
             const uint32_t grid16 = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)n_rays * parts + 3) / 4, kBackwardBlocks16));
+            if (ex.acc_out != nullptr) {                     // both passes in one launch; grid16 slabs, as from the pair
+                const uint32_t nw = mlp_train_waves<P, C>(cfg, n_rays);
+                if (nw == 0u || !with_loss || grad_acc != nullptr) return fail(NAF_ERR_LAUNCH, "mlp backward: this step cannot run mlp16_train_kernel");
+                auto kern = nw == 4u ? mlp16_train_kernel<4u> : mlp16_train_kernel<12u>;
+                const uint32_t lds = sh16 + nw * (3u * kImg16 + kMaxSamplesLds * 4u);
+                if (int rc = raise_lds_limit(kern, lds, "mlp16_train_kernel: cannot raise dynamic LDS limit")) return rc;
+                { ProfScope prof_("mlp_train_kernel", s); hipLaunchKernelGGL(kern, dim3((n_rays * parts + nw - 1u) / nw), dim3(64u * nw), lds, s, (const uint16_t *)feat, mlp, src,
+                                   loss, ex.acc_out, (uint16_t *)dfeat, slabs, n_rays, B, cfg->last_activation, parts, grid16, ex.clear_words); }
+                if (int rc = check_launch("mlp16_train_kernel")) return rc;
+                if (ex.after_backward != nullptr && hipEventRecord(ex.after_backward, s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "mlp backward: cannot record the event");
+                return run_mlp_grad_reduce(slabs, grid16, grad_mlp, loss_out, with_loss, madam, gmax_bits, ex, s);
+            }
             { ProfScope prof_("mlp_backward_kernel", s); hipLaunchKernelGGL(mlp16_backward_kernel, dim3(grid16), dim3(256), lds16, s, (const uint16_t *)feat, mlp, src,
                                grad_acc, loss, (uint16_t *)dfeat, slabs, n_rays, B, cfg->last_activation, parts, ex.clear_words); }
             if (int rc = check_launch("mlp16_backward_kernel")) return rc;
@@ -1280,7 +1446,8 @@ static int render_backward_impl(const float *rays, const float *t_rand, const fl
                                 const float *mlp, float *grad_emb, float *grad_mlp, uint32_t n_rays, const naf_render_cfg *cfg,
                                 void *ws, int features_valid, const naf_grad_buckets *buckets, hipStream_t s,
                                 const AdamTail *adam = nullptr, bool from_train = false, const LossInputs &loss = LossInputs{nullptr, nullptr, nullptr},
-                                float *loss_out = nullptr, const MlpAdam *madam = nullptr, bool loss_assign = false, DrawJob *next_draw = nullptr) {
+                                float *loss_out = nullptr, const MlpAdam *madam = nullptr, bool loss_assign = false, DrawJob *next_draw = nullptr,
+                                float *acc_out = nullptr) {
     const uint32_t B = n_rays * cfg->n_samples;
     const Workspace w = carve(ws, cfg, B);
     const SrcRays src = make_src(rays, t_rand, cfg);
@@ -1298,7 +1465,7 @@ static int render_backward_impl(const float *rays, const float *t_rand, const fl
     // `mlp_ready`), per-level diagnostics keep their launches apart.
     SlabReduce job{};
     const bool defer = w.binned && buckets == nullptr && !per_level_launches(cfg);
-    const StepExtras ex{w.bin.overflow, loss_assign, defer ? &job : nullptr};
+    const StepExtras ex{w.bin.overflow, loss_assign, defer ? &job : nullptr, nullptr, acc_out};
     if (int rc = run_mlp_backward<P, C>(w.feat, mlp, src, grad_acc, loss, w.dfeat, w.slabs, w.bin.gmax, grad_mlp, loss_out, madam, n_rays, B, cfg,
                                         ex, s)) return rc;
     // grad_mlp (and, in the training entry point, the loss) are final here, before the table scatter starts
@@ -1312,12 +1479,16 @@ static int render_train_impl(const float *rays, const float *t_rand, const float
                              const int32_t *offsets, const float *mlp, float *acc, float *grad_emb, float *grad_mlp, float *loss_out,
                              uint32_t n_rays, const naf_render_cfg *cfg, void *ws, const naf_grad_buckets *buckets, hipStream_t s,
                              const AdamTail *adam = nullptr, const MlpAdam *madam = nullptr, bool loss_assign = false, DrawJob *next_draw = nullptr) {
-    if (int rc = render_forward_impl<P, C>(rays, t_rand, emb, offsets, mlp, acc, n_rays, cfg, ws, s, nullptr, nullptr, true)) return rc;
+    // small bf16 steps: the encoder alone here, forward and backward of the MLP in one launch below (mlp16_train_kernel)
+    const bool one_launch = mlp_train_waves<P, C>(cfg, n_rays) != 0u;
+    if (one_launch) {
+        if (int rc = dispatch_encode<P, C>(make_src(rays, t_rand, cfg), emb, offsets, ws, n_rays * cfg->n_samples, cfg, s)) return rc;
+    } else if (int rc = render_forward_impl<P, C>(rays, t_rand, emb, offsets, mlp, acc, n_rays, cfg, ws, s, nullptr, nullptr, true)) return rc;
     // the masked squared error and its gradient are formed inside the backward kernel (LossInputs); the loss reaches loss_out
     // through the slab reduction that also finishes the MLP gradient
     const LossInputs loss{acc, target, ray_weight};
     return render_backward_impl<P, C>(rays, t_rand, nullptr, emb, offsets, mlp, grad_emb, grad_mlp, n_rays, cfg, ws, 1, buckets, s, adam, true,
-                                      loss, loss_out, madam, loss_assign, next_draw);
+                                      loss, loss_out, madam, loss_assign, next_draw, one_launch ? acc : nullptr);
 }
 
 template <typename P, uint32_t C>
@@ -1411,9 +1582,11 @@ static int levels_field_impl(const float *rays, const float *t_rand, const float
     const uint32_t B = n_rays * cfg->n_samples;
     const Workspace w = carve(ws, cfg, B);
     const SrcRays src = make_src(rays, t_rand, cfg);
-    if (int rc = run_mlp_forward<P, C, true>(features, mlp, src, acc, n_rays, B, cfg, s)) return rc;
+    const bool one_launch = mlp_train_waves<P, C>(cfg, n_rays) != 0u;
+    if (!one_launch)
+        if (int rc = run_mlp_forward<P, C, true>(features, mlp, src, acc, n_rays, B, cfg, s)) return rc;
     const LossInputs loss{acc, target, ray_weight};
-    const StepExtras ex{nullptr, true, nullptr, grads_ready};
+    const StepExtras ex{nullptr, true, nullptr, grads_ready, one_launch ? acc : nullptr};
     return run_mlp_backward<P, C>(features, mlp, src, nullptr, loss, feature_grads, w.slabs, nullptr, grad_mlp, loss_out, nullptr, n_rays, B, cfg, ex, s);
 }
 

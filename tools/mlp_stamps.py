@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Phase stamps of mlp16_backward_kernel (library built with -DNAF_MLP_STAMPS, tools/build_variant.sh): shader-clock cycles from kernel
 entry to the end of the weight-fragment build, of the tile loop, of the barrier behind it, of the four-wave fold and of the slab store,
-per workgroup; plus the 100 MHz wall clock at entry and exit (launch skew between workgroups).
+per workgroup; plus the 100 MHz wall clock at entry and exit (launch skew between workgroups).  The fold is shared with
+mlp16_train_kernel (mlp16_fold_slab) and is stamped as a whole: "barrier" and "fold done" repeat "slab stored".  Small steps are run
+with NAF_CFG_MLP_TWO_KERNELS, since only the kernel pair carries stamps.
     python tools/mlp_stamps.py [--rays 1024]"""
 import argparse
 import json
@@ -13,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
-from neuralvolumetricreconstructionformedicalimages_amd import fused  # noqa: E402
+from neuralvolumetricreconstructionformedicalimages_amd import _abi, fused  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--rays", type=int, default=1024)
@@ -21,6 +23,7 @@ args = ap.parse_args()
 dev = torch.device("cuda")
 scan = bench.ChestScan(dev, 1234, with_volume=False)
 eng = bench.make_chest_engine(dev, "bf16", None, None, 0)
+eng.cfg_flags = (eng.cfg_flags or 0) | _abi.CFG_MLP_TWO_KERNELS
 n = args.rays
 rays = torch.empty(n, 8, device=dev)
 w, _ = bench.step_weights(n, dev)
