@@ -471,6 +471,27 @@ size_t naf_ssim_3d_workspace_bytes(uint32_t n1, uint32_t n2, uint32_t n3);
 int naf_ssim_3d(const float *x, const float *y, uint32_t n1, uint32_t n2, uint32_t n3, double *out, void *workspace,
                 size_t workspace_bytes, void *stream);
 
+/* V1  resize a volume with the cubic B-spline, no prefilter: the resize of the reference's `loadImage`
+ * (dataGenerator/generateData.py:111-150), scipy.ndimage.zoom(order=3, prefilter=False) with its default grid.  DESIGN.md section 12.
+ *   in   f32 [a1, a2, a3], out f32 [b1, b2, b3], both C-contiguous; in_dims / out_dims HOST u32 [3], every extent >= 1
+ *   coordinates  output index j of an axis with a inputs and b outputs sits at x = j * r, r = (a - 1) / (b - 1) for b > 1 and
+ *                r = 1 for b = 1; the division and the product are IEEE double
+ *   weights      f = floor(x), t = x - f; the taps f - 1 .. f + 2 carry (1-t)^3/6, (3t^3 - 6t^2 + 4)/6, (-3t^3 + 3t^2 + 3t + 1)/6,
+ *                t^3/6, formed in double and rounded to fp32 once
+ *   boundary     a tap index i outside [0, a - 1] is mirrored about the edge samples (whole-sample symmetric): i mod 2(a - 1),
+ *                then 2(a - 1) - i if that is >= a; an axis with a = 1 maps every tap to 0
+ *   sum          out = the separable 4 x 4 x 4 weighted sum in fp32 of v = fma(in, scale, shift) (the weights sum to 1, so this
+ *                equals resizing scale * in + shift); there is no prefilter: an axis with a = b is still filtered with
+ *                (1/6, 4/6, 1/6), the result is a smoothing and not an interpolation
+ *   minmax       NULL, or DEVICE f32 [2] = minimum and maximum of `out`; both NaN if any output is NaN.  Per-workgroup pairs go to
+ *                the workspace and are folded in a fixed order (no atomics): two calls return the same bits
+ * A zero extent is NAF_ERR_UNSUPPORTED.  `workspace`: naf_resize_volume_workspace_bytes(in_dims, out_dims) bytes (0 for a null
+ * pointer or a zero extent), 16-byte aligned; it holds the per-axis tap tables and the per-workgroup pairs.  No full-size
+ * intermediate, no host synchronisation inside the call.  Offsets are 64-bit (a 1024^3 output is 4 GiB). */
+size_t naf_resize_volume_workspace_bytes(const uint32_t *in_dims, const uint32_t *out_dims);
+int naf_resize_volume(const float *in, const uint32_t *in_dims, float scale, float shift, float *out, const uint32_t *out_dims,
+                      float *minmax, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,3 +3,5 @@ reference project's Python surface.  Compute lives in lib/libnaf_hip.so (hand-wr
 include/naf_hip.h); PyTorch-ROCm supplies device memory, streams and torch.distributed only."""
 
 __version__ = "0.1.0"
+
+from .volume import prepare_volume, resize_volume  # noqa: E402,F401
