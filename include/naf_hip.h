@@ -456,6 +456,24 @@ int naf_project_scan(const float *volume, const uint32_t *dims, const float *dvo
                      uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
                      int parallel, float step, float *out, void *stream);
 
+/* P2  back-projector: the transpose of P1.  With A the linear map volume -> projections of naf_project_rays / naf_project_scan,
+ * these add A^T y into `volume`.
+ *   values / projections  f32, one value y_r per ray: [n_rays], or [n_projections, det_h, det_w] with the rays of naf_project_scan
+ *   volume  f32 [n1, n2, n3] as in P1, ACCUMULATED INTO (+=): the caller zeroes it, so a scan can be back-projected in groups of views
+ * Ray r takes P1's own t0, t1, len, n and seg in fp32, the same sample positions fma(s_k, d, fma(t0, d, o)) and the same trilinear
+ * cell and weights (u_a clamped, i_a = min(floor(u_a), n_a - 2), w_a = u_a - i_a, an axis of one voxel constant: its w_a is 0).
+ * Sample k adds y_r * (len / n) * w_c to each of its eight corner voxels c, w_c = prod_a (w_a or 1 - w_a).  A ray with an empty
+ * segment adds nothing, and neither does a NaN / infinite ray for which P1 returns NaN.  Consecutive samples of a ray that share a
+ * cell have their w_c summed in registers first and y_r * (len / n) applied to the sum; terms that are exactly 0 are not sent.
+ * The sums into the volume are fp32 hardware float atomics, so the result equals A^T y up to rounding and SUMMATION ORDER: this is
+ * the one place in the non-training kernels where two calls on the same inputs need not return the same bits.
+ * All volume offsets are 64-bit.  Empty batches (n_rays == 0, n_projections == 0) return NAF_OK without examining the pointers. */
+int naf_backproject_rays(const float *values, const float *rays, uint64_t n_rays, uint32_t n1, uint32_t n2, uint32_t n3,
+                         const float *dvoxel, float step, float *volume, void *stream);
+int naf_backproject_scan(const float *projections, const uint32_t *dims, const float *dvoxel, const float *poses,
+                         uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD,
+                         float near, float far, int parallel, float step, float *volume, void *stream);
+
 /* M1  3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
  * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
  * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.

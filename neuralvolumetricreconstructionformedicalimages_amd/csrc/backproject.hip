@@ -1,0 +1,125 @@
+// backproject.hip -- the transpose of the forward projector for gfx950: naf_backproject_rays scatters one value per ray into a voxel
+// volume, naf_backproject_scan does it for every pixel ray of a scan.  With A = naf_project_scan this is A^T to rounding and
+// summation order: the segment, the samples and the trilinear cell of every sample come from project_device.h, the code the forward
+// kernel runs.  Defined in include/naf_hip.h (P2) and DESIGN.md section 13.
+//
+// Layout: the forward's.  One lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave, so the 64 lanes of a wave at
+// equal k add into a small neighbourhood of the volume.  The sample spacing is half a voxel, so consecutive samples of a ray often
+// share their cell: the eight corner weights are summed in registers while the cell stays the same and go out as eight fp32 hardware
+// atomics when it changes.  Built with -DNAF_BACKPROJECT_PER_SAMPLE every sample sends its own eight atomics (the A/B of section 13).
+#include "draw_device.h"
+#include "project_device.h"
+
+namespace naf {
+
+namespace {
+
+// Adds scale * acc[c] to the eight corners of the cell at `q`; corners that got no weight (a constant axis, a sample on a voxel
+// centre) are skipped.  Corner c = 4 cx + 2 cy + cz.
+__device__ __forceinline__ void flush_cell(float *__restrict__ q, const ProjVolume &v, float scale, const float acc[8]) {
+    const uint64_t sx = v.next[0], sy = v.next[1], sz = v.next[2];
+    const uint64_t off[8] = {0, sz, sy, sy + sz, sx, sx + sz, sx + sy, sx + sy + sz};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float add = scale * acc[c];
+        if (add != 0.0f) atomicAdd(q + off[c], add);          // no-return global_atomic_add_f32
+    }
+}
+
+// value * (len / n) * w_c into the corners of every sample of the ray.  An empty segment and a NaN / infinite ray add nothing.
+__device__ __forceinline__ void scatter_ray(const ProjVolume &v, float *__restrict__ volume, float4 a, float4 b, float value) {
+    RaySpan s;
+    if (ray_span(v, a, b, s) != kSpanOk) return;
+    const float scale = value * s.weight;
+    constexpr uint64_t kNoCell = ~0ull;
+    uint64_t cell = kNoCell;
+    float acc[8];
+    for (uint32_t k = 0; k < s.n; ++k) {
+        float p[3], w[3];
+        span_point(s, k, p);
+        const uint64_t base = trilinear_cell(v, p[0], p[1], p[2], w);
+#ifdef NAF_BACKPROJECT_PER_SAMPLE
+        const bool moved = true;
+#else
+        const bool moved = base != cell;
+#endif
+        if (moved) {
+            if (cell != kNoCell) flush_cell(volume + cell, v, scale, acc);
+            cell = base;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) acc[c] = 0.0f;
+        }
+        const float x[2] = {1.0f - w[0], w[0]}, y[2] = {1.0f - w[1], w[1]}, z[2] = {1.0f - w[2], w[2]};
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc[c] += (x[c >> 2] * y[(c >> 1) & 1]) * z[c & 1];
+    }
+    if (cell != kNoCell) flush_cell(volume + cell, v, scale, acc);
+}
+
+__global__ void __launch_bounds__(256)
+backproject_rays_kernel(ProjVolume v, float *__restrict__ volume, const float *__restrict__ values, const float *__restrict__ rays,
+                        uint64_t n_rays) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rays) return;
+    const float4 *r = reinterpret_cast<const float4 *>(rays + i * 8);
+    scatter_ray(v, volume, r[0], r[1], values[i]);
+}
+
+// blockIdx.x = projection * tiles_per_projection + tile, as in project_scan_kernel.
+__global__ void __launch_bounds__(256)
+backproject_scan_kernel(ProjVolume v, float *__restrict__ volume, const float *__restrict__ projections, const float *__restrict__ poses,
+                        RayGeo g, uint32_t tiles_x, uint32_t tiles_per_proj) {
+    const uint32_t proj = blockIdx.x / tiles_per_proj, tile = blockIdx.x - proj * tiles_per_proj;
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    uint32_t row, col;
+    tile_pixel(tx, ty, threadIdx.x, row, col);
+    if (row >= g.H || col >= g.W) return;
+    const uint64_t flat = (uint64_t)proj * g.W * g.H + (uint64_t)row * g.W + col;
+    float4 r[2];
+    make_ray(poses, flat, g, r);
+    scatter_ray(v, volume, r[0], r[1], projections[flat]);
+}
+
+}  // namespace
+
+}  // namespace naf
+
+using namespace naf;
+
+extern "C" int naf_backproject_rays(const float *values, const float *rays, uint64_t n_rays, uint32_t n1, uint32_t n2, uint32_t n3,
+                                    const float *dvoxel, float step, float *volume, void *stream) {
+    if (n_rays == 0) return NAF_OK;
+    ProjVolume v;
+    const int rc = make_volume("backproject_rays", volume, n1, n2, n3, dvoxel, step, &v);
+    if (rc != NAF_OK) return rc;
+    if (!values || !rays) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays: null pointer");
+    if (((uintptr_t)rays) & 15u) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays: rays must be 16-byte aligned");
+    const uint64_t blocks = (n_rays + 255u) / 256u;
+    if (blocks > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays: too many rays for one call");
+    { ProfScope prof_("backproject_rays_kernel", (hipStream_t)stream);
+      hipLaunchKernelGGL(backproject_rays_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, v, volume, values, rays,
+                         n_rays); }
+    return check_launch("backproject_rays_kernel");
+}
+
+extern "C" int naf_backproject_scan(const float *projections, const uint32_t *dims, const float *dvoxel, const float *poses,
+                                    uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
+                                    float DSD, float near, float far, int parallel, float step, float *volume, void *stream) {
+    if (n_projections == 0) return NAF_OK;
+    if (!dims) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: null pointer");
+    ProjVolume v;
+    const int rc = make_volume("backproject_scan", volume, dims[0], dims[1], dims[2], dvoxel, step, &v);
+    if (rc != NAF_OK) return rc;
+    if (!poses || !projections) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: null pointer");
+    if (det_w == 0 || det_h == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: empty detector");
+    if (!parallel && !(DSD > 0.0f)) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: DSD must be > 0 for a cone beam");
+    const uint32_t tiles_x = (det_w + kProjTile - 1u) / kProjTile, tiles_y = (det_h + kProjTile - 1u) / kProjTile;
+    const uint64_t per_proj = (uint64_t)tiles_x * tiles_y;
+    if (per_proj * n_projections > 0x7fffffffull)
+        return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: too many pixels for one call");
+    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
+    { ProfScope prof_("backproject_scan_kernel", (hipStream_t)stream);
+      hipLaunchKernelGGL(backproject_scan_kernel, dim3((uint32_t)(per_proj * n_projections)), dim3(256), 0, (hipStream_t)stream, v,
+                         volume, projections, poses, g, tiles_x, (uint32_t)per_proj); }
+    return check_launch("backproject_scan_kernel");
+}

@@ -6,41 +6,17 @@
 // covers 16 x 16 pixels), so that the samples of neighbouring rays at equal k land in the same or neighbouring cache lines.
 // Built with -DNAF_PROJECT_ROW_STRIP the scan kernel takes 256 consecutive pixels of a detector row per workgroup instead
 // (the layout A/B of DESIGN.md section 10).
-#include <cmath>
-#include <cstdio>
-
 #include "draw_device.h"
-#include "naf_host.h"
+#include "project_device.h"
 
 namespace naf {
 
 namespace {
 
-struct ProjVolume {
-    const float *__restrict__ data;  // [n1, n2, n3] fp32, axis 0 = x, C-contiguous
-    uint32_t n[3];
-    uint32_t imax[3];                // max(n_a - 2, 0): the largest lower corner
-    uint64_t stride[3];              // n2 * n3, n3, 1
-    uint64_t next[3];                // stride of the upper corner: 0 when n_a == 1 (constant axis)
-    float half[3];                   // sVoxel / 2
-    float inv_d[3];                  // 1 / dVoxel
-    float step;                      // target sample spacing in metres (accuracy * min dVoxel)
-};
-
 // Value of the volume at p: trilinear, clamp-to-edge.  Only called for points inside the box (midpoints of the clipped segment).
 __device__ __forceinline__ float sample_volume(const ProjVolume &v, float px, float py, float pz) {
-    const float p[3] = {px, py, pz};
-    uint64_t base = 0;
     float w[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float u = (p[a] + v.half[a]) * v.inv_d[a] - 0.5f;
-        u = fminf(fmaxf(u, 0.0f), (float)(v.n[a] - 1u));
-        const uint32_t i = min((uint32_t)u, v.imax[a]);      // u >= 0: truncation is floor
-        w[a] = u - (float)i;
-        base += (uint64_t)i * v.stride[a];                    // 64-bit: a 1024^3 volume is 4 GiB
-    }
-    const float *__restrict__ q = v.data + base;
+    const float *__restrict__ q = v.data + trilinear_cell(v, px, py, pz, w);
     const uint64_t sx = v.next[0], sy = v.next[1], sz = v.next[2];
     const float c000 = q[0], c001 = q[sz], c010 = q[sy], c011 = q[sy + sz];
     const float c100 = q[sx], c101 = q[sx + sz], c110 = q[sx + sy], c111 = q[sx + sy + sz];
@@ -50,39 +26,21 @@ __device__ __forceinline__ float sample_volume(const ProjVolume &v, float px, fl
     return c0 + w[0] * (c1 - c0);
 }
 
-// Midpoint-rule line integral of one ray (o, d, near, far); d is un-normalised.  t0, t1 and n are the quantities a float32
-// restatement reproduces exactly (IEEE add / multiply / divide / sqrt, no contraction: build.py passes -ffp-contract=off).
+// Midpoint-rule line integral of one ray (o, d, near, far); d is un-normalised.  Segment, sample count and sample positions come
+// from project_device.h, shared with the transpose.
 __device__ __forceinline__ float line_integral(const ProjVolume &v, float4 a, float4 b) {
-    const float o[3] = {a.x, a.y, a.z}, d[3] = {a.w, b.x, b.y};
-    float t0 = b.z, t1 = b.w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (d[k] == 0.0f) {
-            if (o[k] < -v.half[k] || o[k] > v.half[k]) t1 = -INFINITY;    // parallel to the slab and outside it
-            continue;
-        }
-        const float ta = (-v.half[k] - o[k]) / d[k], tb = (v.half[k] - o[k]) / d[k];
-        const float lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
-        t0 = lo > t0 ? lo : t0;
-        t1 = hi < t1 ? hi : t1;
-    }
-    if (!(t1 > t0)) return 0.0f;
-    const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    const float len = (t1 - t0) * dn;
-    const float nf = fmaxf(1.0f, ceilf(len / v.step));
-    if (!(nf < 16777216.0f)) return __builtin_nanf("");     // NaN / infinite ray: no sample loop of 2^24+ steps
-    const uint32_t n = (uint32_t)nf;
-    const float seg = (t1 - t0) / nf;
-    // Sample k sits at p0 + s_k d with p0 = o + t0 d and s_k = (k + 1/2) seg, each a single-rounding fma: a cone ray's origin is
-    // ~1 m from the volume, and o + t d with an fp32 t ~ 1 would place every sample ~6e-8 m (6e-5 of a 1 mm voxel) off its spot.
-    const float p0[3] = {fmaf(t0, d[0], o[0]), fmaf(t0, d[1], o[1]), fmaf(t0, d[2], o[2])};
+    RaySpan s;
+    const SpanKind kind = ray_span(v, a, b, s);
+    if (kind == kSpanEmpty) return 0.0f;
+    if (kind == kSpanUnbounded) return __builtin_nanf("");
     float acc = 0.0f;
 #pragma unroll 4
-    for (uint32_t k = 0; k < n; ++k) {                        // position from k, not by increments; fp32 sum in k order
-        const float s = ((float)k + 0.5f) * seg;
-        acc += sample_volume(v, fmaf(s, d[0], p0[0]), fmaf(s, d[1], p0[1]), fmaf(s, d[2], p0[2]));
+    for (uint32_t k = 0; k < s.n; ++k) {                      // position from k, not by increments; fp32 sum in k order
+        float p[3];
+        span_point(s, k, p);
+        acc += sample_volume(v, p[0], p[1], p[2]);
     }
-    return acc * (len / nf);
+    return acc * s.weight;
 }
 
 __global__ void __launch_bounds__(256)
@@ -93,7 +51,7 @@ project_rays_kernel(ProjVolume v, const float *__restrict__ rays, float *__restr
     out[i] = line_integral(v, r[0], r[1]);
 }
 
-constexpr uint32_t kTile = 16;       // 2-D layout: 16 x 16 pixels per workgroup, 8 x 8 per wave
+constexpr uint32_t kTile = kProjTile; // 2-D layout: 16 x 16 pixels per workgroup, 8 x 8 per wave
 constexpr uint32_t kStrip = 256;     // row-strip layout: 256 pixels of one row per workgroup
 
 #ifdef NAF_PROJECT_ROW_STRIP
@@ -113,50 +71,13 @@ project_scan_kernel(ProjVolume v, const float *__restrict__ poses, RayGeo g, flo
         row = ty;
         col = tx * kStrip + threadIdx.x;
     } else {
-        const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-        row = ty * kTile + (wave >> 1) * 8u + (lane >> 3);
-        col = tx * kTile + (wave & 1u) * 8u + (lane & 7u);
+        tile_pixel(tx, ty, threadIdx.x, row, col);
     }
     if (row >= g.H || col >= g.W) return;
     const uint64_t flat = (uint64_t)proj * g.W * g.H + (uint64_t)row * g.W + col;
     float4 r[2];
     make_ray(poses, flat, g, r);
     out[flat] = line_integral(v, r[0], r[1]);
-}
-
-int make_volume(const char *who, const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, float step,
-                ProjVolume *v) {
-    char msg[160];
-    if (!volume || !dvoxel) {
-        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (n1 == 0 || n2 == 0 || n3 == 0) {
-        std::snprintf(msg, sizeof(msg), "%s: zero volume dimension", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (!(step > 0.0f) || !std::isfinite(step)) {
-        std::snprintf(msg, sizeof(msg), "%s: step must be > 0", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    const uint32_t n[3] = {n1, n2, n3};
-    for (int a = 0; a < 3; ++a) {
-        if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) {
-            std::snprintf(msg, sizeof(msg), "%s: voxel size must be > 0", who);
-            return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-        }
-        v->n[a] = n[a];
-        v->imax[a] = n[a] >= 2u ? n[a] - 2u : 0u;
-        v->half[a] = (float)((double)n[a] * (double)dvoxel[a] / 2.0);
-        v->inv_d[a] = 1.0f / dvoxel[a];
-    }
-    v->data = volume;
-    v->stride[0] = (uint64_t)n2 * n3;
-    v->stride[1] = n3;
-    v->stride[2] = 1;
-    for (int a = 0; a < 3; ++a) v->next[a] = n[a] > 1u ? v->stride[a] : 0u;
-    v->step = step;
-    return NAF_OK;
 }
 
 }  // namespace

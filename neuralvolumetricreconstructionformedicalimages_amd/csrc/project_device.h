@@ -1,0 +1,135 @@
+// project_device.h -- the pieces of the projection definition (include/naf_hip.h P1) that the forward
+// projector (project.hip) and its transpose (backproject.hip) must share to the bit: the volume's grid, the clipped segment of a
+// ray with its sample count, the sample positions, and the trilinear cell with its three weights.
+#pragma once
+
+#include <cmath>
+#include <cstdio>
+
+#include "naf_host.h"
+
+namespace naf {
+
+struct ProjVolume {
+    const float *__restrict__ data;  // [n1, n2, n3] fp32, axis 0 = x, C-contiguous (the forward's input; unused by the transpose)
+    uint32_t n[3];
+    uint32_t imax[3];                // max(n_a - 2, 0): the largest lower corner
+    uint64_t stride[3];              // n2 * n3, n3, 1
+    uint64_t next[3];                // stride of the upper corner: 0 when n_a == 1 (constant axis)
+    float half[3];                   // sVoxel / 2
+    float inv_d[3];                  // 1 / dVoxel
+    float step;                      // target sample spacing in metres (accuracy * min dVoxel)
+};
+
+// Trilinear cell of p, clamp-to-edge: offset of the lower corner (64-bit: a 1024^3 volume is 4 GiB) and the weights w_a of the
+// upper corners.  Only called for points inside the box (midpoints of the clipped segment); the clamp keeps every p in bounds.
+__device__ __forceinline__ uint64_t trilinear_cell(const ProjVolume &v, float px, float py, float pz, float w[3]) {
+    const float p[3] = {px, py, pz};
+    uint64_t base = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float u = (p[a] + v.half[a]) * v.inv_d[a] - 0.5f;
+        u = fminf(fmaxf(u, 0.0f), (float)(v.n[a] - 1u));
+        const uint32_t i = min((uint32_t)u, v.imax[a]);      // u >= 0: truncation is floor
+        w[a] = u - (float)i;
+        base += (uint64_t)i * v.stride[a];
+    }
+    return base;
+}
+
+// The part of a ray inside the box and [near, far], cut into n midpoint-rule samples.  t0, t1 and n are the quantities a float32
+// restatement reproduces exactly (IEEE add / multiply / divide / sqrt, no contraction: build.py passes -ffp-contract=off).
+struct RaySpan {
+    float p0[3], d[3];               // p0 = o + t0 d
+    float seg;                       // (t1 - t0) / n
+    float weight;                    // len / n: what one sample contributes per unit of the volume's value
+    uint32_t n;
+};
+
+enum SpanKind { kSpanEmpty = 0, kSpanOk = 1, kSpanUnbounded = 2 };   // unbounded: NaN / infinite ray, no loop of 2^24+ steps
+
+__device__ __forceinline__ SpanKind ray_span(const ProjVolume &v, float4 a, float4 b, RaySpan &s) {
+    const float o[3] = {a.x, a.y, a.z}, d[3] = {a.w, b.x, b.y};
+    float t0 = b.z, t1 = b.w;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (d[k] == 0.0f) {
+            if (o[k] < -v.half[k] || o[k] > v.half[k]) t1 = -INFINITY;    // parallel to the slab and outside it
+            continue;
+        }
+        const float ta = (-v.half[k] - o[k]) / d[k], tb = (v.half[k] - o[k]) / d[k];
+        const float lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
+        t0 = lo > t0 ? lo : t0;
+        t1 = hi < t1 ? hi : t1;
+    }
+    if (!(t1 > t0)) return kSpanEmpty;
+    const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const float len = (t1 - t0) * dn;
+    const float nf = fmaxf(1.0f, ceilf(len / v.step));
+    if (!(nf < 16777216.0f)) return kSpanUnbounded;
+    s.n = (uint32_t)nf;
+    s.seg = (t1 - t0) / nf;
+    s.weight = len / nf;
+    // Sample k sits at p0 + s_k d with p0 = o + t0 d and s_k = (k + 1/2) seg, each a single-rounding fma: a cone ray's origin is
+    // ~1 m from the volume, and o + t d with an fp32 t ~ 1 would place every sample ~6e-8 m (6e-5 of a 1 mm voxel) off its spot.
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        s.d[k] = d[k];
+        s.p0[k] = fmaf(t0, d[k], o[k]);
+    }
+    return kSpanOk;
+}
+
+// Position of sample k, from k and not by increments.
+__device__ __forceinline__ void span_point(const RaySpan &s, uint32_t k, float p[3]) {
+    const float t = ((float)k + 0.5f) * s.seg;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = fmaf(t, s.d[a], s.p0[a]);
+}
+
+// Host: argument checks shared by the entry points, and the grid of a [n1, n2, n3] volume with voxel size dvoxel (HOST f32 [3]).
+inline int make_volume(const char *who, const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, float step,
+                       ProjVolume *v) {
+    char msg[160];
+    if (!volume || !dvoxel) {
+        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    if (n1 == 0 || n2 == 0 || n3 == 0) {
+        std::snprintf(msg, sizeof(msg), "%s: zero volume dimension", who);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    if (!(step > 0.0f) || !std::isfinite(step)) {
+        std::snprintf(msg, sizeof(msg), "%s: step must be > 0", who);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    const uint32_t n[3] = {n1, n2, n3};
+    for (int a = 0; a < 3; ++a) {
+        if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) {
+            std::snprintf(msg, sizeof(msg), "%s: voxel size must be > 0", who);
+            return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+        }
+        v->n[a] = n[a];
+        v->imax[a] = n[a] >= 2u ? n[a] - 2u : 0u;
+        v->half[a] = (float)((double)n[a] * (double)dvoxel[a] / 2.0);
+        v->inv_d[a] = 1.0f / dvoxel[a];
+    }
+    v->data = volume;
+    v->stride[0] = (uint64_t)n2 * n3;
+    v->stride[1] = n3;
+    v->stride[2] = 1;
+    for (int a = 0; a < 3; ++a) v->next[a] = n[a] > 1u ? v->stride[a] : 0u;
+    v->step = step;
+    return NAF_OK;
+}
+
+constexpr uint32_t kProjTile = 16;   // scan kernels: 16 x 16 pixels per workgroup, 8 x 8 per wave
+
+// Pixel of lane `t` (of 256) in tile (tx, ty) of the 2-D layout.
+__device__ __forceinline__ void tile_pixel(uint32_t tx, uint32_t ty, uint32_t t, uint32_t &row, uint32_t &col) {
+    const uint32_t wave = t >> 6, lane = t & 63u;
+    row = ty * kProjTile + (wave >> 1) * 8u + (lane >> 3);
+    col = tx * kProjTile + (wave & 1u) * 8u + (lane & 7u);
+}
+
+}  // namespace naf

@@ -94,3 +94,70 @@ def project_scan(volume, geo, angles, views_per_call=None):
             float(raygen.near), float(raygen.far), int(geo.mode == "parallel"), step, _abi.ptr(out[first:first + count]),
             _abi.stream_ptr()), "project_scan")
     return out
+
+
+def _check_out(out, shape, like, who):
+    """`out=None` allocates zeros; a given `out` is accumulated into."""
+    if out is None:
+        return torch.zeros(shape, device=like.device, dtype=torch.float32)
+    _abi.check_volume(out, who, "out")
+    if tuple(out.shape) != tuple(shape) or out.device != like.device:
+        raise ValueError(f"{who}: out must be a contiguous float32 {tuple(shape)} tensor on the input's device")
+    return out
+
+
+def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None):
+    """Transpose of `project_rays`: adds `values` [n] along `rays` [n, 8] into a volume of `dims` = (n1, n2, n3) voxels of size
+    `dvoxel` -> float32 [n1, n2, n3].  Sums are fp32 atomics: equal to A^T values up to summation order (naf_hip.h, P2)."""
+    if not isinstance(values, torch.Tensor) or not values.is_cuda:
+        raise RuntimeError("backproject_rays: values must be a CUDA/HIP tensor (no CPU path)")
+    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device != values.device:
+        raise RuntimeError("backproject_rays: rays must be a CUDA/HIP tensor on the values' device")
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError(f"backproject_rays: rays must be float32 [n, 8], got {rays.dtype} {tuple(rays.shape)}")
+    n = rays.shape[0]
+    if values.dtype != torch.float32 or tuple(values.shape) != (n,):
+        raise ValueError(f"backproject_rays: values must be float32 [{n}], got {values.dtype} {tuple(values.shape)}")
+    if not rays.is_contiguous() or not values.is_contiguous():
+        raise ValueError("backproject_rays: values and rays must be contiguous")
+    dims = tuple(int(v) for v in dims)
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError(f"backproject_rays: dims must be three positive extents, got {dims}")
+    out = _check_out(out, dims, values, "backproject_rays")
+    _abi.check(_abi.lib().naf_backproject_rays(_abi.ptr(values), _abi.ptr(rays), n, dims[0], dims[1], dims[2],
+                                               ctypes.byref(_dvoxel(dvoxel)), sample_step(dvoxel, accuracy), _abi.ptr(out),
+                                               _abi.stream_ptr()), "backproject_rays")
+    return out
+
+
+def backproject_scan(projections, geo, angles, views_per_call=None, out=None):
+    """Transpose of `project_scan`: adds `projections` [N, H, W] of the scan geometry `geo` at `angles` into a volume on the voxel
+    grid of `geo` -> float32 nVoxel.  Views go to the kernel in groups of `views_per_call` like `project_scan`'s."""
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError("backproject_scan: projections must be a CUDA/HIP tensor (no CPU path)")
+    dims = tuple(int(v) for v in geo.nVoxel)
+    out = _check_out(out, dims, projections, "backproject_scan")
+    check_geometry(out, geo)
+    angles = np.asarray(angles, dtype=np.float64).reshape(-1)
+    N, H, W = len(angles), int(geo.nDetector[1]), int(geo.nDetector[0])
+    if projections.dtype != torch.float32 or tuple(projections.shape) != (N, H, W):
+        raise ValueError(f"backproject_scan: projections must be float32 {(N, H, W)}, got {projections.dtype} "
+                         f"{tuple(projections.shape)}")
+    if not projections.is_contiguous():
+        raise ValueError("backproject_scan: projections must be contiguous")
+    if N == 0:
+        return out
+    raygen = RayGenerator(geo, angles, projections.device)
+    per_call = views_per_call or max(1, MAX_PIXELS_PER_CALL // (H * W))
+    cdims = (ctypes.c_uint32 * 3)(*dims)
+    dv = _dvoxel(geo.dVoxel)
+    step = sample_step(geo.dVoxel, geo.accuracy)
+    lib = _abi.lib()
+    for first in range(0, N, per_call):
+        count = min(per_call, N - first)
+        _abi.check(lib.naf_backproject_scan(
+            _abi.ptr(projections[first:first + count]), ctypes.byref(cdims), ctypes.byref(dv),
+            _abi.ptr(raygen.poses[first:first + count]), count, W, H, float(geo.dDetector[0]), float(geo.dDetector[1]),
+            float(geo.offDetector[0]), float(geo.offDetector[1]), float(geo.DSD), float(raygen.near), float(raygen.far),
+            int(geo.mode == "parallel"), step, _abi.ptr(out), _abi.stream_ptr()), "backproject_scan")
+    return out

@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""SIRT baseline for a scan in the pickle schema train.py reads: reconstructs the `train` projections on the scan's own voxel
+grid with the HIP forward projector and its transpose (reconstruct.sirt) and scores the volume against the
+pickle's `image` with the metrics of train.py's evaluation.
+
+    python tools/reconstruct_sirt.py --scan data/chest_50.pickle --iters 100
+    python tools/reconstruct_sirt.py --scan data/chest_50.pickle --iters 100 --relax 0.8 --out sirt_chest.npy
+
+Prints one JSON line: psnr_3d (utils.get_psnr_3d), ssim_3d (metrics.ssim_3d), the first and last weighted residual and the time.
+"""
+import argparse
+import json
+import os
+import pickle
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    from neuralvolumetricreconstructionformedicalimages_amd import metrics, sirt
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    from neuralvolumetricreconstructionformedicalimages_amd.utils import get_psnr_3d
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scan", required=True, help="pickle with the reference's schema (tools/make_synthetic_scan.py, make_scan_from_volume.py)")
+    ap.add_argument("--iters", type=int, required=True)
+    ap.add_argument("--relax", type=float, default=1.0)
+    ap.add_argument("--no-nonneg", action="store_true", help="do not clamp the volume at 0 after every iteration")
+    ap.add_argument("--out", default=None, help="write the volume here as .npy")
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    with open(args.scan, "rb") as handle:
+        data = pickle.load(handle)
+    geo = ConeGeometry(data)
+    proj = torch.tensor(np.ascontiguousarray(data["train"]["projections"], dtype=np.float32), device=args.device)
+    angles = np.asarray(data["train"]["angles"], dtype=np.float64)
+    image = np.asarray(data["image"], dtype=np.float32)
+    torch.cuda.synchronize()
+    start = time.perf_counter()
+    x, norms = sirt(proj, geo, angles, n_iter=args.iters, relax=args.relax, nonneg=not args.no_nonneg)
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - start
+    res = {"scan": os.path.basename(args.scan), "iters": args.iters, "relax": args.relax, "nonneg": not args.no_nonneg,
+           "views": int(proj.shape[0]), "detector": [int(proj.shape[2]), int(proj.shape[1])], "volume": [int(v) for v in x.shape],
+           "psnr_3d": float(get_psnr_3d(x.cpu().numpy(), image)),
+           "ssim_3d": float(metrics.ssim_3d(x, torch.tensor(image, device=args.device))),
+           "residual_first": norms[0] if norms else None, "residual_last": norms[-1] if norms else None,
+           "seconds": round(seconds, 3)}
+    if args.out:
+        np.save(args.out, x.cpu().numpy())
+    print(json.dumps(res), flush=True)
+    return res
+
+
+if __name__ == "__main__":
+    main()
