@@ -510,6 +510,33 @@ size_t naf_resize_volume_workspace_bytes(const uint32_t *in_dims, const uint32_t
 int naf_resize_volume(const float *in, const uint32_t *in_dims, float scale, float shift, float *out, const uint32_t *out_dims,
                       float *minmax, void *workspace, size_t workspace_bytes, void *stream);
 
+/* V2  3-D total variation of a volume, its gradient, and normalised steepest descent on it: the regulariser of the ASD-POCS
+ * baseline (TIGRE's minimizeTV, which the reference's baselines used).  DESIGN.md section 14.
+ *   f  f32 [n1, n2, n3] C-contiguous, every extent >= 1;  eps > 0 and finite (TIGRE's value is 1e-8)
+ *   D_a f[v] = f[v] - f[v - e_a] if v_a > 0, else 0                  (a = 0, 1, 2: backward differences)
+ *   m[v]     = sqrt(eps + (D_0 f[v])^2 + (D_1 f[v])^2 + (D_2 f[v])^2)
+ *   TV(f)    = sum_v m[v]
+ *   g[v]     = dTV/df[v] = (D_0 + D_1 + D_2) f[v] / m[v]  -  sum_a [v_a < n_a - 1] D_a f[v + e_a] / m[v + e_a]
+ * g is the exact gradient of TV as written: there is no separate boundary rule, an axis of extent 1 contributes nothing, g of a
+ * (1, 1, 1) volume is 0, and |g[v]| <= sqrt(3) + 3.  All per-voxel arithmetic is fp32, one IEEE operation at a time in the order
+ * of csrc/tv_device.h (squares added in axis order, the three neighbour terms subtracted in axis order, true divisions).
+ *   stats    DEVICE f64 [2]: stats[0] = TV(f) = sum of (double)m[v], stats[1] = sum of (double)g[v]^2.  Per-workgroup partial sums
+ *            go to `workspace` and are added in a fixed order (no atomics): two calls on the same input return the same bits
+ * naf_tv_gradient writes g to `grad` (f32 [n1, n2, n3], not x itself) and the two sums of x to `stats`.
+ * naf_tv_descent runs n_steps times  f <- f - s g(f),  s = step / fp32(sqrt(sum g(f)^2))  (s = 0 when that sum is not > 0: a volume
+ * whose gradient vanishes stays as it is, nothing becomes NaN), each step as f[v] - s * g[v] in fp32.  The steps alternate between
+ * `x` and `scratch` (f32 [n1, n2, n3], not x itself; contents lost); the result ends in `x` whatever the parity of n_steps (an
+ * odd count starts from a device copy of x in scratch).  `stats` receives the two sums of the volume BEFORE THE LAST STEP.
+ * n_steps = 0 returns NAF_OK and touches nothing.  step must be finite and >= 0.
+ * `workspace`: naf_tv_workspace_bytes(n1, n2, n3) bytes (0 for a zero extent), 8-byte aligned.  No full-size intermediate (a descent
+ * step reads the volume twice and writes it once), no allocation and no host synchronisation inside the calls.  All volume offsets
+ * are 64-bit. */
+size_t naf_tv_workspace_bytes(uint32_t n1, uint32_t n2, uint32_t n3);
+int naf_tv_gradient(const float *x, uint32_t n1, uint32_t n2, uint32_t n3, float eps, float *grad, double *stats, void *workspace,
+                    size_t workspace_bytes, void *stream);
+int naf_tv_descent(float *x, float *scratch, uint32_t n1, uint32_t n2, uint32_t n3, float step, uint32_t n_steps, float eps,
+                   double *stats, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,9 @@ SIGNATURES = {
     "naf_resize_volume_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_uint32 * 3)]),
     "naf_resize_volume": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), _f32, _f32, _vp, ctypes.POINTER(ctypes.c_uint32 * 3), _vp,
                                  _vp, ctypes.c_size_t, _vp]),
+    "naf_tv_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32]),
+    "naf_tv_gradient": (_i32, [_vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "naf_tv_descent": (_i32, [_vp, _vp, _u32, _u32, _u32, _f32, _u32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 

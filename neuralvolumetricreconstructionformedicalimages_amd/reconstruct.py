@@ -1,6 +1,6 @@
 """Classical iterative reconstruction from the same projections, voxel grid and metrics a NAF is trained and scored on: SIRT
-over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`).  It is the baseline
-the reference took from TIGRE's iterative algorithms, which have no ROCm build.  DESIGN.md section 13.
+and ASD-POCS over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`).  They
+are the baselines the reference took from TIGRE's iterative algorithms, which have no ROCm build.  DESIGN.md sections 13 and 14.
 
 SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the element-wise product):
 
@@ -12,8 +12,19 @@ SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the 
 R-weighted residual ||b - A x_k||_R = sqrt(sum_r R_r (b - A x_k)_r^2) does not increase from one iteration to the next.  The solver
 returns the volume and the list of these norms, one per iteration, each taken before that iteration's update.
 
-The solver is plain array code over two callables and runs on whatever arrays they take (torch tensors on any device, numpy
-arrays); only the two operators bound by `sirt` are HIP kernels.
+ASD-POCS (Sidky and Pan 2008, as TIGRE runs it, with one SIRT update as the data step and no early stop) follows every data step
+with `tv_steps` normalised steepest-descent steps on the volume's total variation (`tv.tv_descent`, include/naf_hip.h V2):
+
+    beta = relax.  For k in range(n_iter):
+        x_prev = x;  x <- x + beta * C ⊙ A^T (R ⊙ (b - A x));  x <- max(x, 0) if `nonneg`;  beta *= relax_red
+        dp = ||x - x_prev||_2;  dd = ||A x - b||_2
+        if k == 0: dtvg = alpha * dp
+        x_data = x;  x <- tv_descent(x, dtvg, tv_steps)          (tv_steps steps of length dtvg each)
+        dg = ||x - x_data||_2
+        if dg > rmax * dp and dd > 0: dtvg *= alpha_red
+
+The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
+arrays); only the operators bound by `sirt` and `asd_pocs` are HIP kernels.
 """
 from __future__ import annotations
 
@@ -28,6 +39,20 @@ def _namespace(a):
     return np, np.clip
 
 
+def _weights_and_start(A, AT, b, x0, xp):
+    """R = 1 / (A 1), C = 1 / (A^T 1) (0 where the sum is not > 0) and the start volume: zeros, or a copy of `x0`."""
+    col = AT(xp.ones_like(b))                                   # A^T 1, which also gives the volume's shape
+    row = A(xp.ones_like(col))                                  # A 1
+    R = xp.where(row > 0, 1.0 / xp.where(row > 0, row, xp.ones_like(row)), xp.zeros_like(row))
+    C = xp.where(col > 0, 1.0 / xp.where(col > 0, col, xp.ones_like(col)), xp.zeros_like(col))
+    x = xp.zeros_like(col) if x0 is None else x0 + xp.zeros_like(col)      # a copy: the caller's x0 stays as it is
+    return R, C, x
+
+
+def _norm(d, xp):
+    return math.sqrt(float((d * d).sum(dtype=xp.float64)))
+
+
 def sirt_operators(A, AT, b, n_iter, relax=1.0, nonneg=True, x0=None, callback=None):
     """SIRT over a forward operator `A` (volume -> projections) and its transpose `AT` (projections -> volume), both callables
     on arrays of `b`'s kind.  `x0` is the start (default zeros of the volume's shape), `callback(k, x, residual_norm)` runs after
@@ -39,11 +64,7 @@ def sirt_operators(A, AT, b, n_iter, relax=1.0, nonneg=True, x0=None, callback=N
     if n_iter < 0:
         raise ValueError(f"sirt: n_iter must be >= 0, got {n_iter}")
     xp, clamp = _namespace(b)
-    col = AT(xp.ones_like(b))                                   # A^T 1, which also gives the volume's shape
-    row = A(xp.ones_like(col))                                  # A 1
-    R = xp.where(row > 0, 1.0 / xp.where(row > 0, row, xp.ones_like(row)), xp.zeros_like(row))
-    C = xp.where(col > 0, 1.0 / xp.where(col > 0, col, xp.ones_like(col)), xp.zeros_like(col))
-    x = xp.zeros_like(col) if x0 is None else x0 + xp.zeros_like(col)      # a copy: the caller's x0 stays as it is
+    R, C, x = _weights_and_start(A, AT, b, x0, xp)
     norms = []
     for k in range(n_iter):
         r = b - A(x)
@@ -68,3 +89,71 @@ def sirt(projections, geo, angles, n_iter=50, relax=1.0, nonneg=True, x0=None, c
         return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call)
 
     return sirt_operators(A, AT, projections, n_iter, relax=relax, nonneg=nonneg, x0=x0, callback=callback)
+
+
+def asd_pocs_operators(A, AT, b, n_iter, tv_descent, relax=1.0, relax_red=0.99, alpha=0.002, alpha_red=0.95, rmax=0.95, tv_steps=20,
+                       nonneg=True, x0=None, callback=None):
+    """ASD-POCS over `A`, `AT` (as in `sirt_operators`) and `tv_descent(x, step, n_steps)`, a callable that returns the volume after
+    `n_steps` normalised TV descent steps of length `step` (a Python float) and leaves its argument as it is.  See the module
+    docstring for the iteration.  `callback(k, x, entry)` runs after every iteration.  Returns (x, history): one dict per iteration
+    with `residual` (dd), `dp`, `dg` and the `dtvg` and `beta` that iteration used."""
+    relax, relax_red, alpha, alpha_red, rmax = float(relax), float(relax_red), float(alpha), float(alpha_red), float(rmax)
+    for name, value in (("relax", relax), ("relax_red", relax_red), ("alpha_red", alpha_red), ("rmax", rmax)):
+        if not (0.0 < value <= 1.0):
+            raise ValueError(f"asd_pocs: {name} must be in (0, 1], got {value}")
+    if not (alpha > 0.0) or not math.isfinite(alpha):
+        raise ValueError(f"asd_pocs: alpha must be > 0 and finite, got {alpha}")
+    tv_steps, n_iter = int(tv_steps), int(n_iter)
+    if tv_steps < 0:
+        raise ValueError(f"asd_pocs: tv_steps must be >= 0, got {tv_steps}")
+    if n_iter < 0:
+        raise ValueError(f"asd_pocs: n_iter must be >= 0, got {n_iter}")
+    xp, clamp = _namespace(b)
+    R, C, x = _weights_and_start(A, AT, b, x0, xp)
+    beta, dtvg, history = relax, 0.0, []
+    for k in range(n_iter):
+        x_prev = x
+        x = x + beta * (C * AT(R * (b - A(x))))
+        if nonneg:
+            x = clamp(x, 0, None)
+        dp, dd = _norm(x - x_prev, xp), _norm(A(x) - b, xp)
+        if k == 0:
+            dtvg = alpha * dp
+        entry = {"residual": dd, "dp": dp, "dg": 0.0, "dtvg": dtvg, "beta": beta}
+        beta *= relax_red
+        if tv_steps > 0:
+            x_data = x
+            x = tv_descent(x, dtvg, tv_steps)
+            entry["dg"] = _norm(x - x_data, xp)
+        if entry["dg"] > rmax * dp and dd > 0:
+            dtvg *= alpha_red
+        history.append(entry)
+        if callback is not None:
+            callback(k, x, entry)
+    return x, history
+
+
+def asd_pocs(projections, geo, angles, n_iter=50, relax=1.0, relax_red=0.99, alpha=0.002, alpha_red=0.95, rmax=0.95, tv_steps=20,
+             tv_eps=1e-8, nonneg=True, x0=None, callback=None, views_per_call=None):
+    """ASD-POCS reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
+    (float32 volume of geo.nVoxel on the projections' device, history).  The data step is `sirt`'s update, the TV step
+    `tv.tv_descent` with `tv_eps`; see the module docstring and `asd_pocs_operators`."""
+    from . import projector, tv
+
+    def A(x):
+        return projector.project_scan(x, geo, angles, views_per_call=views_per_call)
+
+    def AT(y):
+        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call)
+
+    scratch = []
+
+    def descend(x, step, n_steps):
+        if not scratch:
+            scratch.append(x.new_empty(x.shape))
+        out = x.clone()
+        tv.tv_descent(out, step, n_steps, eps=tv_eps, scratch=scratch[0])
+        return out
+
+    return asd_pocs_operators(A, AT, projections, n_iter, descend, relax=relax, relax_red=relax_red, alpha=alpha, alpha_red=alpha_red,
+                              rmax=rmax, tv_steps=tv_steps, nonneg=nonneg, x0=x0, callback=callback)
