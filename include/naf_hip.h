@@ -474,6 +474,24 @@ int naf_backproject_scan(const float *projections, const uint32_t *dims, const f
                          uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD,
                          float near, float far, int parallel, float step, float *volume, void *stream);
 
+/* P3  detector-row filter: every row of a stack of projections convolved with one symmetric tap array, the ramp filter of the FDK
+ * baseline (reconstruct.fdk).
+ *   in, out     f32 [n_views, H, W], C-contiguous; W = detector pixels along u, the axis perpendicular to the rotation axis
+ *   taps        f32 [W]: taps[m] multiplies the input m pixels away, to either side
+ *   pre, post   f32 [H, W] or NULL: weights applied to the input before the sum and to the sum after it (FDK's cosine weights)
+ *   view_scale  f32 [n_views] or NULL: one factor per view (FDK's angular weight and constants)
+ *   out[i, r, n] = view_scale[i] * (post[r, n] * sum_{k = 0 .. W - 1} taps[|n - k|] * (pre[r, k] * in[i, r, k]))
+ * a linear convolution: the row is zero outside 0 .. W - 1.  All arithmetic is fp32: x_k = pre * in is one multiply, the sum starts
+ * from +0 and takes one fused multiply-add per k in ascending k, acc <- fma(taps[|n - k|], x_k, acc), then one multiply by post and
+ * one by view_scale; a NULL factor is skipped.  No atomics: two calls on the same inputs return the same bits.
+ * `out` may be exactly `in` (a workgroup stages its whole row before it stores); any other overlap is the caller's error.
+ * The row and its taps are staged in LDS, so W is limited: W == 0 or W > NAF_FILTER_MAX_WIDTH returns NAF_ERR_INVALID_ARGUMENT and
+ * launches nothing, whatever the other arguments.  Otherwise n_views * H == 0 returns NAF_OK without examining the pointers.
+ * All offsets are 64-bit.  The cost is W^2 FMAs per row (the dense form; no FFT). */
+#define NAF_FILTER_MAX_WIDTH 16384u
+int naf_filter_rows(const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre, const float *post,
+                    const float *view_scale, float *out, void *stream);
+
 /* M1  3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
  * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
  * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.

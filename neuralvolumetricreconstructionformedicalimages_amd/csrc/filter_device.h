@@ -1,0 +1,43 @@
+// filter_device.h -- the per-output arithmetic of the detector-row filter (include/naf_hip.h P3).
+// It includes nothing of HIP, so a host compiler reads it too: tools/filter_host_check.cpp runs these very functions on the CPU
+// under AddressSanitizer / UBSan and compares them with the float64 convolution of the tests.  Every operation is a single IEEE
+// fp32 multiply or fused multiply-add in the order written; the fma is asked for by name, since the library and the host check are
+// built with -ffp-contract=off and the compiler forms none on its own.
+#pragma once
+
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define NAF_FILTER_HD __host__ __device__ __forceinline__
+#else
+#define NAF_FILTER_HD inline
+#endif
+
+namespace naf {
+
+// x[k] = pre[r, k] * in[i, r, k]: the value the sum reads (staged once per row by the kernel).
+NAF_FILTER_HD float filter_weigh(float v, float w) { return w * v; }
+
+// The tap that output n applies to input k: taps[|n - k|].
+NAF_FILTER_HD uint32_t filter_tap_index(uint32_t n, uint32_t k) { return n >= k ? n - k : k - n; }
+
+// One link of the chain: acc <- fma(tap, x, acc).
+NAF_FILTER_HD float filter_step(float acc, float tap, float x) { return __builtin_fmaf(tap, x, acc); }
+
+// out = view_scale * (post * acc); an absent factor is skipped, not replaced by 1.
+NAF_FILTER_HD float filter_finish(float acc, bool has_post, float post, bool has_scale, float scale) {
+    float v = acc;
+    if (has_post) v = post * v;
+    if (has_scale) v = scale * v;
+    return v;
+}
+
+// sum_{k = 0 .. W - 1} taps[|n - k|] * x[k] as the kernel forms it: from +0, one fma per k, k ascending.  The kernel walks eight
+// outputs per lane through this very chain with the taps in a register window; this loop is the same sequence for one output.
+NAF_FILTER_HD float filter_output(const float *taps, const float *x, uint32_t W, uint32_t n) {
+    float acc = 0.0f;
+    for (uint32_t k = 0; k < W; ++k) acc = filter_step(acc, taps[filter_tap_index(n, k)], x[k]);
+    return acc;
+}
+
+}  // namespace naf

@@ -1,6 +1,7 @@
-"""Classical iterative reconstruction from the same projections, voxel grid and metrics a NAF is trained and scored on: SIRT
-and ASD-POCS over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`).  They
-are the baselines the reference took from TIGRE's iterative algorithms, which have no ROCm build.  DESIGN.md sections 13 and 14.
+"""Classical reconstruction from the same projections, voxel grid and metrics a NAF is trained and scored on: SIRT and ASD-POCS
+over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`), and filtered
+back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that same A^T.  They are the baselines the reference
+took from TIGRE, which has no ROCm build.  DESIGN.md sections 13, 14 and 15.
 
 SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the element-wise product):
 
@@ -23,8 +24,27 @@ with `tv_steps` normalised steepest-descent steps on the volume's total variatio
         dg = ||x - x_data||_2
         if dg > rmax * dp and dd > 0: dtvg *= alpha_red
 
+FDK (Feldkamp, Davis and Kress, in the form of Kak and Slaney ch. 3, the row spacing taken at the isocentre).  Detector pixel
+(u, v), u along the last axis of [N, H, W] (pitch du = dDetector[0], perpendicular to the rotation axis), v along the rows (dv);
+cos(gamma) = DSD / sqrt(DSD^2 + u^2 + v^2);  tau = du * DSO / DSD;  t[m] = tau * h(m tau), the taps of `filter.ramp_taps`:
+
+    q_i[r, n] = sum_k t[|n - k|] * cos(gamma)[r, k] * p_i[r, k]            (linear convolution, zero outside the row)
+    f(x)      = sum_i w_i * (DSO^2 / U_i(x)^2) * q_i(u*(x), v*(x))         (U_i: depth of x from the source along the central ray)
+    w_i       = pi * gap_i / sum_j gap_j                                   (`filter.view_weights`; pi / N for equally spaced views)
+
+For a smooth y the matched transpose deposits y * (len / n) * w_c along every ray; the trilinear weights integrate to the voxel
+volume dV and a ray's share of the cross-section at depth U is U^2 du dv / (DSD^2 cos(gamma)), so in the continuum limit
+(A^T y)(x) = y(u*, v*) * (dV / (du dv)) * (DSD^2 / U^2) / cos(gamma) for a cone beam and y(u*, v*) * dV / (du dv) for a parallel
+one.  The 1 / U^2 of FDK is therefore already in A^T and no second back-projector is needed:
+
+    cone:      x_FDK = A^T y,   y_i = w_i * (DSO^2 / DSD^2) * (du dv / dV) * cos(gamma) * q_i
+    parallel:  x_FDK = A^T y,   y_i = w_i * (du dv / dV) * q_i,   with tau = du and no cosine weights
+
+No short-scan (Parker) weights: a cone scan that covers less than a full turn is reconstructed with a bias.  A tilted
+(laminographic) scan is refused: its constant and filter direction are not verified here.
+
 The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
-arrays); only the operators bound by `sirt` and `asd_pocs` are HIP kernels.
+arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk` are HIP kernels.
 """
 from __future__ import annotations
 
@@ -157,3 +177,57 @@ def asd_pocs(projections, geo, angles, n_iter=50, relax=1.0, relax_red=0.99, alp
 
     return asd_pocs_operators(A, AT, projections, n_iter, descend, relax=relax, relax_red=relax_red, alpha=alpha, alpha_red=alpha_red,
                               rmax=rmax, tv_steps=tv_steps, nonneg=nonneg, x0=x0, callback=callback)
+
+
+def fdk_weights(geo, angles, filter="ram-lak"):
+    """What `filter_rows` needs for an FDK reconstruction of a scan of `geo` at `angles`, as float32 numpy arrays, each formed in
+    float64 and rounded once: (taps [W], pre [H, W] or None, post [H, W] or None, view_scale [N]).  See the module docstring."""
+    from . import filter as F
+    import numpy as np
+    if geo.mode not in ("cone", "parallel"):
+        raise ValueError(f"fdk: mode must be 'cone' or 'parallel', got {geo.mode!r}")
+    if float(geo.tilt_angle) != 0.0:
+        raise ValueError(f"fdk: a tilted (laminographic) scan is not supported, got tilt_angle {geo.tilt_angle}: its constant and "
+                         "filter direction are not verified")
+    W = int(geo.nDetector[0])
+    du, dv = float(geo.dDetector[0]), float(geo.dDetector[1])
+    dV = float(np.prod(np.asarray(geo.dVoxel, dtype=np.float64)))
+    w = F.view_weights(angles) * (du * dv / dV)
+    if geo.mode == "parallel":
+        return F.ramp_taps(W, du, filter), None, None, w.astype(np.float32)
+    DSO, DSD = float(geo.DSO), float(geo.DSD)
+    cos = F.cosine_weights(geo).astype(np.float32)
+    return F.ramp_taps(W, du * DSO / DSD, filter), cos, cos, (w * (DSO / DSD) ** 2).astype(np.float32)
+
+
+def fdk_operators(AT, filter_rows, b, geo, angles, filter="ram-lak", nonneg=False):
+    """FDK over the transpose `AT` (projections -> volume, as in `sirt_operators`) and a row filter
+    `filter_rows(b, taps, pre, post, view_scale)` that takes the float32 numpy arrays of `fdk_weights` and returns the filtered
+    projections as an array of `b`'s kind.  Returns AT(filter_rows(b, ...)), clamped at 0 if `nonneg`."""
+    if len(b.shape) != 3 or int(b.shape[0]) != len(angles):
+        raise ValueError(f"fdk: projections must be [N, H, W] with one view per angle, got {tuple(b.shape)} for {len(angles)} angles")
+    taps, pre, post, view_scale = fdk_weights(geo, angles, filter)
+    x = AT(filter_rows(b, taps, pre, post, view_scale))
+    if nonneg:
+        x = _namespace(b)[1](x, 0, None)
+    return x
+
+
+def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call=None):
+    """FDK reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry, cone or untilted parallel
+    beam) at `angles` -> float32 volume of geo.nVoxel on the projections' device.  One pass of `filter.filter_rows` and one of
+    `projector.backproject_scan`; see the module docstring."""
+    import torch
+
+    from . import filter as F, projector
+
+    def on_device(a):
+        return None if a is None else torch.tensor(a, device=projections.device)
+
+    def rows(b, taps, pre, post, view_scale):
+        return F.filter_rows(b, on_device(taps), on_device(pre), on_device(post), on_device(view_scale))
+
+    def AT(y):
+        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call)
+
+    return fdk_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=nonneg)

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Row-filter benchmark: naf_filter_rows with FDK's weights at the chest shape (50 views of 512 x 512) and at a foot-sized detector
+(`--views` views of 2048 x 2048, default 16: the time is linear in the views and a full 720-view scan is 12 GB), next to the same
+sum as one fp32 torch matmul with the dense Toeplitz matrix, and next to the back-projection that follows it in reconstruct.fdk
+(chest shape only).
+
+    python tools/filter_bench.py
+    python tools/filter_bench.py --shape foot --views 64
+
+Reported per shape, one JSON line: device-event time of one call (median, minimum and maximum of `--windows` windows of `--iters`
+calls after warm-up, the method of tools/backproject_bench.py), the W^2 FMAs per row it performs and the rate that gives, the
+matmul's time, and the largest difference between the two results relative to the largest output.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+SHAPES = {"chest": (50, 512, 512, 256), "foot": (None, 2048, 2048, None)}      # views, H, W, voxels of the volume behind it
+
+
+def run(shape, views, warmup, iters, windows):
+    from backproject_bench import _time
+    from neuralvolumetricreconstructionformedicalimages_amd import phantom, projector
+    from neuralvolumetricreconstructionformedicalimages_amd.filter import filter_rows
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import fdk_weights
+    N, H, W, nv = SHAPES[shape]
+    N = N or views
+    data = phantom.scan_geometry(256)
+    data.update(nDetector=[W, H], dDetector=[0.8 * 512 / W] * 2)
+    geo = ConeGeometry(data)
+    angles = np.linspace(0, np.pi, N + 1)[:-1]
+    taps, pre, post, scale = (torch.tensor(a, device="cuda") for a in fdk_weights(geo, angles))
+    x = torch.rand(N, H, W, device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
+    out = torch.empty_like(x)
+    mine = _time(lambda: filter_rows(x, taps, pre, post, scale, out=out), warmup, iters, windows)
+    n = torch.arange(W, device="cuda")
+    T = taps[(n[:, None] - n[None, :]).abs()]                   # T[n, k] = taps[|n - k|]
+    prev = torch.backends.cuda.matmul.allow_tf32
+    torch.backends.cuda.matmul.allow_tf32 = False
+
+    def dense():
+        return scale[:, None, None] * (post * torch.matmul(pre * x, T.t()))
+    theirs = _time(dense, warmup, iters, windows)
+    diff = float((dense() - out).abs().max() / out.abs().max())
+    torch.backends.cuda.matmul.allow_tf32 = prev
+    fmas = N * H * W * W
+    res = {"shape": shape, "views": N, "detector": [W, H], "filter_ms": round(mine[0], 4),
+           "filter_ms_min_max": [round(mine[1], 4), round(mine[2], 4)], "fma": fmas, "tera_fma_per_s": fmas / mine[0] * 1e-9,
+           "torch_matmul_ms": round(theirs[0], 4), "torch_matmul_ms_min_max": [round(theirs[1], 4), round(theirs[2], 4)],
+           "max_difference_from_matmul": diff}
+    if nv:
+        acc = torch.zeros(nv, nv, nv, device="cuda")
+        bwd = _time(lambda: projector.backproject_scan(out, geo, angles, out=acc), warmup, iters, windows)
+        res.update(backproject_ms=round(bwd[0], 4), filter_share_of_fdk=mine[0] / (mine[0] + bwd[0]))
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", choices=["chest", "foot", "all"], default="all")
+    ap.add_argument("--views", type=int, default=16, help="views of the foot shape")
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--iters", type=int, default=2)
+    ap.add_argument("--windows", type=int, default=3)
+    args = ap.parse_args()
+    for shape in (["chest", "foot"] if args.shape == "all" else [args.shape]):
+        print(json.dumps(run(shape, args.views, args.warmup, args.iters, args.windows)), flush=True)
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -5,6 +5,7 @@ volume like tools/reconstruct_sirt.py does, whose loading and scoring code this 
 
     python tools/reconstruct_asd_pocs.py --scan data/chest_50.pickle --iters 100
     python tools/reconstruct_asd_pocs.py --scan data/chest_50.pickle --iters 100 --alpha 0.004 --tv-steps 10 --out pocs_chest.npy
+    python tools/reconstruct_asd_pocs.py --scan data/chest_50.pickle --iters 20 --init fdk   # start from the FDK volume clamped at 0
 
 Prints one JSON line: psnr_3d, ssim_3d, the first and last residual ||A x - b||_2, the last TV step length and the time.
 """
@@ -30,7 +31,7 @@ def main(argv=None):
     def solve(args, proj, geo, angles):
         x, history = asd_pocs(proj, geo, angles, n_iter=args.iters, relax=args.relax, relax_red=args.relax_red, alpha=args.alpha,
                               alpha_red=args.alpha_red, rmax=args.rmax, tv_steps=args.tv_steps, tv_eps=args.tv_eps,
-                              nonneg=not args.no_nonneg)
+                              nonneg=not args.no_nonneg, x0=reconstruct_sirt.start_volume(args, proj, geo, angles))
         extra = {"relax_red": args.relax_red, "alpha": args.alpha, "alpha_red": args.alpha_red, "rmax": args.rmax,
                  "tv_steps": args.tv_steps, "tv_eps": args.tv_eps, "dtvg_last": history[-1]["dtvg"] if history else None}
         return x, [e["residual"] for e in history], extra

@@ -5,6 +5,7 @@ pickle's `image` with the metrics of train.py's evaluation.
 
     python tools/reconstruct_sirt.py --scan data/chest_50.pickle --iters 100
     python tools/reconstruct_sirt.py --scan data/chest_50.pickle --iters 100 --relax 0.8 --out sirt_chest.npy
+    python tools/reconstruct_sirt.py --scan data/chest_50.pickle --iters 20 --init fdk       # start from the FDK volume clamped at 0
 
 Prints one JSON line: psnr_3d (utils.get_psnr_3d), ssim_3d (metrics.ssim_3d), the first and last weighted residual and the time.
 """
@@ -21,23 +22,36 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def start_volume(args, proj, geo, angles):
+    """The `x0` of an iterative solver for `--init`: None (zeros), or the FDK volume (reconstruct.fdk, ram-lak) clamped at 0."""
+    if args.init == "zeros":
+        return None
+    from neuralvolumetricreconstructionformedicalimages_amd import fdk
+    return fdk(proj, geo, angles, nonneg=True)
+
+
 def _sirt(args, proj, geo, angles):
     from neuralvolumetricreconstructionformedicalimages_amd import sirt
-    x, norms = sirt(proj, geo, angles, n_iter=args.iters, relax=args.relax, nonneg=not args.no_nonneg)
+    x, norms = sirt(proj, geo, angles, n_iter=args.iters, relax=args.relax, nonneg=not args.no_nonneg,
+                    x0=start_volume(args, proj, geo, angles))
     return x, norms, {}
 
 
-def main(argv=None, solve=_sirt, add_arguments=None, description=None):
+def main(argv=None, solve=_sirt, add_arguments=None, description=None, iterative=True):
     """`solve(args, proj, geo, angles) -> (volume, residuals, extra result fields)` and `add_arguments(parser)` let another
-    baseline (tools/reconstruct_asd_pocs.py) run behind the same loading, timing and scoring."""
+    baseline (tools/reconstruct_asd_pocs.py, tools/reconstruct_fdk.py) run behind the same loading, timing and scoring; a baseline
+    that is not `iterative` has no --iters, --relax, --no-nonneg and --init."""
     from neuralvolumetricreconstructionformedicalimages_amd import metrics
     from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
     from neuralvolumetricreconstructionformedicalimages_amd.utils import get_psnr_3d
     ap = argparse.ArgumentParser(description=description, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scan", required=True, help="pickle with the reference's schema (tools/make_synthetic_scan.py, make_scan_from_volume.py)")
-    ap.add_argument("--iters", type=int, required=True)
-    ap.add_argument("--relax", type=float, default=1.0)
-    ap.add_argument("--no-nonneg", action="store_true", help="do not clamp the volume at 0 after every iteration")
+    if iterative:
+        ap.add_argument("--iters", type=int, required=True)
+        ap.add_argument("--relax", type=float, default=1.0)
+        ap.add_argument("--no-nonneg", action="store_true", help="do not clamp the volume at 0 after every iteration")
+        ap.add_argument("--init", choices=["zeros", "fdk"], default="zeros",
+                        help="start volume: zeros, or the FDK reconstruction of the same projections clamped at 0 (inside the timing)")
     ap.add_argument("--out", default=None, help="write the volume here as .npy")
     ap.add_argument("--device", default="cuda")
     if add_arguments is not None:
@@ -54,7 +68,8 @@ def main(argv=None, solve=_sirt, add_arguments=None, description=None):
     x, norms, extra = solve(args, proj, geo, angles)
     torch.cuda.synchronize()
     seconds = time.perf_counter() - start
-    res = {"scan": os.path.basename(args.scan), "iters": args.iters, "relax": args.relax, "nonneg": not args.no_nonneg,
+    head = {"iters": args.iters, "relax": args.relax, "nonneg": not args.no_nonneg, "init": args.init} if iterative else {}
+    res = {"scan": os.path.basename(args.scan), **head,
            "views": int(proj.shape[0]), "detector": [int(proj.shape[2]), int(proj.shape[1])], "volume": [int(v) for v in x.shape],
            "psnr_3d": float(get_psnr_3d(x.cpu().numpy(), image)),
            "ssim_3d": float(metrics.ssim_3d(x, torch.tensor(image, device=args.device))),
