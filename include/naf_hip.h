@@ -492,6 +492,43 @@ int naf_backproject_scan(const float *projections, const uint32_t *dims, const f
 int naf_filter_rows(const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre, const float *post,
                     const float *view_scale, float *out, void *stream);
 
+/* P4  the subset step of OS-SART (reconstruct.os_sart): for a list s of views of a scan,
+ *   x <- x + relax * C_s (.) A_s^T (R_s (.) (b_s - A_s x)),  R = 1 / (A 1),  C_s = 1 / (A_s^T 1),  then x <- max(x, 0)
+ * as three launches, with A and A^T those of P1 and P2 restricted to the list.  All arithmetic is fp32, all offsets are 64-bit.
+ *   view_index   DEVICE u32 [n_sub], or NULL for the identity (then n_sub <= n_scan_views).  Launch view j is scan view
+ *                v = view_index[j]; the caller keeps every entry < n_scan_views (an entry that is not gives NaN in y and r and
+ *                adds nothing in the transpose; nothing is read or written through it)
+ *   poses        f32 [n_scan_views, 12] and  projections  f32 [n_scan_views, det_h, det_w]: the WHOLE scan, read in place
+ *   y, r         f32 [n_sub, det_h, det_w], indexed by launch view
+ *   the other geometry arguments are naf_project_scan's / naf_backproject_scan's
+ * naf_sart_residual_scan: pixel (j, row, col) takes the ray naf_generate_rays makes for (v, row, col), P1's own t0, t1, len, n, sample
+ *   positions and trilinear cell, and sums A x exactly as P1 does (same operations in the same order), then writes
+ *     r = b - A x  (r may be NULL)  and  y = r / len,  b = projections[v, row, col], len = (t1 - t0) * |d| as P1 holds it in fp32
+ *   an empty segment gives r = b and y = 0; a NaN / infinite ray, for which P1 returns NaN, gives NaN in both.  Clamp-to-edge makes
+ *   the eight weights of every sample sum to 1, so the row sum (A 1)_r is n * (len / n) = len up to rounding: y is R (.) (b - A x)
+ *   and no stored A 1 is needed.  No atomics: two calls return the same bits.  `projections` is only read.
+ * naf_sart_backproject_scan: the transpose over the same list.  Sample k of the ray of pixel (j, row, col) adds
+ *   y[j, row, col] * (len / n) * w_c to num and, where den is not NULL, (len / n) * w_c to den, for each of its eight corners c.
+ *   num, den  f32 [n1, n2, n3], two different volumes, ACCUMULATED INTO.  P2's merge of consecutive samples that share a cell: one
+ *   set of eight register sums serves both outputs; terms that are exactly 0 are not sent; fp32 hardware atomics, so the sums are
+ *   exact up to rounding and summation order, as in P2.
+ * naf_sart_update: for each of the n elements of x, num and den (4-byte aligned, no overlap)
+ *     c = den_is_reciprocal ? den : (den > 0 ? 1.0f / den : 0.0f)
+ *     x = x + relax * (c * num);  if nonneg: x = x < 0 ? 0 : x  (a NaN stays);  num = 0;  if zero_den: den = 0
+ *   one IEEE operation at a time.  den_is_reciprocal = 1 takes `den` as a stored C_s and only reads it (zero_den must then be 0).
+ *   No reduction and no atomics: two calls on the same inputs return the same bits, whatever the alignment of the three pointers.
+ * Empty calls (n_sub == 0, n == 0) return NAF_OK without examining the pointers. */
+int naf_sart_residual_scan(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub,
+                           uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
+                           int parallel, float step, const uint32_t *view_index, uint32_t n_scan_views, const float *projections,
+                           float *y, float *r, void *stream);
+int naf_sart_backproject_scan(const float *y, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views, const uint32_t *dims,
+                              const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h, float du, float dv, float ou,
+                              float ov, float DSD, float near, float far, int parallel, float step, float *num, float *den,
+                              void *stream);
+int naf_sart_update(float *x, float *num, float *den, uint64_t n, float relax, int nonneg, int den_is_reciprocal, int zero_den,
+                    void *stream);
+
 /* M1  3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
  * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
  * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.

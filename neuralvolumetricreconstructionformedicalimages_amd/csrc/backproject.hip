@@ -6,55 +6,14 @@
 // Layout: the forward's.  One lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave, so the 64 lanes of a wave at
 // equal k add into a small neighbourhood of the volume.  The sample spacing is half a voxel, so consecutive samples of a ray often
 // share their cell: the eight corner weights are summed in registers while the cell stays the same and go out as eight fp32 hardware
-// atomics when it changes.  Built with -DNAF_BACKPROJECT_PER_SAMPLE every sample sends its own eight atomics (the A/B of section 13).
+// atomics when it changes (backproject_device.h, shared with sart.hip).  Built with -DNAF_BACKPROJECT_PER_SAMPLE every sample sends
+// its own eight atomics (the A/B of section 13).
+#include "backproject_device.h"
 #include "draw_device.h"
-#include "project_device.h"
 
 namespace naf {
 
 namespace {
-
-// Adds scale * acc[c] to the eight corners of the cell at `q`; corners that got no weight (a constant axis, a sample on a voxel
-// centre) are skipped.  Corner c = 4 cx + 2 cy + cz.
-__device__ __forceinline__ void flush_cell(float *__restrict__ q, const ProjVolume &v, float scale, const float acc[8]) {
-    const uint64_t sx = v.next[0], sy = v.next[1], sz = v.next[2];
-    const uint64_t off[8] = {0, sz, sy, sy + sz, sx, sx + sz, sx + sy, sx + sy + sz};
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const float add = scale * acc[c];
-        if (add != 0.0f) atomicAdd(q + off[c], add);          // no-return global_atomic_add_f32
-    }
-}
-
-// value * (len / n) * w_c into the corners of every sample of the ray.  An empty segment and a NaN / infinite ray add nothing.
-__device__ __forceinline__ void scatter_ray(const ProjVolume &v, float *__restrict__ volume, float4 a, float4 b, float value) {
-    RaySpan s;
-    if (ray_span(v, a, b, s) != kSpanOk) return;
-    const float scale = value * s.weight;
-    constexpr uint64_t kNoCell = ~0ull;
-    uint64_t cell = kNoCell;
-    float acc[8];
-    for (uint32_t k = 0; k < s.n; ++k) {
-        float p[3], w[3];
-        span_point(s, k, p);
-        const uint64_t base = trilinear_cell(v, p[0], p[1], p[2], w);
-#ifdef NAF_BACKPROJECT_PER_SAMPLE
-        const bool moved = true;
-#else
-        const bool moved = base != cell;
-#endif
-        if (moved) {
-            if (cell != kNoCell) flush_cell(volume + cell, v, scale, acc);
-            cell = base;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[c] = 0.0f;
-        }
-        const float x[2] = {1.0f - w[0], w[0]}, y[2] = {1.0f - w[1], w[1]}, z[2] = {1.0f - w[2], w[2]};
-#pragma unroll
-        for (int c = 0; c < 8; ++c) acc[c] += (x[c >> 2] * y[(c >> 1) & 1]) * z[c & 1];
-    }
-    if (cell != kNoCell) flush_cell(volume + cell, v, scale, acc);
-}
 
 __global__ void __launch_bounds__(256)
 backproject_rays_kernel(ProjVolume v, float *__restrict__ volume, const float *__restrict__ values, const float *__restrict__ rays,
@@ -62,7 +21,7 @@ backproject_rays_kernel(ProjVolume v, float *__restrict__ volume, const float *_
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rays) return;
     const float4 *r = reinterpret_cast<const float4 *>(rays + i * 8);
-    scatter_ray(v, volume, r[0], r[1], values[i]);
+    scatter_ray(v, r[0], r[1], DepositValue{volume, values[i]});
 }
 
 // blockIdx.x = projection * tiles_per_projection + tile, as in project_scan_kernel.
@@ -77,7 +36,7 @@ backproject_scan_kernel(ProjVolume v, float *__restrict__ volume, const float *_
     const uint64_t flat = (uint64_t)proj * g.W * g.H + (uint64_t)row * g.W + col;
     float4 r[2];
     make_ray(poses, flat, g, r);
-    scatter_ray(v, volume, r[0], r[1], projections[flat]);
+    scatter_ray(v, r[0], r[1], DepositValue{volume, projections[flat]});
 }
 
 }  // namespace

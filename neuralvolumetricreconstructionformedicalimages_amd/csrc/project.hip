@@ -13,34 +13,14 @@ namespace naf {
 
 namespace {
 
-// Value of the volume at p: trilinear, clamp-to-edge.  Only called for points inside the box (midpoints of the clipped segment).
-__device__ __forceinline__ float sample_volume(const ProjVolume &v, float px, float py, float pz) {
-    float w[3];
-    const float *__restrict__ q = v.data + trilinear_cell(v, px, py, pz, w);
-    const uint64_t sx = v.next[0], sy = v.next[1], sz = v.next[2];
-    const float c000 = q[0], c001 = q[sz], c010 = q[sy], c011 = q[sy + sz];
-    const float c100 = q[sx], c101 = q[sx + sz], c110 = q[sx + sy], c111 = q[sx + sy + sz];
-    const float c00 = c000 + w[2] * (c001 - c000), c01 = c010 + w[2] * (c011 - c010);
-    const float c10 = c100 + w[2] * (c101 - c100), c11 = c110 + w[2] * (c111 - c110);
-    const float c0 = c00 + w[1] * (c01 - c00), c1 = c10 + w[1] * (c11 - c10);
-    return c0 + w[0] * (c1 - c0);
-}
-
-// Midpoint-rule line integral of one ray (o, d, near, far); d is un-normalised.  Segment, sample count and sample positions come
-// from project_device.h, shared with the transpose.
+// Midpoint-rule line integral of one ray (o, d, near, far); d is un-normalised.  Segment, sample count, sample positions and the
+// sum over the samples come from project_device.h, shared with the transpose and the OS-SART residual.
 __device__ __forceinline__ float line_integral(const ProjVolume &v, float4 a, float4 b) {
     RaySpan s;
     const SpanKind kind = ray_span(v, a, b, s);
     if (kind == kSpanEmpty) return 0.0f;
     if (kind == kSpanUnbounded) return __builtin_nanf("");
-    float acc = 0.0f;
-#pragma unroll 4
-    for (uint32_t k = 0; k < s.n; ++k) {                      // position from k, not by increments; fp32 sum in k order
-        float p[3];
-        span_point(s, k, p);
-        acc += sample_volume(v, p[0], p[1], p[2]);
-    }
-    return acc * s.weight;
+    return span_sum(v, s) * s.weight;
 }
 
 __global__ void __launch_bounds__(256)

@@ -1,6 +1,7 @@
 // project_device.h -- the pieces of the projection definition (include/naf_hip.h P1) that the forward
-// projector (project.hip) and its transpose (backproject.hip) must share to the bit: the volume's grid, the clipped segment of a
-// ray with its sample count, the sample positions, and the trilinear cell with its three weights.
+// projector (project.hip), its transpose (backproject.hip) and the OS-SART subset kernels (sart.hip) must share to the bit: the
+// volume's grid, the clipped segment of a ray with its sample count, the sample positions, the trilinear cell with its three
+// weights, and the forward's sum over the samples.
 #pragma once
 
 #include <cmath>
@@ -42,6 +43,7 @@ __device__ __forceinline__ uint64_t trilinear_cell(const ProjVolume &v, float px
 struct RaySpan {
     float p0[3], d[3];               // p0 = o + t0 d
     float seg;                       // (t1 - t0) / n
+    float len;                       // (t1 - t0) * |d|: the length of the segment in metres
     float weight;                    // len / n: what one sample contributes per unit of the volume's value
     uint32_t n;
 };
@@ -69,6 +71,7 @@ __device__ __forceinline__ SpanKind ray_span(const ProjVolume &v, float4 a, floa
     if (!(nf < 16777216.0f)) return kSpanUnbounded;
     s.n = (uint32_t)nf;
     s.seg = (t1 - t0) / nf;
+    s.len = len;
     s.weight = len / nf;
     // Sample k sits at p0 + s_k d with p0 = o + t0 d and s_k = (k + 1/2) seg, each a single-rounding fma: a cone ray's origin is
     // ~1 m from the volume, and o + t d with an fp32 t ~ 1 would place every sample ~6e-8 m (6e-5 of a 1 mm voxel) off its spot.
@@ -85,6 +88,32 @@ __device__ __forceinline__ void span_point(const RaySpan &s, uint32_t k, float p
     const float t = ((float)k + 0.5f) * s.seg;
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[a] = fmaf(t, s.d[a], s.p0[a]);
+}
+
+// Value of the volume at p: trilinear, clamp-to-edge.  Only called for points inside the box (midpoints of the clipped segment).
+__device__ __forceinline__ float sample_volume(const ProjVolume &v, float px, float py, float pz) {
+    float w[3];
+    const float *__restrict__ q = v.data + trilinear_cell(v, px, py, pz, w);
+    const uint64_t sx = v.next[0], sy = v.next[1], sz = v.next[2];
+    const float c000 = q[0], c001 = q[sz], c010 = q[sy], c011 = q[sy + sz];
+    const float c100 = q[sx], c101 = q[sx + sz], c110 = q[sx + sy], c111 = q[sx + sy + sz];
+    const float c00 = c000 + w[2] * (c001 - c000), c01 = c010 + w[2] * (c011 - c010);
+    const float c10 = c100 + w[2] * (c101 - c100), c11 = c110 + w[2] * (c111 - c110);
+    const float c0 = c00 + w[1] * (c01 - c00), c1 = c10 + w[1] * (c11 - c10);
+    return c0 + w[0] * (c1 - c0);
+}
+
+// Sum of the volume's value at the n samples of a span: position from k, not by increments; fp32 sum in k order.  The line
+// integral is this sum times s.weight.
+__device__ __forceinline__ float span_sum(const ProjVolume &v, const RaySpan &s) {
+    float acc = 0.0f;
+#pragma unroll 4
+    for (uint32_t k = 0; k < s.n; ++k) {
+        float p[3];
+        span_point(s, k, p);
+        acc += sample_volume(v, p[0], p[1], p[2]);
+    }
+    return acc;
 }
 
 // Host: argument checks shared by the entry points, and the grid of a [n1, n2, n3] volume with voxel size dvoxel (HOST f32 [3]).

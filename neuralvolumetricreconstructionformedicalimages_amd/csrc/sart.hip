@@ -1,0 +1,219 @@
+// sart.hip -- the three kernels of one OS-SART subset step for gfx950 (include/naf_hip.h P4):
+//   naf_sart_residual_scan     y = (b - A x) / len and r = b - A x for a list of views of a scan, in one forward march
+//   naf_sart_backproject_scan  num += A_s^T y and den += A_s^T 1 for the same list, in one transpose march
+//   naf_sart_update            x += relax * num / den (clamped at 0), num = 0, den = 0, in one pass over the volume
+// The forward half is project.hip's (project_device.h: ray_span, span_point, span_sum), the transpose half backproject.hip's
+// (backproject_device.h: scatter_ray with the paired deposit), so a subset step is A and A^T of P1 / P2 restricted to the list.
+//
+// Layout of the two scan kernels: P1's.  One lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave; launch view j
+// is scan view view_index[j] (j itself without a list), whose pose, pixel rays and measured values are read in place from the whole
+// scan, so no subset is ever gathered.
+#include "backproject_device.h"
+#include "draw_device.h"
+
+namespace naf {
+
+namespace {
+
+struct ViewList {
+    const uint32_t *__restrict__ index;   // device u32 [n_sub], or null: the identity
+    uint32_t n_scan_views;
+};
+
+// Scan view of launch view j, or n_scan_views (no such view) when the list holds an index outside the scan.
+__device__ __forceinline__ uint32_t scan_view(const ViewList &l, uint32_t j) {
+    const uint32_t view = l.index ? l.index[j] : j;
+    return view < l.n_scan_views ? view : l.n_scan_views;
+}
+
+// blockIdx.x = launch view * tiles_per_projection + tile, as in project_scan_kernel.
+__global__ void __launch_bounds__(256)
+sart_residual_scan_kernel(ProjVolume v, const float *__restrict__ poses, RayGeo g, ViewList list,
+                          const float *__restrict__ projections, float *__restrict__ y, float *__restrict__ r, uint32_t tiles_x,
+                          uint32_t tiles_per_proj) {
+    const uint32_t j = blockIdx.x / tiles_per_proj, tile = blockIdx.x - j * tiles_per_proj;
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    uint32_t row, col;
+    tile_pixel(tx, ty, threadIdx.x, row, col);
+    if (row >= g.H || col >= g.W) return;
+    const uint64_t per_view = (uint64_t)g.W * g.H, pixel = (uint64_t)row * g.W + col;
+    const uint64_t out = (uint64_t)j * per_view + pixel;
+    const uint32_t view = scan_view(list, j);
+    const float nan = __builtin_nanf("");
+    float res = nan, weighted = nan;                          // a view outside the scan: nothing is read through it
+    if (view < list.n_scan_views) {
+        const uint64_t flat = (uint64_t)view * per_view + pixel;
+        const float b = projections[flat];
+        float4 ray[2];
+        make_ray(poses, flat, g, ray);
+        RaySpan s;
+        const SpanKind kind = ray_span(v, ray[0], ray[1], s);
+        if (kind == kSpanEmpty) {
+            res = b;
+            weighted = 0.0f;
+        } else if (kind == kSpanOk) {
+            res = b - span_sum(v, s) * s.weight;              // b - (A x): P1's own sum and product
+            weighted = res / s.len;
+        }
+    }
+    y[out] = weighted;
+    if (r) r[out] = res;
+}
+
+__global__ void __launch_bounds__(256)
+sart_backproject_scan_kernel(ProjVolume v, float *__restrict__ num, float *__restrict__ den, const float *__restrict__ y,
+                             const float *__restrict__ poses, RayGeo g, ViewList list, uint32_t tiles_x, uint32_t tiles_per_proj) {
+    const uint32_t j = blockIdx.x / tiles_per_proj, tile = blockIdx.x - j * tiles_per_proj;
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    uint32_t row, col;
+    tile_pixel(tx, ty, threadIdx.x, row, col);
+    if (row >= g.H || col >= g.W) return;
+    const uint32_t view = scan_view(list, j);
+    if (view >= list.n_scan_views) return;
+    const uint64_t per_view = (uint64_t)g.W * g.H, pixel = (uint64_t)row * g.W + col;
+    float4 ray[2];
+    make_ray(poses, (uint64_t)view * per_view + pixel, g, ray);
+    scatter_ray(v, ray[0], ray[1], DepositPair{num, den, y[(uint64_t)j * per_view + pixel]});
+}
+
+struct UpdateArgs {
+    float relax;
+    int nonneg, den_is_reciprocal, zero_den;
+};
+
+__device__ __forceinline__ void update_voxel(float &x, float &num, float &den, const UpdateArgs &a) {
+    float c = den;
+    if (!a.den_is_reciprocal) {
+        c = den > 0.0f ? 1.0f / den : 0.0f;
+        if (a.zero_den) den = 0.0f;
+    }
+    float next = x + a.relax * (c * num);
+    if (a.nonneg) next = next < 0.0f ? 0.0f : next;           // a NaN stays a NaN
+    x = next;
+    num = 0.0f;
+}
+
+// Elements [head, head + 4 n_vec) as float4 (x + head, num + head and den + head are 16-byte aligned), the `head` elements before
+// and the fewer than four after them one by one.  Grid-stride.
+__global__ void __launch_bounds__(256)
+sart_update_kernel(float *__restrict__ x, float *__restrict__ num, float *__restrict__ den, uint64_t n, uint64_t head, uint64_t n_vec,
+                   UpdateArgs a) {
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t)gridDim.x * blockDim.x;
+    float4 *__restrict__ xv = reinterpret_cast<float4 *>(x + head);
+    float4 *__restrict__ nv = reinterpret_cast<float4 *>(num + head);
+    float4 *__restrict__ dv = reinterpret_cast<float4 *>(den + head);
+    const bool store_den = !a.den_is_reciprocal && a.zero_den;
+    for (uint64_t i = tid; i < n_vec; i += stride) {
+        float4 xs = xv[i], ns = nv[i], ds = dv[i];
+        update_voxel(xs.x, ns.x, ds.x, a);
+        update_voxel(xs.y, ns.y, ds.y, a);
+        update_voxel(xs.z, ns.z, ds.z, a);
+        update_voxel(xs.w, ns.w, ds.w, a);
+        xv[i] = xs;
+        nv[i] = ns;
+        if (store_den) dv[i] = ds;
+    }
+    const uint64_t tail = head + 4u * n_vec, n_single = head + (n - tail);
+    for (uint64_t i = tid; i < n_single; i += stride) {
+        const uint64_t e = i < head ? i : tail + (i - head);
+        float xs = x[e], ns = num[e], ds = den[e];
+        update_voxel(xs, ns, ds, a);
+        x[e] = xs;
+        num[e] = ns;
+        if (store_den) den[e] = ds;
+    }
+}
+
+// The checks and the launch grid the two scan kernels share.  `volume` is any of the call's volume pointers (checked for null).
+int scan_launch(const char *who, const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses,
+                const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views, uint32_t det_w, uint32_t det_h, float DSD,
+                int parallel, float step, ProjVolume *v, uint32_t *tiles_x, uint32_t *per_proj) {
+    char msg[160];
+    if (!dims) {
+        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    const int rc = make_volume(who, volume, dims[0], dims[1], dims[2], dvoxel, step, v);
+    if (rc != NAF_OK) return rc;
+    const char *what = nullptr;
+    const uint32_t tx = (det_w + kProjTile - 1u) / kProjTile, ty = (det_h + kProjTile - 1u) / kProjTile;
+    const uint64_t tiles = (uint64_t)tx * ty;
+    if (!poses) what = "null pointer";
+    else if (det_w == 0 || det_h == 0) what = "empty detector";
+    else if (!parallel && !(DSD > 0.0f)) what = "DSD must be > 0 for a cone beam";
+    else if (!view_index && n_sub > n_scan_views) what = "without a view list n_sub must be <= n_scan_views";
+    else if (n_scan_views == 0) what = "a scan of zero views";
+    else if (tiles * n_sub > 0x7fffffffull) what = "too many pixels for one call";
+    if (what) {
+        std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    *tiles_x = tx;
+    *per_proj = (uint32_t)tiles;
+    return NAF_OK;
+}
+
+}  // namespace
+
+}  // namespace naf
+
+using namespace naf;
+
+extern "C" int naf_sart_residual_scan(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub,
+                                      uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near,
+                                      float far, int parallel, float step, const uint32_t *view_index, uint32_t n_scan_views,
+                                      const float *projections, float *y, float *r, void *stream) {
+    if (n_sub == 0) return NAF_OK;
+    ProjVolume v;
+    uint32_t tiles_x, per_proj;
+    const int rc = scan_launch("sart_residual_scan", volume, dims, dvoxel, poses, view_index, n_sub, n_scan_views, det_w, det_h, DSD,
+                               parallel, step, &v, &tiles_x, &per_proj);
+    if (rc != NAF_OK) return rc;
+    if (!projections || !y) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_residual_scan: null pointer");
+    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
+    { ProfScope prof_("sart_residual_scan_kernel", (hipStream_t)stream);
+      hipLaunchKernelGGL(sart_residual_scan_kernel, dim3(per_proj * n_sub), dim3(256), 0, (hipStream_t)stream, v, poses, g,
+                         ViewList{view_index, n_scan_views}, projections, y, r, tiles_x, per_proj); }
+    return check_launch("sart_residual_scan_kernel");
+}
+
+extern "C" int naf_sart_backproject_scan(const float *y, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
+                                         const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h,
+                                         float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel,
+                                         float step, float *num, float *den, void *stream) {
+    if (n_sub == 0) return NAF_OK;
+    ProjVolume v;
+    uint32_t tiles_x, per_proj;
+    const int rc = scan_launch("sart_backproject_scan", num, dims, dvoxel, poses, view_index, n_sub, n_scan_views, det_w, det_h, DSD,
+                               parallel, step, &v, &tiles_x, &per_proj);
+    if (rc != NAF_OK) return rc;
+    if (!y) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_backproject_scan: null pointer");
+    if (den == num) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_backproject_scan: num and den must be two volumes");
+    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
+    { ProfScope prof_("sart_backproject_scan_kernel", (hipStream_t)stream);
+      hipLaunchKernelGGL(sart_backproject_scan_kernel, dim3(per_proj * n_sub), dim3(256), 0, (hipStream_t)stream, v, num, den, y, poses,
+                         g, ViewList{view_index, n_scan_views}, tiles_x, per_proj); }
+    return check_launch("sart_backproject_scan_kernel");
+}
+
+extern "C" int naf_sart_update(float *x, float *num, float *den, uint64_t n, float relax, int nonneg, int den_is_reciprocal,
+                               int zero_den, void *stream) {
+    if (n == 0) return NAF_OK;
+    if (!x || !num || !den) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_update: null pointer");
+    if (!std::isfinite(relax)) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_update: relax must be finite");
+    if (den_is_reciprocal && zero_den)
+        return fail(NAF_ERR_INVALID_ARGUMENT, "sart_update: a reciprocal den is read only, zero_den cannot be set with it");
+    const uintptr_t ax = (uintptr_t)x, an = (uintptr_t)num, ad = (uintptr_t)den;
+    if ((ax | an | ad) & 3u) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_update: pointers must be 4-byte aligned");
+    // The float4 body needs the three arrays to reach a 16-byte boundary after the same number of elements; otherwise every
+    // element goes one by one (head = n).
+    uint64_t head = n;
+    if ((ax & 15u) == (an & 15u) && (ax & 15u) == (ad & 15u)) head = std::min<uint64_t>(n, ((16u - (ax & 15u)) & 15u) / 4u);
+    const uint64_t n_vec = (n - head) / 4u;
+    const uint64_t work = std::max<uint64_t>(n_vec, n - 4u * n_vec);
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((work + 255u) / 256u, 2048u);
+    UpdateArgs a{relax, nonneg != 0, den_is_reciprocal != 0, zero_den != 0};
+    { ProfScope prof_("sart_update_kernel", (hipStream_t)stream);
+      hipLaunchKernelGGL(sart_update_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, num, den, n, head, n_vec, a); }
+    return check_launch("sart_update_kernel");
+}

@@ -1,7 +1,8 @@
 """Classical reconstruction from the same projections, voxel grid and metrics a NAF is trained and scored on: SIRT and ASD-POCS
-over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`), and filtered
-back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that same A^T.  They are the baselines the reference
-took from TIGRE, which has no ROCm build.  DESIGN.md sections 13, 14 and 15.
+over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`), filtered
+back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that same A^T, and OS-SART over the subset kernels of
+`sart` (the same A and A^T restricted to a list of views).  They are the baselines the reference took from TIGRE, which has no
+ROCm build.  DESIGN.md sections 13, 14, 15 and 16.
 
 SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the element-wise product):
 
@@ -12,6 +13,21 @@ SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the 
 `relax` must lie in (0, 1].  A has no negative entry, so the spectral radius of C A^T R A is at most 1, and in that range the
 R-weighted residual ||b - A x_k||_R = sqrt(sum_r R_r (b - A x_k)_r^2) does not increase from one iteration to the next.  The solver
 returns the volume and the list of these norms, one per iteration, each taken before that iteration's update.
+
+OS-SART (ordered subsets: SART when every subset is one view, SIRT when one subset holds every view).  The views are split into
+subsets (`subset_order`); A_s, b_s and R_s are the rows of A, b and R that belong to the views of subset s:
+
+    R = 1 / (A 1) as above;   C_s = 1 / (A_s^T 1)  where A_s^T 1 > 0, else 0      (inverse column sums of the subset's rows)
+    beta = relax.  For k in range(n_iter):
+        for s in the order of `subsets`:   x <- x + beta * C_s ⊙ A_s^T (R_s ⊙ (b_s - A_s x)),   then x <- max(x, 0) if `nonneg`
+        beta *= relax_red
+
+so the volume is corrected once per subset and not once per pass over the data.  The norm reported for iteration k is
+sqrt(sum_s ||b_s - A_s x||_{R_s}^2), each subset's residual taken just before that subset's update: no extra projection is made
+for it, and with one subset it is SIRT's norm.  `os_sart_operators` is the array code; `os_sart` runs the same iteration on three
+HIP kernels (include/naf_hip.h P4), where the row sum of a ray is its length inside the volume (every sample's eight trilinear
+weights sum to 1), so R is never stored, and where each C_s is kept after the subset's first visit if all of them fit
+`weight_cache_bytes`.
 
 ASD-POCS (Sidky and Pan 2008, as TIGRE runs it, with one SIRT update as the data step and no early stop) follows every data step
 with `tv_steps` normalised steepest-descent steps on the volume's total variation (`tv.tv_descent`, include/naf_hip.h V2):
@@ -44,7 +60,7 @@ No short-scan (Parker) weights: a cone scan that covers less than a full turn is
 (laminographic) scan is refused: its constant and filter direction are not verified here.
 
 The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
-arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk` are HIP kernels.
+arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart`, are HIP kernels.
 """
 from __future__ import annotations
 
@@ -109,6 +125,143 @@ def sirt(projections, geo, angles, n_iter=50, relax=1.0, nonneg=True, x0=None, c
         return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call)
 
     return sirt_operators(A, AT, projections, n_iter, relax=relax, nonneg=nonneg, x0=x0, callback=callback)
+
+
+def subset_order(angles, n_subsets, order="angular-distance", seed=0):
+    """Splits the views of a scan into `n_subsets` subsets and orders the subsets -> list of int64 index arrays into `angles`.
+    The views are taken in sorted-angle order and dealt round-robin, so every subset spans the scan.  `order`:
+    "sequential": as dealt;  "random": a permutation drawn once from `seed`;  "angular-distance" (TIGRE's default idea): start at
+    the first subset, then always the subset whose mean angle, as a direction mod pi, is farthest from those already visited
+    (largest distance to the nearest visited one; ties go to the one farthest from the last visited, then to the lowest index)."""
+    import numpy as np
+    angles = np.asarray(angles, dtype=np.float64).reshape(-1)
+    N, n_subsets = len(angles), int(n_subsets)
+    if not (1 <= n_subsets <= N):
+        raise ValueError(f"os_sart: n_subsets must be in [1, {N}] for {N} views, got {n_subsets}")
+    by_angle = np.argsort(angles, kind="stable")
+    subsets = [by_angle[i::n_subsets].astype(np.int64) for i in range(n_subsets)]
+    if order == "sequential":
+        visit = list(range(n_subsets))
+    elif order == "random":
+        visit = [int(i) for i in np.random.default_rng(seed).permutation(n_subsets)]
+    elif order == "angular-distance":
+        mean = np.array([angles[s].mean() for s in subsets])
+
+        def distance(i, j):
+            d = abs(mean[i] - mean[j]) % math.pi
+            return min(d, math.pi - d)
+
+        visit, left, tie = [0], list(range(1, n_subsets)), 1e-9
+        while left:
+            nearest = [min(distance(i, j) for j in visit) for i in left]
+            best = [i for i, d in zip(left, nearest) if d >= max(nearest) - tie]
+            to_last = [distance(i, visit[-1]) for i in best]
+            visit.append(next(i for i, d in zip(best, to_last) if d >= max(to_last) - tie))
+            left.remove(visit[-1])
+    else:
+        raise ValueError(f"os_sart: order must be 'sequential', 'random' or 'angular-distance', got {order!r}")
+    return [subsets[i] for i in visit]
+
+
+def _check_os_sart(relax, relax_red, n_iter):
+    relax, relax_red, n_iter = float(relax), float(relax_red), int(n_iter)
+    for name, value in (("relax", relax), ("relax_red", relax_red)):
+        if not (0.0 < value <= 1.0):
+            raise ValueError(f"os_sart: {name} must be in (0, 1], got {value}")
+    if n_iter < 0:
+        raise ValueError(f"os_sart: n_iter must be >= 0, got {n_iter}")
+    return relax, relax_red, n_iter
+
+
+def _inverse_where_positive(a, xp):
+    return xp.where(a > 0, 1.0 / xp.where(a > 0, a, xp.ones_like(a)), xp.zeros_like(a))
+
+
+def os_sart_operators(A, AT, b, subsets, n_iter, relax=1.0, relax_red=1.0, nonneg=True, x0=None, callback=None):
+    """OS-SART over `A(x, views)` (volume -> the projections [len(views), H, W] of those views) and `AT(y, views)` (projections of
+    those views -> volume), callables on arrays of the kind of `b` [N, H, W]; `views` is a list of ints.  `subsets` is a list of
+    view lists, visited in its order (`subset_order`).  See the module docstring for the iteration.  `callback(k, x,
+    residual_norm)` runs after every iteration.  Returns (x, residual_norms)."""
+    relax, relax_red, n_iter = _check_os_sart(relax, relax_red, n_iter)
+    subsets = [[int(v) for v in s] for s in subsets]
+    N = int(b.shape[0])
+    if not subsets or any(not s for s in subsets) or any(not (0 <= v < N) for s in subsets for v in s):
+        raise ValueError(f"os_sart: subsets must be non-empty lists of view indices in [0, {N}), got {subsets}")
+    xp, clamp = _namespace(b)
+    C = [_inverse_where_positive(AT(xp.ones_like(b[s]), s), xp) for s in subsets]
+    R = _inverse_where_positive(A(xp.ones_like(C[0]), list(range(N))), xp)
+    x = xp.zeros_like(C[0]) if x0 is None else x0 + xp.zeros_like(C[0])       # a copy: the caller's x0 stays as it is
+    beta, norms = relax, []
+    for k in range(n_iter):
+        total = 0.0
+        for s, Cs in zip(subsets, C):
+            Rs = R[s]
+            r = b[s] - A(x, s)
+            total += float((Rs * r * r).sum(dtype=xp.float64))
+            x = x + beta * (Cs * AT(Rs * r, s))
+            if nonneg:
+                x = clamp(x, 0, None)
+        norms.append(math.sqrt(total))
+        beta *= relax_red
+        if callback is not None:
+            callback(k, x, norms[-1])
+    return x, norms
+
+
+def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-distance", relax=1.0, relax_red=1.0, nonneg=True,
+            x0=None, callback=None, weight_cache_bytes=2 << 30, seed=0):
+    """OS-SART reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
+    (float32 volume of geo.nVoxel on the projections' device, residual norms).  `n_subsets=None` is one view per subset (SART);
+    the subsets and their order come from `subset_order(angles, n_subsets, order, seed)`.  The iteration of `os_sart_operators`,
+    run directly on the subset kernels of `sart`: per subset one residual launch, one paired back-projection and one update.
+    If n_subsets volumes fit `weight_cache_bytes`, C_s is built on the subset's first visit and kept; otherwise the column sums
+    are rebuilt on every visit in the same march as the numerator.  `callback(k, x, residual_norm)` sees the live volume."""
+    import numpy as np
+    import torch
+
+    from . import _abi, projector, sart
+    relax, relax_red, n_iter = _check_os_sart(relax, relax_red, n_iter)
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError("os_sart: projections must be a CUDA/HIP tensor (no CPU path)")
+    angles = np.asarray(angles, dtype=np.float64).reshape(-1)
+    subsets = subset_order(angles, len(angles) if n_subsets is None else n_subsets, order, seed)
+    scan = sart.Scan(geo, angles, projections.device)
+    if x0 is None:
+        x = torch.zeros(scan.dims, device=projections.device, dtype=torch.float32)
+    else:
+        _abi.check_volume(x0, "os_sart", "x0")
+        projector.check_geometry(x0, geo)
+        x = x0.clone()
+    lists = [sart.ViewList(s, scan.N, projections.device) for s in subsets]
+    most = max(len(v) for v in lists)
+    y = torch.empty(most, scan.H, scan.W, device=x.device, dtype=torch.float32)
+    r = torch.empty_like(y)
+    num = torch.zeros_like(x)
+    cached = len(lists) * x.numel() * 4 <= int(weight_cache_bytes)
+    C = [None] * len(lists)
+    den = None if cached else torch.zeros_like(x)
+    beta, norms = relax, []
+    for k in range(n_iter):
+        total = torch.zeros((), device=x.device, dtype=torch.float64)
+        for s, views in enumerate(lists):
+            ys, rs = sart.residual_scan(x, projections, geo, angles, views, y=y[:len(views)], r=r[:len(views)], scan=scan)
+            total += (ys.double() * rs.double()).sum()
+            if C[s] is not None:
+                sart.backproject_scan(ys, geo, angles, views, num=num, scan=scan)
+                sart.update(x, num, C[s], beta, nonneg, den_is_reciprocal=True)
+            elif cached:
+                C[s] = torch.zeros_like(x)
+                sart.backproject_scan(ys, geo, angles, views, num=num, den=C[s], scan=scan)
+                sart.update(x, num, C[s], beta, nonneg)
+                C[s] = torch.where(C[s] > 0, 1.0 / C[s], torch.zeros_like(x))
+            else:
+                sart.backproject_scan(ys, geo, angles, views, num=num, den=den, scan=scan)
+                sart.update(x, num, den, beta, nonneg, zero_den=True)
+        norms.append(math.sqrt(float(total)))
+        beta *= relax_red
+        if callback is not None:
+            callback(k, x, norms[-1])
+    return x, norms
 
 
 def asd_pocs_operators(A, AT, b, n_iter, tv_descent, relax=1.0, relax_red=0.99, alpha=0.002, alpha_red=0.95, rmax=0.95, tv_steps=20,

@@ -1,0 +1,166 @@
+"""OS-SART without a GPU: `reconstruct.os_sart_operators` in float64 over the dense-matrix subset operators of
+tests/_sart_oracle.py, `reconstruct.subset_order`, and the host-side argument checks of the three P4 entry points."""
+import ctypes
+import os
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+import _sart_oracle as S
+import _tv_oracle as T
+
+
+@pytest.fixture(scope="module")
+def case():
+    return S.pocs_operators()
+
+
+def test_one_subset_of_all_views_is_sirt(case):
+    """Same bits as `sirt_operators`, volume and norms, at 7 iterations; also at relax 0.9 and from a start volume."""
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import os_sart_operators, sirt_operators
+    A, AT, b, _, _, (A_all, AT_all, b_flat) = case
+    for kwargs in ({}, {"relax": 0.9, "nonneg": False, "x0": np.full(T.POCS_DIMS, 0.1)}):
+        want, want_norms = sirt_operators(A_all, AT_all, b_flat, 7, **kwargs)
+        got, norms = os_sart_operators(A, AT, b, [[0, 1, 2, 3]], 7, **kwargs)
+        print(f"{kwargs and 'relax 0.9, x0'}: max abs difference {np.abs(got - want).max()}")
+        assert np.array_equal(got, want) and norms == want_norms
+
+
+@pytest.mark.parametrize("n_iter", [5, 20])
+def test_subsets_beat_sirt_at_equal_iterations(case, n_iter):
+    """The rehearsal case (16^3 phantom, four cone views of 24 x 24, float64, relax 1): psnr_3d as pinned in _sart_oracle.POCS_PSNR,
+    OS-SART above SIRT and its final ||b - A x||_2 below SIRT's, for one and for two views per subset."""
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import os_sart_operators, sirt_operators
+    A, AT, b, x_true, _, (A_all, AT_all, b_flat) = case
+    x_sirt, _ = sirt_operators(A_all, AT_all, b_flat, n_iter)
+    p_sirt, d_sirt = T.psnr_3d(x_sirt, x_true), float(np.linalg.norm(b_flat - A_all(x_sirt)))
+    assert abs(p_sirt - S.POCS_PSNR[n_iter][0]) <= 0.01, p_sirt
+    for subsets, pinned in ((S.SART_SUBSETS, S.POCS_PSNR[n_iter][1]), (S.PAIR_SUBSETS, S.POCS_PSNR[n_iter][2])):
+        seen = []
+        x, norms = os_sart_operators(A, AT, b, subsets, n_iter, callback=lambda k, xk, nk: seen.append((k, nk)))
+        p, d = T.psnr_3d(x, x_true), float(np.linalg.norm(b_flat - A_all(x)))
+        print(f"{n_iter} iterations, {len(subsets)} subsets: psnr_3d {p:.3f} dB (SIRT {p_sirt:.3f}), "
+              f"||b - A x||_2 {d:.3e} (SIRT {d_sirt:.3e}), norms {norms[0]:.4e} -> {norms[-1]:.4e}")
+        assert abs(p - pinned) <= 0.01, (p, pinned)
+        assert p > p_sirt and d < d_sirt
+        assert x.shape == T.POCS_DIMS and float(x.min()) >= 0
+        assert len(norms) == n_iter and seen == list(enumerate(norms)) and norms[-1] < norms[0]
+
+
+def test_relax_red_start_volume_and_tensors(case):
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import os_sart_operators
+    A, AT, b, _, _, _ = case
+    x0 = np.full(T.POCS_DIMS, 0.1)
+    got, norms = os_sart_operators(A, AT, b, S.SART_SUBSETS, 0, x0=x0)
+    assert np.array_equal(got, x0) and got is not x0 and norms == []
+    # relax_red: iteration k runs at relax * relax_red^k, so two iterations at (1, 0.5) are one at 1 followed by one at 0.5
+    first, _ = os_sart_operators(A, AT, b, S.SART_SUBSETS, 1)
+    want, _ = os_sart_operators(A, AT, b, S.SART_SUBSETS, 1, relax=0.5, x0=first)
+    got, _ = os_sart_operators(A, AT, b, S.SART_SUBSETS, 2, relax_red=0.5)
+    assert np.array_equal(got, want) and np.array_equal(x0, np.full(T.POCS_DIMS, 0.1))
+    tx, tn = os_sart_operators(lambda x, v: torch.tensor(A(x.numpy(), v)), lambda y, v: torch.tensor(AT(y.numpy(), v)),
+                               torch.tensor(b), S.PAIR_SUBSETS, 3)
+    nx, nn = os_sart_operators(A, AT, b, S.PAIR_SUBSETS, 3)
+    assert isinstance(tx, torch.Tensor) and np.abs(tx.numpy() - nx).max() <= 1e-12 and abs(tn[-1] - nn[-1]) <= 1e-12
+
+
+def test_subset_order():
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import subset_order
+    rng = np.random.default_rng(0)
+    angles = rng.permutation(np.linspace(0, np.pi, 51)[:-1])              # 50 views, not in angular order
+    rank = np.argsort(np.argsort(angles))
+    for n_subsets in (1, 7, 10, 50):
+        for order in ("sequential", "random", "angular-distance"):
+            subsets = subset_order(angles, n_subsets, order, seed=3)
+            assert len(subsets) == n_subsets
+            assert sorted(int(v) for s in subsets for v in s) == list(range(50))          # every view exactly once
+            for s in subsets:                                                              # round-robin in sorted-angle order
+                assert len({int(rank[v]) % n_subsets for v in s}) == 1
+                assert list(rank[s]) == sorted(rank[s]) and len(s) in (50 // n_subsets, -(-50 // n_subsets))
+    seq = subset_order(angles, 7, "sequential")
+    assert [int(rank[s[0]]) for s in seq] == list(range(7))
+    a, b, c = (subset_order(angles, 10, "random", seed=s) for s in (1, 1, 2))
+    assert all(np.array_equal(p, q) for p, q in zip(a, b))
+    assert any(not np.array_equal(p, q) for p, q in zip(a, c))
+    assert any(not np.array_equal(p, q) for p, q in zip(a, subset_order(angles, 10, "sequential")))
+    # eight equally spaced one-view subsets: no two angular neighbours (directions pi / 8 apart, mod pi) in a row
+    eight = np.linspace(0, np.pi, 9)[:-1]
+    visit = [int(s[0]) for s in subset_order(eight, 8, "angular-distance")]
+    print("angular-distance order of 8 equally spaced views:", visit)
+    assert sorted(visit) == list(range(8)) and visit[0] == 0 and visit[1] == 4
+    for p, q in zip(visit, visit[1:]):
+        assert min((p - q) % 8, (q - p) % 8) >= 2, visit
+    for bad in (0, 51, -1):
+        with pytest.raises(ValueError, match="n_subsets"):
+            subset_order(angles, bad)
+    with pytest.raises(ValueError, match="order"):
+        subset_order(angles, 5, "spiral")
+
+
+@pytest.mark.parametrize("name,value", [("relax", 0.0), ("relax", 1.5), ("relax", float("nan")), ("relax_red", 0.0),
+                                        ("relax_red", 1.01), ("n_iter", -1)])
+def test_os_sart_argument_errors(name, value):
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import os_sart_operators
+    kwargs = {"n_iter": 1, name: value}
+    with pytest.raises(ValueError, match=rf"\b{name}\b"):
+        os_sart_operators(lambda x, v: x, lambda y, v: y, np.ones((2, 1, 1)), [[0], [1]], **kwargs)
+
+
+@pytest.mark.parametrize("subsets", [[], [[0], []], [[0, 2]], [[-1]]])
+def test_os_sart_refuses_bad_subsets(subsets):
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import os_sart_operators
+    with pytest.raises(ValueError, match="subsets"):
+        os_sart_operators(lambda x, v: x, lambda y, v: y, np.ones((2, 1, 1)), subsets, 1)
+
+
+def test_library_rejects_bad_arguments():
+    """The three entry points validate on the host before any HIP call: NAF_ERR_INVALID_ARGUMENT and a message; a zero count is a
+    successful no-op whose pointers are not examined.  Without a device the non-null pointers are small made-up addresses, which
+    nothing dereferences; where one is visible they are real device buffers large enough for the sizes the calls state."""
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi, build
+    if not os.path.exists(build.LIB_PATH) and shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("libnaf_hip.so not built and no hipcc here")
+    lib = _abi.lib()
+    if torch.cuda.is_available():
+        keep = [torch.zeros(1 << 20, dtype=torch.uint8, device="cuda") for _ in range(3)]
+        one, two, three = (ctypes.c_void_p(t.data_ptr()) for t in keep)
+    else:
+        one, two, three = ctypes.c_void_p(16), ctypes.c_void_p(32), ctypes.c_void_p(48)
+    dims = (ctypes.c_uint32 * 3)(4, 4, 4)
+    flat = (ctypes.c_uint32 * 3)(4, 0, 4)
+    dv = (ctypes.c_float * 3)(1e-3, 1e-3, 1e-3)
+    det = (8, 8, 1e-3, 1e-3, 0.0, 0.0, 1.5, 0.5, 1.5, 0, 5e-4)          # det_w .. step
+
+    def residual(volume=one, d=dims, voxel=dv, poses=two, n_sub=2, geo=det, index=None, n_scan=2, proj=three, y=three, r=None):
+        return lib.naf_sart_residual_scan(volume, d, voxel, poses, n_sub, *geo, index, n_scan, proj, y, r, None)
+
+    def transpose(y=three, index=None, n_sub=2, n_scan=2, d=dims, voxel=dv, poses=two, geo=det, num=one, den=None):
+        return lib.naf_sart_backproject_scan(y, index, n_sub, n_scan, d, voxel, poses, *geo, num, den, None)
+
+    for call, word in ((lambda: residual(volume=None), b"null pointer"), (lambda: residual(d=None), b"null pointer"),
+                       (lambda: residual(voxel=None), b"null pointer"), (lambda: residual(poses=None), b"null pointer"),
+                       (lambda: residual(proj=None), b"null pointer"), (lambda: residual(y=None), b"null pointer"),
+                       (lambda: residual(d=flat), b"zero volume dimension"),
+                       (lambda: residual(geo=(0,) + det[1:]), b"empty detector"),
+                       (lambda: residual(geo=det[:6] + (0.0,) + det[7:]), b"DSD"),
+                       (lambda: residual(geo=det[:10] + (0.0,)), b"step"),
+                       (lambda: residual(n_sub=3), b"n_sub must be <= n_scan_views"),
+                       (lambda: transpose(y=None), b"null pointer"), (lambda: transpose(num=None), b"null pointer"),
+                       (lambda: transpose(d=None), b"null pointer"), (lambda: transpose(poses=None), b"null pointer"),
+                       (lambda: transpose(d=flat), b"zero volume dimension"),
+                       (lambda: transpose(den=one), b"two volumes"),
+                       (lambda: transpose(n_sub=3), b"n_sub must be <= n_scan_views"),
+                       (lambda: lib.naf_sart_update(None, two, three, 8, 1.0, 1, 0, 0, None), b"null pointer"),
+                       (lambda: lib.naf_sart_update(one, None, three, 8, 1.0, 1, 0, 0, None), b"null pointer"),
+                       (lambda: lib.naf_sart_update(one, two, None, 8, 1.0, 1, 0, 0, None), b"null pointer"),
+                       (lambda: lib.naf_sart_update(one, two, three, 8, float("nan"), 1, 0, 0, None), b"relax"),
+                       (lambda: lib.naf_sart_update(one, two, three, 8, 1.0, 1, 1, 1, None), b"zero_den"),
+                       (lambda: lib.naf_sart_update(ctypes.c_void_p(one.value + 2), two, three, 8, 1.0, 1, 0, 0, None), b"aligned")):
+        assert call() == -1
+        assert word in lib.naf_last_error(), (word, lib.naf_last_error())
+    assert residual(volume=None, d=None, voxel=None, poses=None, n_sub=0, proj=None, y=None) == 0
+    assert transpose(y=None, n_sub=0, d=None, voxel=None, poses=None, num=None) == 0
+    assert lib.naf_sart_update(None, None, None, 0, 1.0, 1, 0, 0, None) == 0
+    assert lib.naf_abi_version() == 5
