@@ -529,6 +529,34 @@ int naf_sart_backproject_scan(const float *y, const uint32_t *view_index, uint32
 int naf_sart_update(float *x, float *num, float *den, uint64_t n, float relax, int nonneg, int den_is_reciprocal, int zero_den,
                     void *stream);
 
+/* P5  back-projector in gather form: the operator of P2 / P4's transpose, evaluated per voxel with no atomics.
+ *   values       f32 [n_sub, det_h, det_w], one value y_r per ray, indexed by LAUNCH view (P4's y)
+ *   view_index, n_sub, n_scan_views, poses  as in P4: launch view j is scan view v = view_index[j] (j itself when NULL, then
+ *                n_sub <= n_scan_views); poses f32 [n_scan_views, 12] is the whole scan, read in place; an index >= n_scan_views
+ *                adds nothing and nothing is read through it
+ *   volume       f32 [n1, n2, n3], ACCUMULATED INTO: volume += A_s^T values
+ *   den          f32 [n1, n2, n3] or NULL, another volume, ACCUMULATED INTO: den += A_s^T 1, from the same march.  Whether den is
+ *                given does not change a bit of `volume`
+ *   workspace    DEVICE, 8-byte aligned, or NULL.  With one, a pre-pass writes the span (p0, d, seg, len / n, n) of every ray into
+ *                it, NAF_GATHER_SPAN_BYTES per ray, and the gather reads them; the views go in groups of
+ *                workspace_bytes / (NAF_GATHER_SPAN_BYTES * det_h * det_w), which must be >= 1.  Without one every span is
+ *                recomputed where it is needed.  The spans are the same floats either way: the result has the same bits
+ * Ray r takes P1's own t0, t1, len, n, seg, sample positions, trilinear cell and weights, as in P2.  One lane owns one voxel c and,
+ * view after view in launch order, forms
+ *     s_view = sum over the view's pixels in ascending (row, col) of  (y_r * (len / n)) * W_r,   W_r = sum_{k ascending} w_c(r, k)
+ * in fp32 (rays with W_r == 0 are skipped; den takes (len / n) * W_r), then volume[c] = (...((volume[c] + s_1) + s_2)...).  w_c(r, k)
+ * is the weight P2's sample k of ray r gives c: the same (x * y) * z product of the same w_a or 1 - w_a.  Only the pixels of c's
+ * footprint rectangle and the samples of a k-range are visited (csrc/backproject_gather_device.h); both are supersets of the pairs
+ * with w_c != 0, so the sums are those of A^T.  The order is fixed: two calls on the same inputs return the same bits, and so does
+ * a scan split into several calls in view order.  Against P2 the result differs by rounding only (P2 sums per cell run and in
+ * hardware order).  No atomics, no LDS.  All offsets are 64-bit.
+ * n_sub == 0 returns NAF_OK without examining the pointers; a pixel pitch that is 0 or not finite is refused. */
+#define NAF_GATHER_SPAN_BYTES 40u
+int naf_backproject_scan_gather(const float *values, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
+                                const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h,
+                                float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel, float step,
+                                float *volume, float *den, void *workspace, size_t workspace_bytes, void *stream);
+
 /* M1  3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
  * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
  * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.

@@ -18,12 +18,8 @@ struct RayGeo {
     int parallel;           // 0 cone, 1 parallel
 };
 
-__device__ __forceinline__ void make_ray(const float *__restrict__ poses, uint64_t flat, const RayGeo &g, float4 *out) {
-    const uint64_t per_proj = (uint64_t)g.W * g.H;
-    const uint32_t proj = (uint32_t)(flat / per_proj);
-    const uint32_t rem = (uint32_t)(flat - (uint64_t)proj * per_proj);
-    const uint32_t row = rem / g.W, col = rem - row * g.W;
-    const float *P = poses + (size_t)proj * 12;                 // 3x4 row-major [R | t]
+// The ray of pixel (row, col) of the view with pose P (3x4 row-major [R | t]).
+__device__ __forceinline__ void make_pixel_ray(const float *__restrict__ P, uint32_t row, uint32_t col, const RayGeo &g, float4 *out) {
     // tigre.py:423-429: uu along columns, vv along rows
     const float uu = ((float)col + 0.5f - (float)g.W / 2.0f) * g.du + g.ou;
     const float vv = ((float)row + 0.5f - (float)g.H / 2.0f) * g.dv + g.ov;
@@ -44,6 +40,14 @@ __device__ __forceinline__ void make_ray(const float *__restrict__ poses, uint64
     }
     out[0] = make_float4(o[0], o[1], o[2], d[0]);
     out[1] = make_float4(d[1], d[2], g.near, g.far);
+}
+
+__device__ __forceinline__ void make_ray(const float *__restrict__ poses, uint64_t flat, const RayGeo &g, float4 *out) {
+    const uint64_t per_proj = (uint64_t)g.W * g.H;
+    const uint32_t proj = (uint32_t)(flat / per_proj);
+    const uint32_t rem = (uint32_t)(flat - (uint64_t)proj * per_proj);
+    const uint32_t row = rem / g.W, col = rem - row * g.W;
+    make_pixel_ray(poses + (size_t)proj * 12, row, col, g, out);
 }
 
 // ---- G6: the data side of a training step on the device (reference src/dataset/tigre.py:354-372) ------------------

@@ -20,6 +20,10 @@ from .geometry import RayGenerator
 
 # pixels per launch of naf_project_scan: keeps one launch of a 720 x 1024^2 scan to a bounded grid
 MAX_PIXELS_PER_CALL = 1 << 26
+# the gather transpose's span table (naf_hip.h P5): 40 bytes per ray, and at most this much of it, so that it stays in the caches
+GATHER_SPAN_BYTES = 40
+GATHER_WORKSPACE_CAP = 32 << 20
+METHODS = ("scatter", "gather")
 
 
 def _check_volume(volume):
@@ -108,7 +112,9 @@ def _check_out(out, shape, like, who):
 
 def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None):
     """Transpose of `project_rays`: adds `values` [n] along `rays` [n, 8] into a volume of `dims` = (n1, n2, n3) voxels of size
-    `dvoxel` -> float32 [n1, n2, n3].  Sums are fp32 atomics: equal to A^T values up to summation order (naf_hip.h, P2)."""
+    `dvoxel` -> float32 [n1, n2, n3].  Sums are fp32 atomics: equal to A^T values up to summation order (naf_hip.h, P2).
+    Arbitrary rays lie on no pixel lattice, so this entry point keeps the scatter only: the atomic-free gather form
+    (`backproject_scan(..., method="gather")`) exists for scans."""
     if not isinstance(values, torch.Tensor) or not values.is_cuda:
         raise RuntimeError("backproject_rays: values must be a CUDA/HIP tensor (no CPU path)")
     if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device != values.device:
@@ -130,9 +136,29 @@ def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None):
     return out
 
 
-def backproject_scan(projections, geo, angles, views_per_call=None, out=None):
+def check_method(method, who):
+    if method not in METHODS:
+        raise ValueError(f"{who}: method must be one of {METHODS}, got {method!r}")
+    return method
+
+
+def gather_workspace(n_views, H, W, device, span_table=True):
+    """Span table of the gather transpose for calls of up to `n_views` views of H x W pixels -> uint8 tensor, or None without a
+    table.  At least one view, at most GATHER_WORKSPACE_CAP bytes beyond that: the entry point walks the views in groups that fit."""
+    if not span_table:
+        return None
+    per_view = GATHER_SPAN_BYTES * H * W
+    views = max(1, min(int(n_views), GATHER_WORKSPACE_CAP // per_view))
+    return torch.empty(views * per_view, device=device, dtype=torch.uint8)
+
+
+def backproject_scan(projections, geo, angles, views_per_call=None, out=None, method="scatter", span_table=True):
     """Transpose of `project_scan`: adds `projections` [N, H, W] of the scan geometry `geo` at `angles` into a volume on the voxel
-    grid of `geo` -> float32 nVoxel.  Views go to the kernel in groups of `views_per_call` like `project_scan`'s."""
+    grid of `geo` -> float32 nVoxel.  Views go to the kernel in groups of `views_per_call` like `project_scan`'s.
+    `method="scatter"` (the default) is the ray scatter on fp32 atomics, equal to A^T y up to summation order; `method="gather"`
+    is the same operator evaluated per voxel in a fixed order with no atomics (naf_hip.h P5): two calls return the same bits,
+    whatever `views_per_call` and `span_table` (whether the rays' spans are tabulated by a pre-pass or recomputed) are."""
+    check_method(method, "backproject_scan")
     if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
         raise RuntimeError("backproject_scan: projections must be a CUDA/HIP tensor (no CPU path)")
     dims = tuple(int(v) for v in geo.nVoxel)
@@ -153,11 +179,18 @@ def backproject_scan(projections, geo, angles, views_per_call=None, out=None):
     dv = _dvoxel(geo.dVoxel)
     step = sample_step(geo.dVoxel, geo.accuracy)
     lib = _abi.lib()
+    detector = (W, H, float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]),
+                float(geo.DSD), float(raygen.near), float(raygen.far), int(geo.mode == "parallel"), step)
+    work = gather_workspace(min(per_call, N), H, W, projections.device, span_table) if method == "gather" else None
     for first in range(0, N, per_call):
         count = min(per_call, N - first)
+        if method == "gather":
+            _abi.check(lib.naf_backproject_scan_gather(
+                _abi.ptr(projections[first:first + count]), None, count, count, ctypes.byref(cdims), ctypes.byref(dv),
+                _abi.ptr(raygen.poses[first:first + count]), *detector, _abi.ptr(out), None, _abi.ptr(work),
+                0 if work is None else work.numel(), _abi.stream_ptr()), "backproject_scan_gather")
+            continue
         _abi.check(lib.naf_backproject_scan(
             _abi.ptr(projections[first:first + count]), ctypes.byref(cdims), ctypes.byref(dv),
-            _abi.ptr(raygen.poses[first:first + count]), count, W, H, float(geo.dDetector[0]), float(geo.dDetector[1]),
-            float(geo.offDetector[0]), float(geo.offDetector[1]), float(geo.DSD), float(raygen.near), float(raygen.far),
-            int(geo.mode == "parallel"), step, _abi.ptr(out), _abi.stream_ptr()), "backproject_scan")
+            _abi.ptr(raygen.poses[first:first + count]), count, *detector, _abi.ptr(out), _abi.stream_ptr()), "backproject_scan")
     return out

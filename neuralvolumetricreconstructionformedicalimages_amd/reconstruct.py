@@ -113,16 +113,25 @@ def sirt_operators(A, AT, b, n_iter, relax=1.0, nonneg=True, x0=None, callback=N
     return x, norms
 
 
-def sirt(projections, geo, angles, n_iter=50, relax=1.0, nonneg=True, x0=None, callback=None, views_per_call=None):
+def _method(deterministic):
+    """`deterministic=True` binds the gather transpose (projector.backproject_scan(method="gather")): no atomics, so a run returns
+    the same bits every time; the default keeps the scatter."""
+    return "gather" if deterministic else "scatter"
+
+
+def sirt(projections, geo, angles, n_iter=50, relax=1.0, nonneg=True, x0=None, callback=None, views_per_call=None,
+         deterministic=False):
     """SIRT reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
-    (float32 volume of geo.nVoxel on the projections' device, residual norms).  See the module docstring for the iteration."""
+    (float32 volume of geo.nVoxel on the projections' device, residual norms).  See the module docstring for the iteration.
+    `deterministic=True` takes the atomic-free transpose: two runs return the same bits."""
     from . import projector
+    method = _method(deterministic)
 
     def A(x):
         return projector.project_scan(x, geo, angles, views_per_call=views_per_call)
 
     def AT(y):
-        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call)
+        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call, method=method)
 
     return sirt_operators(A, AT, projections, n_iter, relax=relax, nonneg=nonneg, x0=x0, callback=callback)
 
@@ -209,13 +218,15 @@ def os_sart_operators(A, AT, b, subsets, n_iter, relax=1.0, relax_red=1.0, nonne
 
 
 def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-distance", relax=1.0, relax_red=1.0, nonneg=True,
-            x0=None, callback=None, weight_cache_bytes=2 << 30, seed=0):
+            x0=None, callback=None, weight_cache_bytes=2 << 30, seed=0, deterministic=False):
     """OS-SART reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, residual norms).  `n_subsets=None` is one view per subset (SART);
     the subsets and their order come from `subset_order(angles, n_subsets, order, seed)`.  The iteration of `os_sart_operators`,
     run directly on the subset kernels of `sart`: per subset one residual launch, one paired back-projection and one update.
     If n_subsets volumes fit `weight_cache_bytes`, C_s is built on the subset's first visit and kept; otherwise the column sums
-    are rebuilt on every visit in the same march as the numerator.  `callback(k, x, residual_norm)` sees the live volume."""
+    are rebuilt on every visit in the same march as the numerator.  `callback(k, x, residual_norm)` sees the live volume.
+    `deterministic=True` takes the atomic-free transpose for the numerator and the column sums on all three routes: two runs
+    return the same bits and the same norms."""
     import numpy as np
     import torch
 
@@ -234,6 +245,9 @@ def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-
         x = x0.clone()
     lists = [sart.ViewList(s, scan.N, projections.device) for s in subsets]
     most = max(len(v) for v in lists)
+    transpose = {"method": _method(deterministic), "scan": scan}
+    if deterministic:
+        transpose["workspace"] = projector.gather_workspace(most, scan.H, scan.W, projections.device)
     y = torch.empty(most, scan.H, scan.W, device=x.device, dtype=torch.float32)
     r = torch.empty_like(y)
     num = torch.zeros_like(x)
@@ -247,15 +261,15 @@ def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-
             ys, rs = sart.residual_scan(x, projections, geo, angles, views, y=y[:len(views)], r=r[:len(views)], scan=scan)
             total += (ys.double() * rs.double()).sum()
             if C[s] is not None:
-                sart.backproject_scan(ys, geo, angles, views, num=num, scan=scan)
+                sart.backproject_scan(ys, geo, angles, views, num=num, **transpose)
                 sart.update(x, num, C[s], beta, nonneg, den_is_reciprocal=True)
             elif cached:
                 C[s] = torch.zeros_like(x)
-                sart.backproject_scan(ys, geo, angles, views, num=num, den=C[s], scan=scan)
+                sart.backproject_scan(ys, geo, angles, views, num=num, den=C[s], **transpose)
                 sart.update(x, num, C[s], beta, nonneg)
                 C[s] = torch.where(C[s] > 0, 1.0 / C[s], torch.zeros_like(x))
             else:
-                sart.backproject_scan(ys, geo, angles, views, num=num, den=den, scan=scan)
+                sart.backproject_scan(ys, geo, angles, views, num=num, den=den, **transpose)
                 sart.update(x, num, den, beta, nonneg, zero_den=True)
         norms.append(math.sqrt(float(total)))
         beta *= relax_red
@@ -307,17 +321,19 @@ def asd_pocs_operators(A, AT, b, n_iter, tv_descent, relax=1.0, relax_red=0.99, 
 
 
 def asd_pocs(projections, geo, angles, n_iter=50, relax=1.0, relax_red=0.99, alpha=0.002, alpha_red=0.95, rmax=0.95, tv_steps=20,
-             tv_eps=1e-8, nonneg=True, x0=None, callback=None, views_per_call=None):
+             tv_eps=1e-8, nonneg=True, x0=None, callback=None, views_per_call=None, deterministic=False):
     """ASD-POCS reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, history).  The data step is `sirt`'s update, the TV step
-    `tv.tv_descent` with `tv_eps`; see the module docstring and `asd_pocs_operators`."""
+    `tv.tv_descent` with `tv_eps`; see the module docstring and `asd_pocs_operators`.  `deterministic=True` takes the atomic-free
+    transpose: two runs return the same bits and the same history."""
     from . import projector, tv
+    method = _method(deterministic)
 
     def A(x):
         return projector.project_scan(x, geo, angles, views_per_call=views_per_call)
 
     def AT(y):
-        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call)
+        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call, method=method)
 
     scratch = []
 
@@ -366,13 +382,15 @@ def fdk_operators(AT, filter_rows, b, geo, angles, filter="ram-lak", nonneg=Fals
     return x
 
 
-def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call=None):
+def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call=None, deterministic=False):
     """FDK reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry, cone or untilted parallel
     beam) at `angles` -> float32 volume of geo.nVoxel on the projections' device.  One pass of `filter.filter_rows` and one of
-    `projector.backproject_scan`; see the module docstring."""
+    `projector.backproject_scan`; see the module docstring.  `deterministic=True` takes the atomic-free transpose: two runs return
+    the same bits."""
     import torch
 
     from . import filter as F, projector
+    method = _method(deterministic)
 
     def on_device(a):
         return None if a is None else torch.tensor(a, device=projections.device)
@@ -381,6 +399,6 @@ def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call
         return F.filter_rows(b, on_device(taps), on_device(pre), on_device(post), on_device(view_scale))
 
     def AT(y):
-        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call)
+        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call, method=method)
 
     return fdk_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=nonneg)

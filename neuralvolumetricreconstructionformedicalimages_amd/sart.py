@@ -120,10 +120,13 @@ def residual_scan(volume, projections, geo, angles, views=None, y=None, r=None, 
     return y, r
 
 
-def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None):
+def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None, method="scatter", workspace=None):
     """Transpose over the same view list: adds A_s^T y into `num` (None: a zeroed volume) and, if `den` is given, A_s^T 1 into
-    `den`, both float32 volumes on the voxel grid of `geo` that are accumulated into -> num."""
+    `den`, both float32 volumes on the voxel grid of `geo` that are accumulated into -> num.  `method="gather"` takes the
+    atomic-free gather form (naf_hip.h P5; the same bits on every call) instead of the scatter; `workspace` is then a span table
+    from `projector.gather_workspace` to reuse across calls (None: one is made; False: none, the spans are recomputed)."""
     who = "sart.backproject_scan"
+    projector.check_method(method, who)
     if not isinstance(y, torch.Tensor) or not y.is_cuda:
         raise RuntimeError(f"{who}: y must be a CUDA/HIP tensor (no CPU path)")
     scan = _scan(geo, angles, y.device, scan)
@@ -137,7 +140,20 @@ def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None):
             raise ValueError(f"{who}: den must be a contiguous float32 {scan.dims} tensor on the input's device")
         if den.data_ptr() == num.data_ptr():
             raise ValueError(f"{who}: num and den must be two volumes")
-    if m:
+    if m and method == "gather":
+        if workspace is None:
+            workspace = projector.gather_workspace(m, scan.H, scan.W, y.device)
+        elif workspace is False:
+            workspace = None
+        elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+              or not workspace.is_contiguous() or workspace.device != y.device):
+            raise ValueError(f"{who}: workspace must be a contiguous uint8 [bytes] tensor on the input's device "
+                             "(projector.gather_workspace), None or False")
+        _abi.check(_abi.lib().naf_backproject_scan_gather(
+            _abi.ptr(y), _index_ptr(views), m, scan.N, ctypes.byref(scan._cdims), ctypes.byref(scan._dvoxel),
+            _abi.ptr(scan.raygen.poses), *scan.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.ptr(workspace),
+            0 if workspace is None else workspace.numel(), _abi.stream_ptr()), "backproject_scan_gather")
+    elif m:
         _abi.check(_abi.lib().naf_sart_backproject_scan(
             _abi.ptr(y), _index_ptr(views), m, scan.N, ctypes.byref(scan._cdims), ctypes.byref(scan._dvoxel),
             _abi.ptr(scan.raygen.poses), *scan.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.stream_ptr()),

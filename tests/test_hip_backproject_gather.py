@@ -1,0 +1,370 @@
+"""The gather-form transpose on the GPU (naf_backproject_scan_gather; `method="gather"` of projector.backproject_scan and
+sart.backproject_scan, `deterministic=True` of the four baselines) against the float64 scatter of
+tests/_backproject_oracle.py, the shipped scatter and forward kernels, and itself: the same bits on every call."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import _backproject_gather_oracle as G
+import _backproject_oracle as B
+import _sart_oracle as S
+import _tv_oracle as T
+from test_hip_projector import _geometry
+
+pytestmark = pytest.mark.gpu
+
+BOUND = 1e-5                   # tests/test_hip_backproject.py's bound for the scatter: max abs error <= 1e-5 x max |A^T y|
+SEVEN = np.linspace(0.1, 3.0, 7)
+
+# name -> (scanner dict, angles): the geometries of the CPU test plus the seven-view scans with partial tiles of the scatter tests
+# (dims (40, 48, 24): ten bricks along x, twelve along y, two workgroups along z, the second half empty)
+CASES = dict(G.geometries())
+for _mode, _tilt in (("cone", 0), ("parallel", 29)):
+    CASES[f"{_mode}-{_tilt}-seven"] = (dict(_geometry(_mode, _tilt), nDetector=[37, 21]), SEVEN)
+PARITY = [n for n in CASES if n.split("-")[0] in ("cone", "parallel")]
+SPECIAL = ["axis-parallel", "clipped", "off-detector", "anisotropic"]
+
+
+def _dev(a):
+    return torch.tensor(a, device="cuda")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """Inputs and float64 references of a case, made once and shared by the tests (read only)."""
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    data, angles = CASES[name]
+    geo = ConeGeometry(data)
+    angles = np.asarray(angles, dtype=np.float64)
+    dims = tuple(int(v) for v in geo.nVoxel)
+    N, H, W = len(angles), int(geo.nDetector[1]), int(geo.nDetector[0])
+    y = np.random.default_rng(len(name)).uniform(0.5, 1.5, (N, H, W)).astype(np.float32)
+    rays = B.case_rays(geo, angles)
+    num, den = S.backprojection(y, rays, geo, dims)
+    for a in (y, rays, num, den):
+        a.setflags(write=False)
+    return dict(geo=geo, angles=angles, dims=dims, y=y, rays=rays, num=num, den=den)
+
+
+def _check(got, want, what):
+    got = got.cpu().numpy().astype(np.float64)
+    scale, err = np.abs(want).max(), np.abs(got - want).max()
+    print(f"{what}: max abs err / max = {err / scale:.3e}, zero voxels {(want == 0).sum()} of {want.size}")
+    assert scale > 0 and (got[want == 0] == 0).all()
+    assert err <= BOUND * scale, (what, err, scale)
+
+
+@pytest.mark.parametrize("name", PARITY + SPECIAL)
+def test_gather_matches_float64(name):
+    from neuralvolumetricreconstructionformedicalimages_amd import projector
+    c = _case(name)
+    got = projector.backproject_scan(_dev(c["y"]), c["geo"], c["angles"], method="gather")
+    assert got.shape == c["dims"] and got.dtype == torch.float32
+    _check(got, c["num"], name)
+    assert torch.equal(got, projector.backproject_scan(_dev(c["y"]), c["geo"], c["angles"], method="gather", span_table=False))
+
+
+def test_near_and_far_cut_through_the_volume():
+    """Through the C entry point, with a [near, far] window that ends inside the volume on both sides."""
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi, projector
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import RayGenerator
+    c = _case("cone-0-seven")
+    geo, dims = c["geo"], c["dims"]
+    near, far = float(geo.DSO) - 0.011, float(geo.DSO) + 0.007
+    rays = c["rays"].copy()
+    rays[:, 6], rays[:, 7] = near, far
+    full = B.ray_lengths(c["rays"], dims, geo.dVoxel, geo.accuracy)
+    cut = B.ray_lengths(rays, dims, geo.dVoxel, geo.accuracy)
+    assert ((cut > 0) & (cut < 0.9 * full)).sum() > 1000
+    want = B.backproject_rays(c["y"].reshape(-1), geo.dVoxel, rays, dims, geo.accuracy)
+    gen = RayGenerator(geo, c["angles"], "cuda")
+    N, H, W = c["y"].shape
+    for table in (True, False):
+        out = torch.zeros(dims, device="cuda")
+        work = projector.gather_workspace(N, H, W, "cuda", table)
+        _abi.check(_abi.lib().naf_backproject_scan_gather(
+            _abi.ptr(_dev(c["y"])), None, N, N, ctypes.byref((ctypes.c_uint32 * 3)(*dims)), ctypes.byref(projector._dvoxel(geo.dVoxel)),
+            _abi.ptr(gen.poses), W, H, float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]),
+            float(geo.offDetector[1]), float(geo.DSD), near, far, 0, projector.sample_step(geo.dVoxel, geo.accuracy), _abi.ptr(out), None,
+            _abi.ptr(work), 0 if work is None else work.numel(), _abi.stream_ptr()), "backproject_scan_gather")
+        _check(out, want, f"near / far, span table {table}")
+
+
+@pytest.mark.parametrize("name", ["cone-0-seven", "parallel-29-seven"])
+@pytest.mark.parametrize("views", [[5, 0, 3], None])
+def test_view_list_and_column_sums(name, views):
+    from neuralvolumetricreconstructionformedicalimages_amd import sart
+    c = _case(name)
+    geo, angles, dims = c["geo"], c["angles"], c["dims"]
+    listed = list(range(len(angles))) if views is None else views
+    y = np.ascontiguousarray(c["y"][:len(listed)])
+    want_num, want_den = S.backprojection(y, S.view_rays(geo, angles, listed), geo, dims)
+    den = torch.zeros(dims, device="cuda")
+    num = sart.backproject_scan(_dev(y), geo, angles, views, den=den, method="gather")
+    _check(num, want_num, f"{name} {views}: num")
+    _check(den, want_den, f"{name} {views}: den")
+    assert torch.equal(sart.backproject_scan(_dev(y), geo, angles, views, method="gather"), num)            # den = NULL: same bits
+    assert torch.equal(sart.backproject_scan(_dev(y), geo, angles, views, method="gather", workspace=False), num)
+    again = torch.zeros(dims, device="cuda")
+    sart.backproject_scan(_dev(y), geo, angles, views, den=again, method="gather", workspace=False)
+    assert torch.equal(again, den)
+
+
+@pytest.mark.parametrize("name", ["cone-0-seven", "parallel-29-seven"])
+def test_the_same_bits_every_time(name):
+    from neuralvolumetricreconstructionformedicalimages_amd import projector
+    c = _case(name)
+    geo, angles, y = c["geo"], c["angles"], _dev(c["y"])
+    full = projector.backproject_scan(y, geo, angles, method="gather")
+    assert int((full != 0).sum()) > 500
+    assert torch.equal(projector.backproject_scan(y, geo, angles, method="gather"), full)
+    for per_call in (1, 3):
+        assert torch.equal(projector.backproject_scan(y, geo, angles, views_per_call=per_call, method="gather"), full), per_call
+    # accumulating into a non-zero volume: start, then the views one by one, each a single fp32 add per voxel
+    start = torch.rand(c["dims"], device="cuda", generator=torch.Generator(device="cuda").manual_seed(5)) * full.max()
+    out = start.clone()
+    assert projector.backproject_scan(y, geo, angles, out=out, method="gather") is out
+    want = start.clone()
+    for i in range(len(angles)):
+        want = want + projector.backproject_scan(y[i:i + 1], geo, angles[i:i + 1], method="gather")
+    assert torch.equal(out, want)
+    assert float((out - start).max()) > 0.5 * float(full.max())
+
+
+@pytest.mark.parametrize("name", ["cone-0-seven", "parallel-29-seven"])
+def test_against_the_scatter_and_the_forward(name):
+    from neuralvolumetricreconstructionformedicalimages_amd import projector
+    c = _case(name)
+    geo, angles, y = c["geo"], c["angles"], _dev(c["y"])
+    gather = projector.backproject_scan(y, geo, angles, method="gather")
+    scatter = projector.backproject_scan(y, geo, angles)
+    diff, top = float((gather - scatter).abs().max()), float(scatter.abs().max())
+    print(f"{name}: gather vs scatter {diff / top:.3e} of max")
+    assert diff <= 2 * BOUND * top
+    x = torch.rand(c["dims"], device="cuda", generator=torch.Generator(device="cuda").manual_seed(6)) + 0.1
+    ax = projector.project_scan(x, geo, angles)
+    lhs, rhs = float((ax.double() * y.double()).sum()), float((x.double() * gather.double()).sum())
+    rel = abs(lhs - rhs) / abs(lhs)
+    print(f"{name}: <Ax, y> = {lhs:.9e}, <x, A^T y> = {rhs:.9e}, relative difference {rel:.3e}")
+    assert lhs > 0 and rel <= 1e-5
+
+
+def test_volume_beyond_4gib():
+    """A zeroed 1040^3 fp32 volume (4.2 GiB) and one view of a 64 x 2 detector that spans it: non-zero voxels past the 4 GiB byte
+    offset, and the volume's sum is sum_r y_r len_r."""
+    from neuralvolumetricreconstructionformedicalimages_amd import projector
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    n = 1040
+    assert n ** 3 * 4 > 2 ** 32
+    free, _ = torch.cuda.mem_get_info()
+    if free < 6 * 2 ** 30:
+        pytest.skip("needs 6 GiB of free device memory")
+    data = _geometry("cone", 0, (n, n, n), (0.25, 0.25, 0.25))
+    data.update(nDetector=[64, 2], dDetector=[6.5, 40.0], offDetector=[0.0, 0.0])
+    geo = ConeGeometry(data)
+    angles = np.array([0.3])
+    y = np.random.default_rng(17).uniform(0.5, 1.5, (1, 2, 64)).astype(np.float32)
+    vol = torch.zeros(n, n, n, device="cuda")
+    projector.backproject_scan(_dev(y), geo, angles, out=vol, method="gather")
+    lengths = B.ray_lengths(B.case_rays(geo, angles), (n, n, n), geo.dVoxel, geo.accuracy)
+    assert (lengths > 0).sum() >= 100
+    flat = vol.reshape(-1)
+    past = flat[2 ** 30:]                                                        # element 2^30 starts at byte 2^32
+    assert int((past != 0).sum()) > 1000
+    total, want = float(flat.sum(dtype=torch.float64)), float((y.reshape(-1).astype(np.float64) * lengths).sum())
+    print(f"sum {total:.9e} vs {want:.9e}: relative {abs(total - want) / want:.3e}")
+    assert abs(total - want) <= 1e-5 * want
+    del vol, flat, past
+    torch.cuda.empty_cache()
+
+
+# ---- end to end: the baselines with deterministic=True, each run twice, at the rehearsals of their own GPU tests ----------------
+
+@functools.lru_cache(maxsize=None)
+def _pocs_scan():
+    from neuralvolumetricreconstructionformedicalimages_amd import projector
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    geo = ConeGeometry(T.pocs_geometry())
+    truth = T.pocs_phantom()
+    return geo, truth, projector.project_scan(_dev(truth), geo, T.POCS_ANGLES)
+
+
+def test_sirt_and_asd_pocs_are_reproducible():
+    """tests/test_hip_tv.py's rehearsal and tolerances (0.5 dB of the float64 figures, ASD-POCS 1.5 dB above SIRT)."""
+    from neuralvolumetricreconstructionformedicalimages_amd import asd_pocs, sirt
+    geo, truth, proj = _pocs_scan()
+    runs = [sirt(proj, geo, T.POCS_ANGLES, n_iter=T.POCS_ITERS, deterministic=True) for _ in range(2)]
+    assert torch.equal(runs[0][0], runs[1][0]) and runs[0][1] == runs[1][1] and len(runs[0][1]) == T.POCS_ITERS
+    pocs = [asd_pocs(proj, geo, T.POCS_ANGLES, n_iter=T.POCS_ITERS, deterministic=True) for _ in range(2)]
+    assert torch.equal(pocs[0][0], pocs[1][0]) and pocs[0][1] == pocs[1][1] and len(pocs[0][1]) == T.POCS_ITERS
+    p_sirt, p_pocs = T.psnr_3d(runs[0][0].cpu().numpy(), truth), T.psnr_3d(pocs[0][0].cpu().numpy(), truth)
+    print(f"psnr_3d after {T.POCS_ITERS} iterations, deterministic: SIRT {p_sirt:.3f} dB (float64 {T.POCS_PSNR_SIRT}), "
+          f"ASD-POCS {p_pocs:.3f} dB (float64 {T.POCS_PSNR_ASD_POCS})")
+    assert p_pocs >= p_sirt + 1.5
+    assert abs(p_sirt - T.POCS_PSNR_SIRT) <= 0.5 and abs(p_pocs - T.POCS_PSNR_ASD_POCS) <= 0.5
+
+
+def test_os_sart_is_reproducible():
+    """tests/test_hip_sart.py's rehearsal and tolerances: cached, uncached and two subsets."""
+    from neuralvolumetricreconstructionformedicalimages_amd import os_sart, sirt
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import os_sart_operators
+    A, AT, b64, x_true, (geo, _), _ = S.pocs_operators()
+    x64, norms64 = os_sart_operators(A, AT, b64, S.SART_SUBSETS, 20)
+    b = _dev(b64.astype(np.float32))
+    routes = {"cached": dict(n_iter=20), "uncached": dict(n_iter=20, weight_cache_bytes=0),
+              "two subsets": dict(n_iter=5, n_subsets=2, order="sequential")}
+    got = {}
+    for name, kwargs in routes.items():
+        first, second = (os_sart(b, geo, T.POCS_ANGLES, deterministic=True, **kwargs) for _ in range(2))
+        assert torch.equal(first[0], second[0]) and first[1] == second[1], name
+        got[name] = first
+    x, norms = got["cached"]
+    p, p64 = T.psnr_3d(x.cpu().numpy().astype(np.float64), x_true), T.psnr_3d(x64, x_true)
+    p_un = T.psnr_3d(got["uncached"][0].cpu().numpy(), x_true)
+    print(f"deterministic os_sart: psnr_3d {p:.3f} dB (float64 {p64:.3f}), uncached {p_un:.4f} dB, first norm relative "
+          f"{abs(norms[0] - norms64[0]) / norms64[0]:.3e}")
+    assert abs(p - p64) <= 0.1 and abs(norms[0] - norms64[0]) <= 1e-5 * norms64[0]
+    assert abs(p - p_un) <= 0.01
+    one, _ = sirt(b, geo, T.POCS_ANGLES, n_iter=5, deterministic=True)
+    assert T.psnr_3d(got["two subsets"][0].cpu().numpy(), x_true) > T.psnr_3d(one.cpu().numpy(), x_true)
+
+
+def test_fdk_is_reproducible():
+    """tests/test_hip_fdk.py's 16^3 cone rehearsal, its per-voxel bound against float64 and its 0.1 dB."""
+    import _filter_oracle as F
+    from neuralvolumetricreconstructionformedicalimages_amd import fdk
+    from neuralvolumetricreconstructionformedicalimages_amd.utils import get_psnr_3d
+    r = F.fdk_rehearsal(F.REHEARSAL_SIZES[0], "cone")
+    b = _dev(r["b"])
+    x, again = (fdk(b, r["geo"], r["angles"], deterministic=True) for _ in range(2))
+    assert torch.equal(x, again)
+    assert torch.equal(fdk(b, r["geo"], r["angles"], deterministic=True, views_per_call=5), x)
+    got = x.cpu().numpy().astype(np.float64)
+    bound = 2e-5 * float(r["AT"](np.abs(r["y"])).max()) + r["AT"](F.filter_bound(r["b"], *r["weights"]))
+    err = np.abs(got - r["x"])
+    psnr = float(get_psnr_3d(x.cpu().numpy(), r["truth"]))
+    print(f"deterministic fdk: worst ratio to the bound {(err / bound).max():.4f}, psnr_3d {psnr:.4f} dB (float64 {r['psnr']:.4f})")
+    assert np.all(err <= bound) and abs(psnr - r["psnr"]) <= 0.1
+
+
+def test_out_of_range_view_index_adds_nothing():
+    """P4's rule, through the C entry point (sart.ViewList refuses such an index): an index >= n_scan_views adds nothing to either
+    output, so the list [5, 9, 3] of a seven-view scan returns the bits of [5, 3]."""
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi, projector, sart
+    c = _case("cone-0-seven")
+    geo, dims = c["geo"], c["dims"]
+    scan = sart.Scan(geo, c["angles"], torch.device("cuda"))
+    y = _dev(c["y"][:3])
+
+    def call(index, values, table):
+        num, den = torch.zeros(dims, device="cuda"), torch.zeros(dims, device="cuda")
+        idx = torch.tensor(index, device="cuda", dtype=torch.int32)
+        work = projector.gather_workspace(len(index), scan.H, scan.W, "cuda", table)
+        _abi.check(_abi.lib().naf_backproject_scan_gather(
+            _abi.ptr(values), _abi.ptr(idx), len(index), scan.N, ctypes.byref(scan._cdims), ctypes.byref(scan._dvoxel),
+            _abi.ptr(scan.raygen.poses), *scan.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.ptr(work),
+            0 if work is None else work.numel(), _abi.stream_ptr()), "backproject_scan_gather")
+        return num, den
+
+    for table in (True, False):
+        want = call([5, 3], y[[0, 2]].contiguous(), table)
+        for bad in (7, 9, 2 ** 31 - 1):
+            got = call([5, bad, 3], y, table)
+            assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), (table, bad)
+        assert int((want[0] != 0).sum()) > 500 and int((want[1] != 0).sum()) > 500
+    nothing = call([7, 8], y[:2].contiguous(), True)
+    assert int((nothing[0] != 0).sum()) == 0 and int((nothing[1] != 0).sum()) == 0
+
+
+def test_wrong_shapes_and_dtypes_are_refused():
+    """The checks of the scatter route hold for method="gather": the existing errors, and a given `out` / `num` / `den` untouched."""
+    from neuralvolumetricreconstructionformedicalimages_amd import projector, sart
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    geo = ConeGeometry(_geometry("cone"))
+    dims = tuple(int(v) for v in geo.nVoxel)
+    angles = [0.2, 1.9]
+    y = torch.ones(2, 16, 20, device="cuda")
+    keep = torch.full(dims, 2.0, device="cuda")
+
+    def gather(*args, **kwargs):
+        return projector.backproject_scan(*args, method="gather", **kwargs)
+
+    with pytest.raises(ValueError, match="projections must be"):
+        gather(y[:, :, :19].contiguous(), geo, angles, out=keep)
+    with pytest.raises(ValueError, match="projections must be"):
+        gather(y[:1], geo, angles, out=keep)
+    with pytest.raises(ValueError, match="float32"):
+        gather(y.double(), geo, angles, out=keep)
+    with pytest.raises(ValueError, match="contiguous"):
+        gather(torch.ones(2, 20, 16, device="cuda").transpose(1, 2), geo, angles, out=keep)
+    with pytest.raises(ValueError, match="out must be"):
+        gather(y, geo, angles, out=torch.zeros(40, 48, 25, device="cuda"))
+    with pytest.raises(TypeError, match="float32"):
+        gather(y, geo, angles, out=torch.zeros(dims, device="cuda", dtype=torch.float64))
+    with pytest.raises(ValueError, match="offOrigin"):
+        gather(y, ConeGeometry(dict(_geometry("cone"), offOrigin=[0, 1.0, 0])), angles, out=keep)
+    with pytest.raises(ValueError, match="method must be one of"):
+        projector.backproject_scan(y, geo, angles, out=keep, method="x")
+    assert torch.equal(gather(torch.zeros(0, 16, 20, device="cuda"), geo, [], out=keep), keep)       # an empty scan: a no-op
+    num, den = keep.clone(), torch.full(dims, 3.0, device="cuda")
+
+    def paired(values, views=None, **kwargs):
+        return sart.backproject_scan(values, geo, angles, views, method="gather", **{"num": num, "den": den, **kwargs})
+
+    with pytest.raises(ValueError, match="y must be float32"):
+        paired(y[:, :15].contiguous())
+    with pytest.raises(ValueError, match="y must be float32"):
+        paired(y, [1])                                                           # one view listed, two given
+    with pytest.raises(ValueError, match="y must be float32"):
+        paired(y.half())
+    with pytest.raises(ValueError, match="out must be"):
+        paired(y, num=torch.zeros(40, 48, 25, device="cuda"))
+    with pytest.raises(ValueError, match="den must be"):
+        paired(y, den=torch.zeros(40, 48, 25, device="cuda"))
+    with pytest.raises(TypeError, match="float32"):
+        paired(y, den=torch.zeros(dims, device="cuda", dtype=torch.float64))
+    with pytest.raises(ValueError, match="two volumes"):
+        paired(y, den=num)
+    with pytest.raises(ValueError, match="view index out of range"):
+        paired(y, [0, 2])
+    with pytest.raises(ValueError, match="method must be one of"):
+        sart.backproject_scan(y, geo, angles, num=num, den=den, method="scatter ")
+    for bad in (torch.empty(1 << 16, dtype=torch.uint8), torch.empty(1 << 14, device="cuda"),
+                torch.empty(4, 1 << 14, device="cuda", dtype=torch.uint8), "table"):
+        with pytest.raises(ValueError, match="workspace must be"):
+            paired(y, workspace=bad)
+    with pytest.raises(RuntimeError, match="workspace too small"):
+        paired(y, workspace=torch.empty(40 * 16 * 20 - 8, device="cuda", dtype=torch.uint8))
+    assert torch.equal(keep, torch.full(dims, 2.0, device="cuda"))
+    assert torch.equal(num, keep) and torch.equal(den, torch.full(dims, 3.0, device="cuda"))
+    # and one view's worth of workspace is enough for two views, to the same bits
+    small = paired(y, num=None, den=None, workspace=torch.empty(40 * 16 * 20, device="cuda", dtype=torch.uint8))
+    assert torch.equal(small, paired(y, num=None, den=None)) and int((small != 0).sum()) > 500
+
+
+def test_the_tools_with_deterministic_and_an_fdk_start(tmp_path):
+    """`--deterministic --init fdk`: the start volume takes the gather transpose too, so two runs of a tool write the same bits."""
+    import importlib.util
+    import os
+    import pickle
+    geo, truth, proj = _pocs_scan()
+    data = dict(T.pocs_geometry(), image=truth, train={"projections": proj.cpu().numpy(), "angles": np.asarray(T.POCS_ANGLES)})
+    scan = tmp_path / "scan.pickle"
+    with open(scan, "wb") as handle:
+        pickle.dump(data, handle)
+    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
+    for name, extra in (("reconstruct_sirt", ["--iters", "3", "--init", "fdk"]), ("reconstruct_asd_pocs", ["--iters", "3", "--init", "fdk"]),
+                        ("reconstruct_os_sart", ["--iters", "2", "--init", "fdk"]), ("reconstruct_fdk", [])):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(tools, name + ".py"))
+        tool = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(tool)
+        volumes = []
+        for run in range(2):
+            out = tmp_path / f"{name}_{run}.npy"
+            res = tool.main(["--scan", str(scan), "--deterministic", "--out", str(out), *extra])
+            volumes.append((np.load(out), res["residual_first"], res["residual_last"]))
+        assert volumes[0][0].tobytes() == volumes[1][0].tobytes() and volumes[0][1:] == volumes[1][1:], name
+        assert np.abs(volumes[0][0]).max() > 0.1

@@ -4,6 +4,12 @@ the chest shape (50 x 512^2 pixels, 256^3 volume, accuracy 0.5) and a 1024^3 vol
 
     python tools/backproject_bench.py                         # both shapes, one JSON line each
     python tools/backproject_bench.py --shape chest --lib lib/ab/per_sample.so      # an A/B variant of libnaf_hip.so
+    python tools/backproject_bench.py --gather --shape chest  # the gather form next to the scatter
+
+With `--gather` (shapes chest, step: one 512^2 view into 256^3, the OS-SART subset step, and small: 50 x 256^2 into 128^3) the line
+also holds the gather transpose's time with and without the span table, its ratio to the scatter, whether two calls returned the
+same bits, and the per-voxel, per-view counts of pixels visited, candidate samples and non-zero samples over `--count-voxels`
+random voxels and three views (the float32 restatement of tests/_backproject_gather_oracle.py, on the host).
 
 Reported: device-event time of one call (median of `--windows` windows of `--iters` calls after warm-up; A^T accumulates into a
 volume that is zeroed once, outside the timing), the exact sample count, the atomics A^T would send without merging (8 per
@@ -38,8 +44,34 @@ def _time(fn, warmup, iters, windows):
     return statistics.median(out), min(out), max(out)
 
 
-def run(shape, warmup, iters, windows):
+GATHER_SHAPES = {"step": (256, 512, 1, 0.8, 1.0), "small": (128, 256, 50, 1.6, 2.0)}
+
+
+def gather_columns(geo, angles, y, scatter, scatter_ms, warmup, iters, windows, count_voxels):
+    from neuralvolumetricreconstructionformedicalimages_amd import projector
+    out = {}
+    acc = torch.zeros_like(scatter)
+    for name, table in (("gather_ms", True), ("gather_no_table_ms", False)):
+        t = _time(lambda: projector.backproject_scan(y, geo, angles, out=acc, method="gather", span_table=table), warmup, iters, windows)
+        out[name], out[name + "_min_max"] = round(t[0], 4), [round(t[1], 4), round(t[2], 4)]
+    out["gather_to_scatter"] = round(out["gather_ms"] / scatter_ms, 3)
+    a, b = (projector.backproject_scan(y, geo, angles, method="gather", span_table=t) for t in (True, False))
+    out["gather_same_bits"] = bool(torch.equal(a, b) and torch.equal(a, projector.backproject_scan(y, geo, angles, method="gather")))
+    out["gather_vs_scatter_max_rel"] = float((a - scatter).abs().max() / scatter.abs().max())
+    if count_voxels:
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        import _backproject_gather_oracle as G
+        voxels = np.random.default_rng(0).integers(0, [int(v) for v in geo.nVoxel], (count_voxels, 3))
+        some = angles[np.linspace(0, len(angles) - 1, min(3, len(angles))).astype(int)]
+        counts = G.visit_counts(geo, some, voxels)
+        out["per_voxel_view"] = {"pixels": round(counts[0], 2), "candidate_samples": round(counts[1], 2),
+                                 "nonzero_samples": round(counts[2], 2), "voxels": count_voxels, "views": len(some)}
+    return out
+
+
+def run(shape, warmup, iters, windows, gather=False, count_voxels=0):
     from project_bench import SHAPES, segments
+    SHAPES = {**SHAPES, **GATHER_SHAPES}
     from neuralvolumetricreconstructionformedicalimages_amd import phantom, projector
     from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry, RayGenerator
     nv, det, views, pitch, vox = SHAPES[shape]
@@ -58,16 +90,21 @@ def run(shape, warmup, iters, windows):
     raygen = RayGenerator(geo, angles, "cuda")
     step = projector.sample_step(geo.dVoxel, geo.accuracy)
     samples = sum(int(segments(raygen.rays_for_projection(i), x.shape, geo.dVoxel, step)[3].sum()) for i in range(views))
-    return {"shape": shape, "volume": [nv] * 3, "detector": [det, det], "views": views, "accuracy": geo.accuracy,
+    res = {"shape": shape, "volume": [nv] * 3, "detector": [det, det], "views": views, "accuracy": geo.accuracy,
             "forward_ms": round(fwd[0], 4), "forward_ms_min_max": [round(fwd[1], 4), round(fwd[2], 4)],
             "backproject_ms": round(bwd[0], 4), "backproject_ms_min_max": [round(bwd[1], 4), round(bwd[2], 4)],
             "ratio_to_forward": round(bwd[0] / fwd[0], 2), "samples": samples, "samples_per_s": samples / bwd[0] * 1e3,
             "unmerged_atomic_GB_per_s": samples * 32 / bwd[0] * 1e-6, "adjoint_mismatch": abs(lhs - rhs) / lhs}
+    if gather:
+        res.update(gather_columns(geo, angles, y, aty, bwd[0], warmup, iters, windows, count_voxels))
+    return res
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", choices=["chest", "big", "all"], default="all")
+    ap.add_argument("--shape", choices=["chest", "big", "step", "small", "all"], default="all")
+    ap.add_argument("--gather", action="store_true", help="also time the gather transpose (with and without its span table)")
+    ap.add_argument("--count-voxels", type=int, default=64, help="voxels of the per-voxel visit counts of --gather (0: none)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--windows", type=int, default=3)
@@ -77,7 +114,7 @@ def main():
         from neuralvolumetricreconstructionformedicalimages_amd import build
         build.LIB_PATH = os.path.abspath(args.lib)
     for shape in (["chest", "big"] if args.shape == "all" else [args.shape]):
-        res = run(shape, args.warmup, args.iters, args.windows)
+        res = run(shape, args.warmup, args.iters, args.windows, args.gather, args.count_voxels if args.gather else 0)
         if args.lib:
             res["lib"] = os.path.basename(args.lib)
         print(json.dumps(res), flush=True)

@@ -31,7 +31,8 @@ def main(argv=None):
     def solve(args, proj, geo, angles):
         x, history = asd_pocs(proj, geo, angles, n_iter=args.iters, relax=args.relax, relax_red=args.relax_red, alpha=args.alpha,
                               alpha_red=args.alpha_red, rmax=args.rmax, tv_steps=args.tv_steps, tv_eps=args.tv_eps,
-                              nonneg=not args.no_nonneg, x0=reconstruct_sirt.start_volume(args, proj, geo, angles))
+                              nonneg=not args.no_nonneg, x0=reconstruct_sirt.start_volume(args, proj, geo, angles),
+                              deterministic=args.deterministic)
         extra = {"relax_red": args.relax_red, "alpha": args.alpha, "alpha_red": args.alpha_red, "rmax": args.rmax,
                  "tv_steps": args.tv_steps, "tv_eps": args.tv_eps, "dtvg_last": history[-1]["dtvg"] if history else None}
         return x, [e["residual"] for e in history], extra

@@ -41,7 +41,7 @@ def main(argv=None):
 
     def solve(args, proj, geo, angles):
         covered, short = coverage(geo, angles)
-        x = fdk(proj, geo, angles, filter=args.filter, nonneg=args.nonneg)
+        x = fdk(proj, geo, angles, filter=args.filter, nonneg=args.nonneg, deterministic=args.deterministic)
         return x, [], {"filter": args.filter, "covered_degrees": round(covered, 3), "short_scan": short, "nonneg": args.nonneg}
 
     return reconstruct_sirt.main(argv, solve=solve, add_arguments=add_arguments, description=__doc__, iterative=False)

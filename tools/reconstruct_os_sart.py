@@ -31,7 +31,7 @@ def main(argv=None):
     def solve(args, proj, geo, angles):
         x, norms = os_sart(proj, geo, angles, n_iter=args.iters, n_subsets=args.subsets, order=args.order, relax=args.relax,
                            relax_red=args.relax_red, nonneg=not args.no_nonneg, x0=reconstruct_sirt.start_volume(args, proj, geo, angles),
-                           weight_cache_bytes=int(args.weight_cache_gib * 2 ** 30), seed=args.seed)
+                           weight_cache_bytes=int(args.weight_cache_gib * 2 ** 30), seed=args.seed, deterministic=args.deterministic)
         extra = {"subsets": args.subsets or len(angles), "order": args.order, "relax_red": args.relax_red,
                  "weights_cached": (args.subsets or len(angles)) * x.numel() * 4 <= int(args.weight_cache_gib * 2 ** 30)}
         return x, norms, extra

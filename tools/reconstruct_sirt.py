@@ -23,17 +23,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def start_volume(args, proj, geo, angles):
-    """The `x0` of an iterative solver for `--init`: None (zeros), or the FDK volume (reconstruct.fdk, ram-lak) clamped at 0."""
+    """The `x0` of an iterative solver for `--init`: None (zeros), or the FDK volume (reconstruct.fdk, ram-lak) clamped at 0,
+    back-projected by the transpose the solve itself takes (`--deterministic`: a reproducible run needs a reproducible start)."""
     if args.init == "zeros":
         return None
     from neuralvolumetricreconstructionformedicalimages_amd import fdk
-    return fdk(proj, geo, angles, nonneg=True)
+    return fdk(proj, geo, angles, nonneg=True, deterministic=args.deterministic)
 
 
 def _sirt(args, proj, geo, angles):
     from neuralvolumetricreconstructionformedicalimages_amd import sirt
     x, norms = sirt(proj, geo, angles, n_iter=args.iters, relax=args.relax, nonneg=not args.no_nonneg,
-                    x0=start_volume(args, proj, geo, angles))
+                    x0=start_volume(args, proj, geo, angles), deterministic=args.deterministic)
     return x, norms, {}
 
 
@@ -54,6 +55,8 @@ def main(argv=None, solve=_sirt, add_arguments=None, description=None, iterative
                         help="start volume: zeros, or the FDK reconstruction of the same projections clamped at 0 (inside the timing)")
     ap.add_argument("--out", default=None, help="write the volume here as .npy")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="take the atomic-free gather transpose (DESIGN.md section 17): two runs return the same bits")
     if add_arguments is not None:
         add_arguments(ap)
     args = ap.parse_args(argv)
