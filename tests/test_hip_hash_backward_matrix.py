@@ -1,0 +1,265 @@
+"""naf_hash_encode_backward / _backward_ws pinned to float64 references over the whole dispatch table.
+
+The equivalence tests of the suite (binned scatter == atomic scatter, _ws == atomic route, Adam tail == naf_adam_step) prove as much as
+is known about hash_backward_kernel and input_backward_kernel; here those two are compared with tests/_hash_backward_oracle.py, per
+element and with bounds derived there (validated on the CPU in test_hash_backward_oracle_cpu.py): D in {2, 3} x C in {1, 2, 4, 8} x
+fp32 / fp16 / bf16 gradients x both layouts (load_vec widths of 2 .. 32 bytes), the `+=` contract, level sizes that are no powers of
+two (the real-modulo hash regime, reachable through `offsets` alone), and the workspace route with input gradients."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import _hash_backward_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+DTYPES = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}
+DC = [(D, C) for D in (2, 3) for C in (1, 2, 4, 8)]
+L, H, B = O.MATRIX_L, O.MATRIX_H, O.MATRIX_B
+PREFILL, SENTINEL, GUARD_ROWS = 0.375, -7.25, 64
+
+
+def _mods():
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi
+    from oracle import c_oracle
+    return _abi, c_oracle
+
+
+def _layout(_abi, g_blc, layout, n_levels):
+    """[B, L*C] host tensor in its storage type -> device tensor in `layout`, layout code."""
+    gd = g_blc.cuda()
+    if layout == "lbc":
+        return gd.view(gd.shape[0], n_levels, -1).permute(1, 0, 2).contiguous(), _abi.LAYOUT_LBC
+    return gd, _abi.LAYOUT_BLC
+
+
+@functools.lru_cache(maxsize=None)
+def _grad(kind, D, C, dtype):
+    """Points, offsets, the gradient rounded to its storage type, and the float64 table reference of those stored values."""
+    offs = O.matrix_offsets(D) if kind == "matrix" else O.odd_offsets(D)
+    x = O.matrix_points(D, 10 * D + C)
+    g = torch.from_numpy(O.matrix_grad(C, 100 + 10 * D + C)).to(DTYPES[dtype])
+    s, a, n = O.table_gradient(g.double().numpy(), x, offs, H, C)
+    for arr in (s, a, n):
+        arr.setflags(write=False)
+    return offs, x, g, (s, a, n)
+
+
+def _check_table(got_all, rows, ref, what):
+    """got_all: [rows + GUARD_ROWS, C] after a `+=` into PREFILL; the pre-fill is one more term of the sum (of `a` and of `n`)."""
+    s, a, n = ref
+    got_all = got_all.cpu()
+    assert torch.equal(got_all[rows:], torch.full_like(got_all[rows:], SENTINEL)), f"{what}: rows behind the table were written"
+    got = got_all[:rows].numpy()
+    assert np.array_equal(got[n == 0], np.full_like(got[n == 0], PREFILL)), f"{what}: a row no point touches has changed"
+    err = np.abs(got.astype(np.float64) - (s + PREFILL))
+    bound = O.table_bound(a + PREFILL, n + 1.0)
+    hit = n > 0
+    print(f"{what}: worst element uses {(err[hit] / bound[hit]).max():.3f} of the bound")
+    assert np.all(err[hit] <= bound[hit]), f"{what}: {int((err[hit] > bound[hit]).sum())} elements outside the bound"
+
+
+def _table(rows, C):
+    t = torch.full((rows + GUARD_ROWS, C), PREFILL, device="cuda")
+    t[rows:] = SENTINEL
+    return t
+
+
+def _backward(_abi, gd, lay, xd, od, ge, D, C, dtype, n_levels=L, base=H, calc=0, jac=None, gi=None):
+    _abi.check(_abi.lib().naf_hash_encode_backward(_abi.ptr(gd), _abi.ptr(xd), None, _abi.ptr(od), _abi.ptr(ge), xd.shape[0], D, C, n_levels,
+                                                   base, calc, _abi.ptr(jac), _abi.ptr(gi), _abi.dtype_code(DTYPES[dtype]), lay,
+                                                   _abi.stream_ptr()))
+    torch.cuda.synchronize()
+
+
+def _forward(_abi, xd, ed, od, D, C, layout, mode, n_levels=L, base=H):
+    n = xd.shape[0]
+    lay = _abi.LAYOUT_BLC if layout == "blc" else _abi.LAYOUT_LBC
+    out = torch.empty((n, n_levels * C) if layout == "blc" else (n_levels, n, C), device="cuda", dtype=ed.dtype)
+    jac = torch.empty(n, n_levels, D, C, device="cuda", dtype=ed.dtype) if mode else None
+    _abi.check(_abi.lib().naf_hash_encode_forward(_abi.ptr(xd), _abi.ptr(ed), _abi.ptr(od), _abi.ptr(out), n, D, C, n_levels, base, mode,
+                                                  _abi.ptr(jac), _abi.dtype_code(ed.dtype), lay, _abi.stream_ptr()))
+    torch.cuda.synchronize()
+    return out, jac
+
+
+# ---- a. the table gradient over the whole dispatch table -------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ["blc", "lbc"])
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("D,C", DC)
+def test_table_gradient(D, C, dtype, layout):
+    _abi, _ = _mods()
+    offs, x, g, ref = _grad("matrix", D, C, dtype)
+    rows = int(offs[-1])
+    gd, lay = _layout(_abi, g, layout, L)
+    ge = _table(rows, C)
+    _backward(_abi, gd, lay, torch.from_numpy(x).cuda(), torch.from_numpy(offs).cuda(), ge, D, C, dtype)
+    _check_table(ge, rows, ref, f"D={D} C={C} {dtype} {layout}")
+
+
+# ---- b. the forward's dy_dx store and the input gradient -------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _forward_ref(kind, D, C, dtype, mode):
+    """The table rounded to its storage type and oracle/hash_ref.c (fp32 math) on those rounded values: outputs [L, B, C], dy_dx."""
+    _, c_oracle = _mods()
+    offs, x, _, _ = _grad(kind, D, C, dtype)
+    rng = np.random.default_rng(1000 + 10 * D + C)
+    emb = torch.from_numpy(rng.uniform(-1, 1, (int(offs[-1]), C)).astype(np.float32)).to(DTYPES[dtype])
+    out, jac = c_oracle.hash_encode_forward(x, emb.float().numpy(), offs, H, calc_grad_inputs=mode)
+    return emb, torch.from_numpy(out), (torch.from_numpy(jac) if mode else None)
+
+
+def _check_forward(out, jac, ref_out, ref_jac, layout, dt, what):
+    """fp32: bit-exact; 16-bit: the fp32 result rounded once at the store (torch's conversion is round-to-nearest-even too)."""
+    n = ref_out.shape[1]
+    expect = ref_out if layout == "lbc" else ref_out.permute(1, 0, 2).reshape(n, -1)
+    assert torch.equal(out.cpu(), expect.to(dt)), f"{what}: outputs"
+    if ref_jac is not None:
+        assert torch.equal(jac.cpu(), ref_jac.to(dt)), f"{what}: dy_dx"
+
+
+@pytest.mark.parametrize("mode", [1, 2], ids=["exact", "reference"])
+@pytest.mark.parametrize("layout", ["blc", "lbc"])
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("D,C", DC)
+def test_dy_dx_and_input_gradient(D, C, dtype, layout, mode):
+    _abi, _ = _mods()
+    dt = DTYPES[dtype]
+    offs, x, g, _ = _grad("matrix", D, C, dtype)
+    emb, ref_out, ref_jac = _forward_ref("matrix", D, C, dtype, mode)
+    xd, od = torch.from_numpy(x).cuda(), torch.from_numpy(offs).cuda()
+    what = f"D={D} C={C} {dtype} {layout} mode={mode}"
+    out, jac = _forward(_abi, xd, emb.cuda(), od, D, C, layout, mode)
+    _check_forward(out, jac, ref_out, ref_jac, layout, dt, what)
+
+    start = torch.from_numpy(np.random.default_rng(D + C).standard_normal((B, D)).astype(np.float32))
+    gi = start.cuda()
+    gd, lay = _layout(_abi, g, layout, L)
+    _backward(_abi, gd, lay, xd, od, _table(int(offs[-1]), C), D, C, dtype, calc=mode, jac=jac, gi=gi)
+    s, a = O.input_gradient(g.double().numpy().reshape(B, L, C), jac.cpu().double().numpy(), start.numpy())
+    err, bound = np.abs(gi.cpu().double().numpy() - s), O.input_bound(start.numpy(), a, L, C)
+    print(f"{what}: worst input gradient uses {(err / bound).max():.3f} of the bound")
+    assert np.all(err <= bound)
+
+
+# ---- c. level sizes that are no powers of two ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", ["fp32", "fp16"])
+@pytest.mark.parametrize("D", [2, 3])
+def test_level_sizes_that_are_no_powers_of_two(D, dtype):
+    """Hand-written offsets, sizes [5^D, 500, 777, 1000, 512, 333]: the hashed ones but 512 take `index % size` with a real modulo.
+    Forward without dy_dx (D = 3: the training path's encoder) and with it (the one-point-per-lane kernel), then the scatter."""
+    _abi, _ = _mods()
+    C, dt = 2, DTYPES[dtype]
+    offs, x, g, ref = _grad("odd", D, C, dtype)
+    rows = int(offs[-1])
+    assert rows == 5 ** D + 500 + 777 + 1000 + 512 + 333
+    xd, od = torch.from_numpy(x).cuda(), torch.from_numpy(offs).cuda()
+    emb, ref_out, ref_jac = _forward_ref("odd", D, C, dtype, 1)
+    for layout in ("lbc", "blc"):
+        out, _ = _forward(_abi, xd, emb.cuda(), od, D, C, layout, 0)
+        _check_forward(out, None, ref_out, None, layout, dt, f"odd sizes D={D} {dtype} {layout}")
+        out, jac = _forward(_abi, xd, emb.cuda(), od, D, C, layout, 1)
+        _check_forward(out, jac, ref_out, ref_jac, layout, dt, f"odd sizes D={D} {dtype} {layout} with dy_dx")
+        gd, lay = _layout(_abi, g, layout, L)
+        ge = _table(rows, C)
+        _backward(_abi, gd, lay, xd, od, ge, D, C, dtype)
+        _check_table(ge, rows, ref, f"odd sizes D={D} {dtype} {layout}")
+
+
+# ---- d. the workspace route with input gradients ---------------------------------------------------------------------------------
+WS_L, WS_H, WS_LOG2T, WS_B = 16, 16, 14, 8192
+
+
+@functools.lru_cache(maxsize=None)
+def _ws_points():
+    """Samples of rays inside [0, 1]^3: runs of equal cells on the coarse levels, like the points of a training step."""
+    g0 = torch.Generator().manual_seed(11)
+    n_rays, S = 64, 128
+    o = torch.rand(n_rays, 1, 3, generator=g0)
+    d = torch.rand(n_rays, 1, 3, generator=g0) - 0.5
+    x = (o + d * torch.linspace(0, 1.0, S).view(1, S, 1)).clamp(0.0, 1.0).reshape(-1, 3).contiguous()
+    assert x.shape[0] == WS_B
+    from oracle import hashgrid_ref
+    return x, hashgrid_ref.level_offsets(WS_L, WS_H, WS_LOG2T, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def _ws_case(C, dtype):
+    x, offs = _ws_points()
+    g0 = torch.Generator().manual_seed(100 + C)
+    g = torch.randn(WS_B, WS_L * C, generator=g0).to(DTYPES[dtype])
+    # table values of +-2^-10: the finest level's d feature / d x is 2^19 times a difference of two of them, and has to fit fp16
+    emb = ((torch.rand(int(offs[-1]), C, generator=g0) * 2 - 1) * 2.0 ** -10).to(DTYPES[dtype])
+    start = torch.randn(WS_B, 3, generator=g0)
+    return g, emb, start, O.table_gradient(g.double().numpy(), x.numpy(), offs, WS_H, C)
+
+
+def _backward_ws(_abi, gd, lay, xd, od, ge, C, dtype, n, jac, gi, ws, ws_bytes):
+    _abi.check(_abi.lib().naf_hash_encode_backward_ws(_abi.ptr(gd), _abi.ptr(xd), None, _abi.ptr(od), _abi.ptr(ge), n, 3, C, WS_L, WS_H, 1,
+                                                      _abi.ptr(jac), _abi.ptr(gi), _abi.dtype_code(DTYPES[dtype]), lay, WS_LOG2T,
+                                                      _abi.ptr(ws), ws_bytes, _abi.stream_ptr()))
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("layout", ["blc", "lbc"])
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("C", [2, 4])
+def test_workspace_route_with_input_gradients(C, dtype, layout):
+    """B = 8192, the floor of the binned scatter.  Its fixed-point reducer has an error model of its own: the table gradient is held
+    to the figures the suite already uses for this route (1e-5 of the largest sum for fp32 records, 3e-3 where the records carry
+    16-bit gradients), but against float64 instead of the atomic kernel.  grad_inputs comes from the same deterministic kernel on
+    both routes: equal bit for bit, and inside the input bound."""
+    _abi, _ = _mods()
+    x, offs = _ws_points()
+    g, emb, start, (s, a, n) = _ws_case(C, dtype)
+    rows = int(offs[-1])
+    dtc = _abi.dtype_code(DTYPES[dtype])
+    need = int(_abi.lib().naf_hash_encode_workspace_bytes(WS_B, 3, C, WS_L, WS_LOG2T, dtc))
+    assert need > 0
+    assert int(_abi.lib().naf_hash_encode_workspace_bytes(WS_B - 1, 3, C, WS_L, WS_LOG2T, dtc)) == 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    xd, od = x.cuda(), torch.from_numpy(offs).cuda()
+    _, jac = _forward(_abi, xd, emb.cuda(), od, 3, C, "blc", 1, WS_L, WS_H)
+    assert bool(torch.isfinite(jac.float()).all()) and float(jac.float().abs().max()) > 100.0
+    gd, lay = _layout(_abi, g, layout, WS_L)
+    what = f"ws C={C} {dtype} {layout}"
+
+    gi_atomic, ge_atomic = start.cuda(), _table(rows, C)
+    _backward(_abi, gd, lay, xd, od, ge_atomic, 3, C, dtype, WS_L, WS_H, calc=1, jac=jac, gi=gi_atomic)
+    _check_table(ge_atomic, rows, (s, a, n), what + " atomic route")
+
+    gi_ws, ge_ws = start.cuda(), _table(rows, C)
+    _backward_ws(_abi, gd, lay, xd, od, ge_ws, C, dtype, WS_B, jac, gi_ws, ws, need)
+    got = ge_ws.cpu()
+    assert torch.equal(got[rows:], torch.full_like(got[rows:], SENTINEL)), f"{what}: rows behind the table were written"
+    got = got[:rows].double().numpy() - PREFILL
+    assert np.array_equal(got[n == 0], np.zeros_like(got[n == 0])), f"{what}: a row no point touches has changed"
+    tol = 1e-5 if dtype == "fp32" else 3e-3
+    print(f"{what}: largest error {np.abs(got - s).max() / np.abs(s).max():.3e} of the largest sum (allowed {tol:.0e})")
+    np.testing.assert_allclose(got, s, rtol=0, atol=tol * np.abs(s).max())
+
+    assert torch.equal(gi_ws, gi_atomic), f"{what}: grad_inputs differs between the two routes"
+    si, ai = O.input_gradient(g.double().numpy().reshape(WS_B, WS_L, C), jac.cpu().double().numpy(), start.numpy())
+    err, bound = np.abs(gi_ws.cpu().double().numpy() - si), O.input_bound(start.numpy(), ai, WS_L, C)
+    print(f"{what}: worst input gradient uses {(err / bound).max():.3f} of the bound")
+    assert np.all(err <= bound)
+
+    # a workspace one byte too small, and one point fewer than the floor: the atomic route, inside its per-element bound
+    ge_small = _table(rows, C)
+    _backward_ws(_abi, gd, lay, xd, od, ge_small, C, dtype, WS_B, jac, start.cuda(), ws, need - 1)
+    _check_table(ge_small, rows, (s, a, n), what + " workspace one byte short")
+    g1 = g[:WS_B - 1].contiguous()
+    gd1, _ = _layout(_abi, g1, layout, WS_L)
+    ge_floor, gi_floor = _table(rows, C), start[:WS_B - 1].contiguous().cuda()
+    _backward_ws(_abi, gd1, lay, xd[:WS_B - 1].contiguous(), od, ge_floor, C, dtype, WS_B - 1, jac[:WS_B - 1].contiguous(), gi_floor, ws, need)
+    _check_table(ge_floor, rows, _ws_floor_ref(C, dtype), what + " B = 8191")
+    assert torch.equal(gi_floor, gi_atomic[:WS_B - 1])
+
+
+@functools.lru_cache(maxsize=None)
+def _ws_floor_ref(C, dtype):
+    x, offs = _ws_points()
+    g = _ws_case(C, dtype)[0]
+    return O.table_gradient(g[:WS_B - 1].double().numpy(), x[:WS_B - 1].numpy(), offs, WS_H, C)
