@@ -289,7 +289,9 @@ scatter_bin2_kernel(SrcRays src, const uint16_t *__restrict__ grad, const int32_
                         } else {
                             ra[k] = (pg[0] ^ h[k]) % m.size;
                             xm[k] = ra[k] ^ (((pg[0] + 1u) ^ h[k]) % m.size);
-                            formed[k] = (xm[k] & (xm[k] + 1u)) == 0u;
+                            // (xm == 0: both corners in ONE row -- 2^e - 1 apart before a modulo by 2^e - 1.  e = 0 marks a single, whose
+                            // second share the reducer drops: such a pair travels as two singles)
+                            formed[k] = xm[k] != 0u && (xm[k] & (xm[k] + 1u)) == 0u;
                         }
                     }
                 } else {
@@ -303,7 +305,7 @@ scatter_bin2_kernel(SrcRays src, const uint16_t *__restrict__ grad, const int32_
                         else if constexpr (MODE == kDenseMask) { ra[k] = raw[k] & (m.size - 1u); rb = (raw[k] + 1u) & (m.size - 1u); formed[k] = true; }
                         else { ra[k] = raw[k] % m.size; rb = (raw[k] + 1u) % m.size; }
                         xm[k] = ra[k] ^ rb;
-                        if constexpr (MODE == kDenseMod) formed[k] = (xm[k] & (xm[k] + 1u)) == 0u;
+                        if constexpr (MODE == kDenseMod) formed[k] = xm[k] != 0u && (xm[k] & (xm[k] + 1u)) == 0u;
                     }
                 }
             });

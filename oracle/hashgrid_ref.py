@@ -77,7 +77,8 @@ def corners(x01, level, offsets, base_resolution):
     scale, res = level_scale_res(level, base_resolution)
     T = int(offsets[level + 1]) - int(offsets[level])
     pos = _fma32(x01, scale, np.float32(0.5))
-    pg = np.floor(pos).astype(np.uint32)
+    # the reference's float -> uint32 conversion saturates (a negative position, from a coordinate nobody range-checked, gives cell 0)
+    pg = np.floor(np.maximum(pos, np.float32(0.0))).astype(np.uint32)
     frac = (pos - pg.astype(np.float32)).astype(np.float32)
     rows = np.empty((B, 1 << D), dtype=np.int64)
     w = np.empty((B, 1 << D), dtype=np.float32)

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import _hash_backward_oracle as O
+import _scatter_oracle as S
 
 pytestmark = pytest.mark.gpu
 
@@ -239,6 +240,14 @@ def test_workspace_route_with_input_gradients(C, dtype, layout):
     tol = 1e-5 if dtype == "fp32" else 3e-3
     print(f"{what}: largest error {np.abs(got - s).max() / np.abs(s).max():.3e} of the largest sum (allowed {tol:.0e})")
     np.testing.assert_allclose(got, s, rtol=0, atol=tol * np.abs(s).max())
+    # ... and every row to the bound of its record family (tests/_scatter_oracle.py): fp32 gradients travel as PairF32 records, 16-bit
+    # ones (fp16 too) as PairBF16; the fixed-point scale follows the largest gradient of the call
+    ref = dict(s=s, a=a, n=n, p=a, E=int(np.floor(np.log2(float(g.float().abs().max())))))
+    family = "f32" if dtype == "fp32" else "bf16"
+    err, bound = np.abs(got - s), S.bound(family, ref, np.full(s.shape, PREFILL, dtype=np.float32))
+    hit = n > 0
+    print(f"{what}: worst element uses {(err[hit] / bound[hit]).max():.3f} of the {family} record bound")
+    assert np.all(err[hit] <= bound[hit]), f"{what}: {int((err[hit] > bound[hit]).sum())} elements outside the record bound"
 
     assert torch.equal(gi_ws, gi_atomic), f"{what}: grad_inputs differs between the two routes"
     si, ai = O.input_gradient(g.double().numpy().reshape(WS_B, WS_L, C), jac.cpu().double().numpy(), start.numpy())
@@ -263,3 +272,50 @@ def _ws_floor_ref(C, dtype):
     x, offs = _ws_points()
     g = _ws_case(C, dtype)[0]
     return O.table_gradient(g[:WS_B - 1].double().numpy(), x[:WS_B - 1].numpy(), offs, WS_H, C)
+
+
+@functools.lru_cache(maxsize=None)
+def _outside_case(C, dtype):
+    """Samples of rays that leave [0, 1]^3 on both sides (no clamp), by at most a few cells of level 0: below 0 the reference's cell
+    index saturates at 0 and its weights leave [0, 1] (hashgrid_ref.corners restates that), above 1 the dense levels wrap."""
+    g0 = torch.Generator().manual_seed(23)
+    n_rays, S = 64, 128
+    o = torch.rand(n_rays, 1, 3, generator=g0)
+    d = (torch.rand(n_rays, 1, 3, generator=g0) - 0.5) * 1.5
+    x = (o + d * torch.linspace(0, 1.0, S).view(1, S, 1)).clamp(-0.125, 1.125).reshape(-1, 3).contiguous()
+    below, above = int((x < 0).any(1).sum()), int((x > 1).any(1).sum())
+    assert x.shape[0] == WS_B and below > 100 and above > 100, (below, above)
+    _, offs = _ws_points()
+    g = torch.randn(WS_B, WS_L * C, generator=g0).to(DTYPES[dtype])
+    return x, offs, g, O.table_gradient(g.double().numpy(), x.numpy(), offs, WS_H, C)
+
+
+@pytest.mark.parametrize("C,dtype,layout", [(2, "fp32", "blc"), (2, "bf16", "lbc"), (4, "fp16", "blc"), (4, "fp32", "lbc")])
+def test_workspace_route_with_points_outside_the_unit_cube(C, dtype, layout):
+    """A point outside [0, 1] emits no record: the binned scatter sends its contributions to the table with fp32 atomics, the
+    reference's way (their weights are not bounded by 1, which the fixed-point scale assumes).  Every row, whichever way its
+    contributions came, is held to its record family's bound around the float64 sum."""
+    _abi, _ = _mods()
+    x, offs, g, (s, a, n) = _outside_case(C, dtype)
+    rows = int(offs[-1])
+    dtc = _abi.dtype_code(DTYPES[dtype])
+    need = int(_abi.lib().naf_hash_encode_workspace_bytes(WS_B, 3, C, WS_L, WS_LOG2T, dtc))
+    assert need > 0
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    xd, od = x.cuda(), torch.from_numpy(offs).cuda()
+    gd, lay = _layout(_abi, g, layout, WS_L)
+    ge = _table(rows, C)
+    _abi.check(_abi.lib().naf_hash_encode_backward_ws(_abi.ptr(gd), _abi.ptr(xd), None, _abi.ptr(od), _abi.ptr(ge), WS_B, 3, C, WS_L, WS_H, 0,
+                                                      None, None, dtc, lay, WS_LOG2T, _abi.ptr(ws), need, _abi.stream_ptr()))
+    torch.cuda.synchronize()
+    what = f"ws outside C={C} {dtype} {layout}"
+    got = ge.cpu()
+    assert torch.equal(got[rows:], torch.full_like(got[rows:], SENTINEL)), f"{what}: rows behind the table were written"
+    got = got[:rows].double().numpy() - PREFILL
+    assert np.array_equal(got[n == 0], np.zeros_like(got[n == 0])), f"{what}: a row no point touches has changed"
+    ref = dict(s=s, a=a, n=n, p=a, E=int(np.floor(np.log2(float(g.float().abs().max())))))
+    family = "f32" if dtype == "fp32" else "bf16"
+    err, bound = np.abs(got - s), S.bound(family, ref, np.full(s.shape, PREFILL, dtype=np.float32))
+    hit = n > 0
+    print(f"{what}: worst element uses {(err[hit] / bound[hit]).max():.3f} of the {family} record bound; largest |w g| sum {a.max():.3e}")
+    assert np.all(err[hit] <= bound[hit]), f"{what}: {int((err[hit] > bound[hit]).sum())} elements outside the record bound"
