@@ -620,6 +620,34 @@ int naf_tv_gradient(const float *x, uint32_t n1, uint32_t n2, uint32_t n3, float
 int naf_tv_descent(float *x, float *scratch, uint32_t n1, uint32_t n2, uint32_t n3, float step, uint32_t n_steps, float eps,
                    double *stats, void *workspace, size_t workspace_bytes, void *stream);
 
+/* V3  the proximal map of the exact isotropic total variation (no eps), optionally with x >= 0: the regulariser step of the FISTA-TV
+ * baseline (reconstruct.fista_tv) and a denoiser on its own (tv.tv_prox).  DESIGN.md section 18.
+ *   b  f32 [n1, n2, n3] C-contiguous, every extent >= 1;  p, r, r_next  f32 [3, n1, n2, n3] (the dual variable, one plane per axis)
+ *   D_a f[v]   = f[v] - f[v - e_a] if v_a > 0, else 0                                   (the differences of V2)
+ *   TV(f)      = sum_v sqrt((D_0 f[v])^2 + (D_1 f[v])^2 + (D_2 f[v])^2)
+ *   (D^T p)[v] = sum_a ( [v_a > 0] p_a[v] - [v_a < n_a - 1] p_a[v + e_a] )
+ *   P_C(t)     = t, or with `nonneg`  t < 0 ? 0 : t  (a NaN stays NaN)
+ *   prox_{lambda TV + C}(b) = P_C(b - lambda D^T p*), p* the limit of the fast gradient projection of Beck and Teboulle (2009).
+ * The masks are applied on every read: whatever lies in p_a[v] (or r_a[v]) at v_a = 0 has no effect, and the step writes 0 there.
+ * An axis of extent 1 contributes nothing.
+ * naf_tv_prox_step is one iteration of that method at the extrapolated point r, with p = p_{k-1} on entry and p_k on return:
+ *   u         = P_C(b - lambda D^T r)
+ *   q_a[v]    = r_a[v] + (1 / (12 lambda)) D_a u[v]                                     (12 >= ||D D^T|| in 3-D)
+ *   p_k[v]    = q[v] / max(1, sqrt(q_0^2 + q_1^2 + q_2^2))
+ *   r_next[v] = p_k[v] + momentum (p_k[v] - p_{k-1}[v])
+ * `p` is updated in place (its update is point-wise); `r` is read at neighbours, so `r_next` must be another buffer than `r`; it
+ * may be NULL (the last iteration needs none).  lambda must be finite and > 0, momentum finite and >= 0: the caller forms
+ * t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2 and momentum = (t_k - 1) / t_{k+1} in double and rounds once.
+ * naf_tv_prox_primal writes x = P_C(b - lambda D^T p); x may be b itself; lambda must be finite and >= 0.
+ * All arithmetic is fp32, one IEEE operation at a time without contraction, in the order of csrc/tvprox_device.h (the three terms
+ * of D^T and the three squares added in axis order, true divisions).  No reduction and no atomic: two calls return the same bits.
+ * A zero extent is NAF_ERR_UNSUPPORTED; any overlap of buffers other than those named above is the caller's error.  No workspace,
+ * no allocation and no host synchronisation inside the calls; all offsets are 64-bit. */
+int naf_tv_prox_step(const float *b, const float *r, float *p, float *r_next, uint32_t n1, uint32_t n2, uint32_t n3, float lambda,
+                     float momentum, int nonneg, void *stream);
+int naf_tv_prox_primal(const float *b, const float *p, float *x, uint32_t n1, uint32_t n2, uint32_t n3, float lambda, int nonneg,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

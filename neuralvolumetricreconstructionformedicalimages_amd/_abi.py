@@ -161,6 +161,8 @@ SIGNATURES = {
     "naf_tv_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32]),
     "naf_tv_gradient": (_i32, [_vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "naf_tv_descent": (_i32, [_vp, _vp, _u32, _u32, _u32, _f32, _u32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
+    "naf_tv_prox_step": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _i32, _vp]),
+    "naf_tv_prox_primal": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _i32, _vp]),
 }
 
 

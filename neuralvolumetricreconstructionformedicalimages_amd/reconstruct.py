@@ -1,8 +1,9 @@
 """Classical reconstruction from the same projections, voxel grid and metrics a NAF is trained and scored on: SIRT and ASD-POCS
 over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`), filtered
-back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that same A^T, and OS-SART over the subset kernels of
-`sart` (the same A and A^T restricted to a list of views).  They are the baselines the reference took from TIGRE, which has no
-ROCm build.  DESIGN.md sections 13, 14, 15 and 16.
+back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that same A^T, OS-SART over the subset kernels of
+`sart` (the same A and A^T restricted to a list of views), and FISTA on the TV-penalised least-squares objective over those
+kernels and the TV proximal map (`tv.tv_prox`).  They are the baselines the reference took from TIGRE, which has no ROCm build.
+DESIGN.md sections 13 to 18.
 
 SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the element-wise product):
 
@@ -29,8 +30,8 @@ HIP kernels (include/naf_hip.h P4), where the row sum of a ray is its length ins
 weights sum to 1), so R is never stored, and where each C_s is kept after the subset's first visit if all of them fit
 `weight_cache_bytes`.
 
-ASD-POCS (Sidky and Pan 2008, as TIGRE runs it, with one SIRT update as the data step and no early stop) follows every data step
-with `tv_steps` normalised steepest-descent steps on the volume's total variation (`tv.tv_descent`, include/naf_hip.h V2):
+ASD-POCS (Sidky and Pan 2008, as TIGRE runs it, with one SIRT update as the data step and no early stop) is the heuristic of the two
+TV-regularised baselines: it has no stated objective, and its result depends on its schedule.  It follows every data step with `tv_steps` normalised steepest-descent steps on the volume's total variation (`tv.tv_descent`, include/naf_hip.h V2):
 
     beta = relax.  For k in range(n_iter):
         x_prev = x;  x <- x + beta * C ⊙ A^T (R ⊙ (b - A x));  x <- max(x, 0) if `nonneg`;  beta *= relax_red
@@ -39,6 +40,24 @@ with `tv_steps` normalised steepest-descent steps on the volume's total variatio
         x_data = x;  x <- tv_descent(x, dtvg, tv_steps)          (tv_steps steps of length dtvg each)
         dg = ||x - x_data||_2
         if dg > rmax * dp and dd > 0: dtvg *= alpha_red
+
+FISTA-TV (Beck and Teboulle 2009) is the convergent one.  It minimises
+
+    F(x) = 1/2 ||A x - b||_R^2 + lam * TV(x)   over x >= 0 (if `nonneg`),     ||d||_R^2 = sum_r R_r d_r^2,  R = 1 / (A 1) as above,
+
+with TV the exact isotropic total variation of include/naf_hip.h V3 (no eps).  Its one weight is `lam`; F can be printed, and its
+minimiser does not depend on a schedule.  A^T is the exact transpose of A and A has no negative entry, so A^T R A is symmetric with
+row sums (A^T R A 1)[v] = (A^T 1)[v] and L = max_v (A^T 1)[v] >= ||A^T R A||_2: a rigorous step bound without a power iteration.
+
+    y_0 = x_0, t_0 = 1.  For k in range(n_iter):
+        res = b - A y_k;   norm_k = ||res||_R
+        z = y_k + A^T (R ⊙ res) / L
+        x_{k+1} = prox_{(lam / L) TV + C}(z)                       (`tv.tv_prox`: `tv_iters` dual iterations, warm-started)
+        t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2;   y_{k+1} = x_{k+1} + ((t_k - 1) / t_{k+1}) (x_{k+1} - x_k)
+
+The norm reported for iteration k is taken at the extrapolated point y_k, not at x_k: it is the residual the step needs anyway
+and costs no extra projection (y_0 = x_0, and y_k - x_k -> 0 as the iteration converges).  `fista_tv_operators` is the array code;
+`fista_tv` runs the same iteration with `sart.residual_scan` (R ⊙ res in one launch) and `sart.backproject_scan` over all views.
 
 FDK (Feldkamp, Davis and Kress, in the form of Kak and Slaney ch. 3, the row spacing taken at the isocentre).  Detector pixel
 (u, v), u along the last axis of [N, H, W] (pitch du = dDetector[0], perpendicular to the rotation axis), v along the rows (dv);
@@ -60,7 +79,7 @@ No short-scan (Parker) weights: a cone scan that covers less than a full turn is
 (laminographic) scan is refused: its constant and filter direction are not verified here.
 
 The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
-arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart`, are HIP kernels.
+arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart` and `fista_tv`, are HIP kernels.
 """
 from __future__ import annotations
 
@@ -346,6 +365,101 @@ def asd_pocs(projections, geo, angles, n_iter=50, relax=1.0, relax_red=0.99, alp
 
     return asd_pocs_operators(A, AT, projections, n_iter, descend, relax=relax, relax_red=relax_red, alpha=alpha, alpha_red=alpha_red,
                               rmax=rmax, tv_steps=tv_steps, nonneg=nonneg, x0=x0, callback=callback)
+
+
+def _check_fista_tv(n_iter, lam):
+    n_iter, lam = int(n_iter), float(lam)
+    if n_iter < 0:
+        raise ValueError(f"fista_tv: n_iter must be >= 0, got {n_iter}")
+    if not math.isfinite(lam) or lam < 0.0:
+        raise ValueError(f"fista_tv: lam must be >= 0 and finite, got {lam}")
+    return n_iter, lam
+
+
+def _next_t(t):
+    return (1.0 + math.sqrt(1.0 + 4.0 * t * t)) / 2.0
+
+
+def fista_tv_operators(A, AT, b, n_iter, prox, lam, nonneg=True, x0=None, callback=None):
+    """FISTA on F(x) = 1/2 ||A x - b||_R^2 + lam TV(x) (x >= 0 if `nonneg`) over `A`, `AT` (as in `sirt_operators`) and
+    `prox(z, t, nonneg)`, a callable that returns prox_{t TV}(z), restricted to x >= 0 if `nonneg`, and leaves z as it is.  See the
+    module docstring for the iteration.  `callback(k, x, residual_norm)` runs after every iteration.  Returns (x, norms) with
+    norms[k] = ||b - A y_k||_R taken at the extrapolated point y_k (y_0 = x0), which costs no extra projection; it is not the
+    residual of the returned iterates x_k."""
+    n_iter, lam = _check_fista_tv(n_iter, lam)
+    xp, _ = _namespace(b)
+    R, _, x = _weights_and_start(A, AT, b, x0, xp)
+    L = float(AT(xp.ones_like(b)).max())                        # max (A^T 1) >= ||A^T R A||_2
+    if not L > 0.0:
+        raise ValueError(f"fista_tv: max(A^T 1) must be > 0, got {L}: no ray meets the volume")
+    y, t, norms = x, 1.0, []
+    for k in range(n_iter):
+        res = b - A(y)
+        norms.append(math.sqrt(float((R * res * res).sum(dtype=xp.float64))))
+        x_next = prox(y + AT(R * res) / L, lam / L, nonneg)
+        t_next = _next_t(t)
+        y = x_next + ((t - 1.0) / t_next) * (x_next - x)
+        x, t = x_next, t_next
+        if callback is not None:
+            callback(k, x, norms[-1])
+    return x, norms
+
+
+DEFAULT_FISTA_TV_LAMBDA = 1e-4          # DESIGN.md section 18's sweep on the synthetic chest scan
+
+
+def fista_tv(projections, geo, angles, n_iter=30, lam=DEFAULT_FISTA_TV_LAMBDA, tv_iters=20, nonneg=True, x0=None, callback=None,
+             deterministic=False):
+    """FISTA-TV reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
+    (float32 volume of geo.nVoxel on the projections' device, residual norms at the extrapolated points).  The iteration of
+    `fista_tv_operators` on the kernels: per iteration one `sart.residual_scan` and one `sart.backproject_scan` over all views
+    (the first also returns A^T 1, whose maximum is L) and `tv.tv_prox` with `tv_iters` dual iterations, the dual carried from one
+    iteration to the next as a warm start.  `lam` is the weight of TV in F (the module docstring; the default is DESIGN.md section
+    18's).  `callback(k, x, residual_norm)` reads the norm back, which otherwise happens once at the end.
+    `deterministic=True` takes the atomic-free transpose: two runs return the same bits and the same norms."""
+    import torch
+
+    from . import _abi, projector, sart, tv
+    n_iter, lam = _check_fista_tv(n_iter, lam)
+    tv_iters = int(tv_iters)
+    if tv_iters < 0:
+        raise ValueError(f"fista_tv: tv_iters must be >= 0, got {tv_iters}")
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError("fista_tv: projections must be a CUDA/HIP tensor (no CPU path)")
+    scan = sart.Scan(geo, angles, projections.device)
+    if x0 is None:
+        x = torch.zeros(scan.dims, device=projections.device, dtype=torch.float32)
+    else:
+        _abi.check_volume(x0, "fista_tv", "x0")
+        projector.check_geometry(x0, geo)
+        x = x0.clone()
+    transpose = {"method": _method(deterministic), "scan": scan}
+    if deterministic:
+        transpose["workspace"] = projector.gather_workspace(scan.N, scan.H, scan.W, projections.device)
+    yw = torch.empty(scan.N, scan.H, scan.W, device=x.device, dtype=torch.float32)
+    res = torch.empty_like(yw)
+    num = torch.zeros_like(x)
+    dual = torch.zeros((3, *scan.dims), device=x.device, dtype=torch.float32)
+    y, t, L, norms = x, 1.0, None, []
+    for k in range(n_iter):
+        sart.residual_scan(y, projections, geo, angles, None, y=yw, r=res, scan=scan)             # yw = R ⊙ res
+        norms.append((yw.double() * res.double()).sum())
+        if L is None:
+            den = torch.zeros_like(x)
+            sart.backproject_scan(yw, geo, angles, None, num=num, den=den, **transpose)
+            L = float(den.max())
+            del den
+            if not L > 0.0:
+                raise ValueError(f"fista_tv: max(A^T 1) must be > 0, got {L}: no ray meets the volume")
+        else:
+            sart.backproject_scan(yw, geo, angles, None, num=num.zero_(), **transpose)
+        x_next, dual = tv.tv_prox(torch.add(y, num, alpha=1.0 / L), lam / L, tv_iters, nonneg, dual=dual, return_dual=True)
+        t_next = _next_t(t)
+        y = torch.add(x_next, x_next - x, alpha=(t - 1.0) / t_next)
+        x, t = x_next, t_next
+        if callback is not None:
+            callback(k, x, math.sqrt(float(norms[-1])))
+    return x, [math.sqrt(float(v)) for v in norms]
 
 
 def fdk_weights(geo, angles, filter="ram-lak"):

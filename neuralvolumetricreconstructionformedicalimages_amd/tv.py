@@ -1,9 +1,12 @@
-"""3-D total variation on the device: its value and gradient (`naf_tv_gradient`) and normalised steepest descent on it
-(`naf_tv_descent`), the regulariser step of the ASD-POCS baseline (`reconstruct.asd_pocs`), through libnaf_hip.so.
+"""3-D total variation on the device: its value and gradient (`naf_tv_gradient`), normalised steepest descent on it
+(`naf_tv_descent`), the regulariser step of the ASD-POCS baseline (`reconstruct.asd_pocs`), and its proximal map (`naf_tv_prox_step`,
+`naf_tv_prox_primal`), the regulariser step of the FISTA-TV baseline (`reconstruct.fista_tv`), through libnaf_hip.so.
 
 The definition is written down in include/naf_hip.h (V2) and DESIGN.md section 14: backward differences, m = sqrt(eps + |D f|^2),
 TV = sum m, g = the exact gradient of that sum.  A descent step reads the volume twice and writes it once; the gradient is never
-stored, and the whole run of steps is queued without returning to the host.  There is no CPU path, like the rest of the hot path.
+stored, and the whole run of steps is queued without returning to the host.  The proximal map is that of the exact isotropic TV
+(no eps), include/naf_hip.h (V3) and DESIGN.md section 18: one launch per dual iteration of the fast gradient projection, the
+momentum sequence formed on the host.  There is no CPU path, like the rest of the hot path.
 """
 from __future__ import annotations
 
@@ -99,3 +102,62 @@ def tv_descent(x, step, n_steps=20, eps=DEFAULT_EPS, scratch=None):
                                       ws.numel(), _abi.stream_ptr()), "tv_descent")
         tv, g2 = (float(v) for v in stats.tolist())
         return tv, math.sqrt(g2) if g2 >= 0 else math.nan
+
+
+def prox_momenta(n_iter):
+    """The momentum c_k = (t_k - 1) / t_{k+1} of each of `n_iter` dual iterations, t_1 = 1, t_{k+1} = (1 + sqrt(1 + 4 t_k^2)) / 2,
+    in float64 (the kernel argument is rounded to fp32 once)."""
+    t, out = 1.0, []
+    for _ in range(int(n_iter)):
+        t_next = (1.0 + math.sqrt(1.0 + 4.0 * t * t)) / 2.0
+        out.append((t - 1.0) / t_next)
+        t = t_next
+    return out
+
+
+def tv_prox(b, lam, n_iter=50, nonneg=False, dual=None, return_dual=False):
+    """prox_{lam TV + C}(b) = argmin_x 1/2 ||x - b||^2 + lam TV(x) (over x >= 0 with `nonneg`) of a CUDA float32 volume
+    [n1, n2, n3], TV the exact isotropic total variation -> a new tensor of b's shape; (x, dual) with `return_dual`.  `n_iter`
+    iterations of the fast gradient projection on the dual variable [3, n1, n2, n3], from zeros or from `dual` (a warm start: the
+    dual a previous call returned).  With `return_dual` a given `dual` is advanced in place and is the tensor returned; without,
+    it is copied and left as it is.  `n_iter` step launches and one primal launch are queued, nothing is
+    read back; `lam == 0` or `n_iter == 0` launches the primal only."""
+    who = "tv_prox"
+    _abi.check_volume(b, who, "b")
+    if isinstance(lam, torch.Tensor) or not isinstance(lam, (int, float)) or isinstance(lam, bool):
+        raise TypeError(f"{who}: lam must be a Python float, got {type(lam).__name__}")
+    lam = float(lam)
+    if not math.isfinite(lam) or lam < 0.0:
+        raise ValueError(f"{who}: lam must be >= 0 and finite, got {lam}")
+    n_iter = int(n_iter)
+    if n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be >= 0, got {n_iter}")
+    if min(b.shape) < 1:
+        raise ValueError(f"{who}: every extent of b must be at least 1, got shape {tuple(b.shape)}")
+    if dual is not None:
+        if not isinstance(dual, torch.Tensor) or not dual.is_cuda:
+            raise RuntimeError(f"{who}: dual must be a CUDA/HIP tensor (no CPU path)")
+        if dual.dtype != torch.float32:
+            raise TypeError(f"{who}: dual must be float32, got {dual.dtype}")
+        if tuple(dual.shape) != (3, *b.shape) or dual.device != b.device:
+            raise ValueError(f"{who}: dual must be {(3, *b.shape)} on {b.device}, got {tuple(dual.shape)} on {dual.device}")
+        if not dual.is_contiguous():
+            raise ValueError(f"{who}: dual must be contiguous")
+        if _overlap(dual, b):
+            raise ValueError(f"{who}: dual must not overlap b")
+    lib = _abi.lib()
+    dims = tuple(int(v) for v in b.shape)
+    flag = int(bool(nonneg))
+    with torch.cuda.device(b.device):
+        p = torch.zeros((3, *dims), dtype=torch.float32, device=b.device) if dual is None else (dual if return_dual else dual.clone())
+        if lam > 0.0 and n_iter > 0:
+            # r_1 = p_0; the extrapolated point alternates between two buffers, because a step reads it at neighbours
+            r, r_next = p.clone(), (torch.empty_like(p) if n_iter > 1 else None)
+            for k, c in enumerate(prox_momenta(n_iter)):
+                last = k == n_iter - 1
+                _abi.check(lib.naf_tv_prox_step(_abi.ptr(b), _abi.ptr(r), _abi.ptr(p), None if last else _abi.ptr(r_next), *dims, lam,
+                                                c, flag, _abi.stream_ptr()), "tv_prox_step")
+                r, r_next = r_next, r
+        x = torch.empty_like(b)
+        _abi.check(lib.naf_tv_prox_primal(_abi.ptr(b), _abi.ptr(p), _abi.ptr(x), *dims, lam, flag, _abi.stream_ptr()), "tv_prox_primal")
+    return (x, p) if return_dual else x

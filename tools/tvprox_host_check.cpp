@@ -1,0 +1,117 @@
+// tvprox_host_check.cpp -- runs the per-voxel arithmetic of csrc/tvprox_device.h on the CPU, so that it can be compared with the
+// float64 oracle and run under AddressSanitizer / UBSan (tools/tvprox_host_check.py builds and drives it).
+// The neighbours and the edge flags of every voxel are gathered here by a plain loop over flat indices: the kernel's LDS staging,
+// halo and chunking in csrc/tvprox.hip are not compiled into this program, and only the GPU tests cover them.  No GPU, no HIP.
+//
+//   tvprox_host_check step   n1 n2 n3 lambda momentum nonneg b.f32 r.f32 p_old.f32 p.f32 r_next.f32    one dual iteration
+//   tvprox_host_check primal n1 n2 n3 lambda nonneg b.f32 p.f32 x.f32                                  x = P_C(b - lambda D^T p)
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../neuralvolumetricreconstructionformedicalimages_amd/csrc/tvprox_device.h"
+
+namespace {
+
+struct Dims {
+    uint32_t n[3];
+    uint64_t stride[3], volume;
+};
+
+// u[v] = P_C(b[v] - lambda (D^T p)[v]) for every voxel, in volume order.
+void primal(const Dims &d, const std::vector<float> &b, const std::vector<float> &p, float lambda, bool nonneg, std::vector<float> &u) {
+    for (uint32_t x = 0; x < d.n[0]; ++x)
+        for (uint32_t y = 0; y < d.n[1]; ++y)
+            for (uint32_t z = 0; z < d.n[2]; ++z) {
+                const uint32_t v[3] = {x, y, z};
+                const uint64_t at = x * d.stride[0] + y * d.stride[1] + z;
+                float lo[3], hi[3];
+                bool has_lo[3], has_hi[3];
+                for (int a = 0; a < 3; ++a) {
+                    has_lo[a] = v[a] > 0;
+                    has_hi[a] = v[a] + 1 < d.n[a];
+                    lo[a] = p.at(a * d.volume + at);                     // read whatever is there: the select must drop it
+                    hi[a] = has_hi[a] ? p.at(a * d.volume + at + d.stride[a]) : 0.0f;
+                }
+                u.at(at) = naf::tvprox_primal(b.at(at), naf::tvprox_adjoint(lo, hi, has_lo, has_hi), lambda, nonneg);
+            }
+}
+
+void step(const Dims &d, const std::vector<float> &b, const std::vector<float> &r, std::vector<float> &p, float lambda, float momentum,
+          bool nonneg, std::vector<float> &r_next) {
+    std::vector<float> u(d.volume);
+    primal(d, b, r, lambda, nonneg, u);
+    const float dual_step = naf::tvprox_dual_step(lambda);
+    for (uint32_t x = 0; x < d.n[0]; ++x)
+        for (uint32_t y = 0; y < d.n[1]; ++y)
+            for (uint32_t z = 0; z < d.n[2]; ++z) {
+                const uint32_t v[3] = {x, y, z};
+                const uint64_t at = x * d.stride[0] + y * d.stride[1] + z;
+                float u_lo[3], rr[3], p_old[3], p_new[3], rn[3];
+                bool has_lo[3];
+                for (int a = 0; a < 3; ++a) {
+                    has_lo[a] = v[a] > 0;
+                    u_lo[a] = has_lo[a] ? u.at(at - d.stride[a]) : 0.0f;
+                    rr[a] = r.at(a * d.volume + at);
+                    p_old[a] = p.at(a * d.volume + at);
+                }
+                naf::tvprox_dual(u.at(at), u_lo, rr, p_old, has_lo, dual_step, momentum, p_new, rn);
+                for (int a = 0; a < 3; ++a) {
+                    p.at(a * d.volume + at) = p_new[a];
+                    r_next.at(a * d.volume + at) = rn[a];
+                }
+            }
+}
+
+bool read_all(const char *path, std::vector<float> &v) {
+    FILE *fp = std::fopen(path, "rb");
+    if (!fp) return false;
+    const size_t got = std::fread(v.data(), sizeof(float), v.size(), fp);
+    std::fclose(fp);
+    return got == v.size();
+}
+
+bool write_all(const char *path, const std::vector<float> &v) {
+    FILE *fp = std::fopen(path, "wb");
+    if (!fp) return false;
+    const size_t put = std::fwrite(v.data(), sizeof(float), v.size(), fp);
+    return std::fclose(fp) == 0 && put == v.size();
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    const bool is_step = argc == 13 && !std::strcmp(argv[1], "step");
+    const bool is_primal = argc == 10 && !std::strcmp(argv[1], "primal");
+    if (!is_step && !is_primal) {
+        std::fprintf(stderr, "usage: %s step n1 n2 n3 lambda momentum nonneg b r p_old p r_next | primal n1 n2 n3 lambda nonneg b p x\n",
+                     argv[0]);
+        return 2;
+    }
+    Dims d;
+    for (int a = 0; a < 3; ++a) d.n[a] = (uint32_t)std::atoi(argv[2 + a]);
+    if (d.n[0] == 0 || d.n[1] == 0 || d.n[2] == 0) return 2;
+    d.stride[0] = (uint64_t)d.n[1] * d.n[2];
+    d.stride[1] = d.n[2];
+    d.stride[2] = 1;
+    d.volume = d.stride[0] * d.n[0];
+    const float lambda = (float)std::atof(argv[5]);
+    std::vector<float> b(d.volume), p(3 * d.volume);
+    if (is_step) {
+        const float momentum = (float)std::atof(argv[6]);
+        const bool nonneg = std::atoi(argv[7]) != 0;
+        std::vector<float> r(3 * d.volume), r_next(3 * d.volume);
+        if (!read_all(argv[8], b) || !read_all(argv[9], r) || !read_all(argv[10], p)) return 3;
+        step(d, b, r, p, lambda, momentum, nonneg, r_next);
+        if (!write_all(argv[11], p) || !write_all(argv[12], r_next)) return 3;
+    } else {
+        const bool nonneg = std::atoi(argv[6]) != 0;
+        std::vector<float> x(d.volume);
+        if (!read_all(argv[7], b) || !read_all(argv[8], p)) return 3;
+        primal(d, b, p, lambda, nonneg, x);
+        if (!write_all(argv[9], x)) return 3;
+    }
+    return 0;
+}
