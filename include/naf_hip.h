@@ -648,6 +648,45 @@ int naf_tv_prox_step(const float *b, const float *r, float *p, float *r_next, ui
 int naf_tv_prox_primal(const float *b, const float *p, float *x, uint32_t n1, uint32_t n2, uint32_t n3, float lambda, int nonneg,
                        void *stream);
 
+/* K1  the vector half of CGLS, conjugate gradients on A^T W A x = A^T W b with one weight w_r >= 0 per ray: the Krylov baseline
+ * reconstruct.cgls.  DESIGN.md section 19.  A and A^T are P1 and P2 / P5; these three entry points are everything else of an
+ * iteration, and they keep its scalars on the device, so a solve is one stream of launches without a host read-back:
+ *   q = A p;                     naf_cgls_wdot(q, w, .., NAF_CGLS_SLOT_DELTA)          delta  = sum w q^2
+ *                                naf_cgls_residual_step(r, q, w, y, .., k)             history[k] = sum w r^2;  r -= alpha q;  y = w r
+ *   s = A^T y;                   naf_cgls_wdot(s, NULL, .., (k + 1) & 1)               gamma' = sum s^2
+ *                                naf_cgls_direction_step(x, p, s, .., k)               x += alpha p;  p = s + beta p
+ * with alpha = gamma / delta and beta = gamma' / gamma, divided in fp64 and rounded to fp32 once.
+ * `workspace`: naf_cgls_workspace_bytes(n_max, n_iter_max) bytes, 8-byte aligned, for arrays of up to n_max elements and n_iter_max
+ * iterations; the same n_iter_max is passed to every call.  It starts with the scalars, fp64:
+ *   [0], [1]  gamma: iteration k reads gamma from slot k & 1 and gamma' from slot (k + 1) & 1, so "gamma <- gamma'" is the parity
+ *   [2]       delta                                           (NAF_CGLS_SLOT_DELTA)
+ *   [3]       the stop mark: 0 while running, k + 1 once iteration k was a breakdown (NAF_CGLS_SLOT_STOPPED); sticky
+ *   [4 .. 7]  reserved, 0
+ *   [NAF_CGLS_SCALARS + k]  history: sum w r^2 of the r that iteration k was given, k < n_iter_max
+ * followed by the per-workgroup partial sums.  A workspace of zero bytes is a fresh solve (hipMemsetAsync).
+ * Iteration k is live if the stop mark is 0 and gamma > 0 and delta > 0 (a NaN in either is not > 0).  If it is not, the residual
+ * step sets the stop mark to k + 1 where it is still 0, and both steps leave r, x and p exactly as they are (y = w r is still
+ * written, and the history slot too): once stopped, stay stopped, and no NaN or Inf is formed from gamma / 0.
+ * naf_cgls_wdot: scalars[slot] <- sum_i w_i a_i^2, slot 0, 1 or 2 (w == NULL: sum a_i^2).  Each term is (double)a * (double)a, which
+ * is exact, times (double)w; every workgroup adds its terms in a fixed order into one fp64 partial, and one workgroup adds the
+ * partials in a fixed order: no atomics, two calls return the same bits, whatever the alignment of the pointers.  A NaN propagates.
+ * naf_cgls_residual_step: r <- fma(-alpha, q, r), y <- w * r (y <- r for w == NULL), and sum w r^2 of the r that came in, by the
+ * path of naf_cgls_wdot, into history slot k.  y must not be q or r; k < n_iter_max.
+ * naf_cgls_direction_step: x <- fma(alpha, p, x), p <- fma(beta, p, s) in one pass that reads three arrays and writes two.
+ * No launch rewrites a scalar that a workgroup of the same launch reads: the scalars are written by the single-workgroup reduce
+ * that follows each pass.  All element offsets are 64-bit; n == 0 returns NAF_OK without examining the pointers; pointers are
+ * 4-byte aligned (16-byte aligned ones take the float4 path, with the same bits).  No allocation, no host synchronisation. */
+#define NAF_CGLS_SLOT_DELTA 2u
+#define NAF_CGLS_SLOT_STOPPED 3u
+#define NAF_CGLS_SCALARS 8u
+size_t naf_cgls_workspace_bytes(uint64_t n_max, uint32_t n_iter_max);
+int naf_cgls_wdot(const float *a, const float *w, uint64_t n, uint32_t slot, uint32_t n_iter_max, void *workspace,
+                  size_t workspace_bytes, void *stream);
+int naf_cgls_residual_step(float *r, const float *q, const float *w, float *y, uint64_t n, uint32_t k, uint32_t n_iter_max,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int naf_cgls_direction_step(float *x, float *p, const float *s, uint64_t n, uint32_t k, uint32_t n_iter_max, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

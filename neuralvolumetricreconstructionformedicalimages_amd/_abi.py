@@ -163,6 +163,10 @@ SIGNATURES = {
     "naf_tv_descent": (_i32, [_vp, _vp, _u32, _u32, _u32, _f32, _u32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
     "naf_tv_prox_step": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _i32, _vp]),
     "naf_tv_prox_primal": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _i32, _vp]),
+    "naf_cgls_workspace_bytes": (ctypes.c_size_t, [_u64, _u32]),
+    "naf_cgls_wdot": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
+    "naf_cgls_residual_step": (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
+    "naf_cgls_direction_step": (_i32, [_vp, _vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
 }
 
 

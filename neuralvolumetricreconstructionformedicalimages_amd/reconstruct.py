@@ -1,9 +1,9 @@
 """Classical reconstruction from the same projections, voxel grid and metrics a NAF is trained and scored on: SIRT and ASD-POCS
 over the forward projector A (`projector.project_scan`) and its transpose A^T (`projector.backproject_scan`), filtered
 back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that same A^T, OS-SART over the subset kernels of
-`sart` (the same A and A^T restricted to a list of views), and FISTA on the TV-penalised least-squares objective over those
-kernels and the TV proximal map (`tv.tv_prox`).  They are the baselines the reference took from TIGRE, which has no ROCm build.
-DESIGN.md sections 13 to 18.
+`sart` (the same A and A^T restricted to a list of views), FISTA on the TV-penalised least-squares objective over those
+kernels and the TV proximal map (`tv.tv_prox`), and CGLS with per-ray weights over the same pair and the vector kernels of `cgls_kernels`.
+They are the baselines the reference took from TIGRE, which has no ROCm build.  DESIGN.md sections 13 to 19.
 
 SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the element-wise product):
 
@@ -59,6 +59,25 @@ The norm reported for iteration k is taken at the extrapolated point y_k, not at
 and costs no extra projection (y_0 = x_0, and y_k - x_k -> 0 as the iteration converges).  `fista_tv_operators` is the array code;
 `fista_tv` runs the same iteration with `sart.residual_scan` (R ⊙ res in one launch) and `sart.backproject_scan` over all views.
 
+CGLS (conjugate gradients on the normal equations A^T W A x = A^T W b; Hestenes and Stiefel 1952, TIGRE's Krylov method) minimises
+1/2 ||b - A x||_W^2 with ||d||_W^2 = sum_r w_r d_r^2 and one weight w_r >= 0 per ray (`weights=None`: all ones).  A weight of 0
+leaves a ray out, R = 1 / (A 1) (`ray_length_weights`) makes the objective FISTA-TV's data term and the norms comparable with
+SIRT's, and exp(-b) (`pwls_weights`) is the statistical weight of `dataset.add_noise`'s model.  No row or column sums are needed:
+
+    r = b - A x0;  s = A^T (w ⊙ r);  p = s;  gamma = ||s||^2
+    for k in range(n_iter):
+        norm_k = ||r||_W                         (taken before the update, like every other solver's list)
+        q = A p;  delta = sum w q^2
+        if not gamma > 0 or not delta > 0: stop  (x is a minimiser, or p lies in the null space of W^(1/2) A)
+        alpha = gamma / delta;  x += alpha p;  r -= alpha q
+        s = A^T (w ⊙ r);  gamma' = ||s||^2;  beta = gamma' / gamma;  p = s + beta p;  gamma = gamma'
+
+The method is linear, so nothing is clamped inside the loop; `nonneg` clamps the returned volume once at the end.  r is the
+recurred residual, not b - A x recomputed, and there are no restarts: in float32 the two drift apart over many iterations, which
+ten to twenty iterations do not reach.  The finite termination and the monotone ||r||_W rest on A^T being the exact transpose of A,
+which it is here.  `cgls_operators` is the array code; `cgls` runs the same iteration with the scalars kept
+on the device by three HIP kernels (`cgls_kernels`, include/naf_hip.h K1): fp64 sums in a fixed order, no host read-back per iteration.
+
 FDK (Feldkamp, Davis and Kress, in the form of Kak and Slaney ch. 3, the row spacing taken at the isocentre).  Detector pixel
 (u, v), u along the last axis of [N, H, W] (pitch du = dDetector[0], perpendicular to the rotation axis), v along the rows (dv);
 cos(gamma) = DSD / sqrt(DSD^2 + u^2 + v^2);  tau = du * DSO / DSD;  t[m] = tau * h(m tau), the taps of `filter.ramp_taps`:
@@ -79,7 +98,7 @@ No short-scan (Parker) weights: a cone scan that covers less than a full turn is
 (laminographic) scan is refused: its constant and filter direction are not verified here.
 
 The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
-arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart` and `fista_tv`, are HIP kernels.
+arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart`, `fista_tv` and `cgls`, are HIP kernels.
 """
 from __future__ import annotations
 
@@ -460,6 +479,141 @@ def fista_tv(projections, geo, angles, n_iter=30, lam=DEFAULT_FISTA_TV_LAMBDA, t
         if callback is not None:
             callback(k, x, math.sqrt(float(norms[-1])))
     return x, [math.sqrt(float(v)) for v in norms]
+
+
+def _check_cgls(n_iter):
+    n_iter = int(n_iter)
+    if n_iter < 0:
+        raise ValueError(f"cgls: n_iter must be >= 0, got {n_iter}")
+    return n_iter
+
+
+def cgls_operators(A, AT, b, n_iter, weights=None, x0=None, nonneg=True, callback=None):
+    """CGLS on 1/2 ||b - A x||_W^2 over `A`, `AT` (as in `sirt_operators`); `weights` is an array of `b`'s kind with one weight
+    >= 0 per ray, None for all ones.  See the module docstring for the iteration.  `callback(k, x, residual_norm)` runs after every
+    iteration that took a step.  Returns (x, norms) with norms[k] = ||r_k||_W, r the recurred residual; the list ends with the norm
+    of the iteration that stopped, if one did (gamma or delta not > 0)."""
+    n_iter = _check_cgls(n_iter)
+    xp, clamp = _namespace(b)
+    w = weights
+
+    def weighted(d):
+        return d if w is None else w * d
+
+    def wsum(d):
+        return float((d * d if w is None else w * d * d).sum(dtype=xp.float64))
+
+    if x0 is None:
+        r = b + xp.zeros_like(b)
+        s = AT(weighted(r))
+        x = xp.zeros_like(s)
+    else:
+        r = b - A(x0)
+        s = AT(weighted(r))
+        x = x0 + xp.zeros_like(s)                                # a copy: the caller's x0 stays as it is
+    p = s
+    gamma = float((s * s).sum(dtype=xp.float64))
+    norms = []
+    for k in range(n_iter):
+        norms.append(math.sqrt(wsum(r)))
+        q = A(p)
+        delta = wsum(q)
+        if not gamma > 0.0 or not delta > 0.0:
+            break
+        alpha = gamma / delta
+        x = x + alpha * p
+        r = r - alpha * q
+        s = AT(weighted(r))
+        gamma_next = float((s * s).sum(dtype=xp.float64))
+        p = s + (gamma_next / gamma) * p
+        gamma = gamma_next
+        if callback is not None:
+            callback(k, x, norms[-1])
+    if nonneg:
+        x = clamp(x, 0, None)
+    return x, norms
+
+
+def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True, callback=None, views_per_call=None,
+         deterministic=False, info=None):
+    """CGLS reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
+    (float32 volume of geo.nVoxel on the projections' device, residual norms ||r_k||_W).  The iteration of `cgls_operators`:
+    A is `projector.project_scan`, A^T `sart.backproject_scan` over all views into a zeroed volume, and the rest three HIP launches
+    per iteration (`cgls_kernels.wdot`, `residual_step`, `direction_step`) that keep alpha, beta and the norms on the device, so
+    the whole solve is queued without a host read-back; the history and the stop mark are read once at the end, or per iteration
+    when a `callback(k, x, residual_norm)` is given (it sees the live, unclamped volume).  `weights` is a float32 [N, H, W] tensor
+    on the projections' device, >= 0 and finite (`ray_length_weights`, `pwls_weights`, a mask, or their product).  The norms are cut
+    at the iteration that stopped, if one did; `info`, a dict, receives `stopped_at` (that iteration, or None).
+    `deterministic=True` takes the atomic-free transpose: with the fixed-order fp64 sums two runs return the same bits and norms."""
+    import torch
+
+    from . import _abi, cgls_kernels as K, projector, sart
+    n_iter = _check_cgls(n_iter)
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError("cgls: projections must be a CUDA/HIP tensor (no CPU path)")
+    scan = sart.Scan(geo, angles, projections.device)
+    sart._check_stack(projections, (scan.N, scan.H, scan.W), None, "cgls", "projections")
+    w = weights
+    if w is not None:
+        sart._check_stack(w, (scan.N, scan.H, scan.W), projections, "cgls", "weights")
+        if bool(((w < 0) | ~torch.isfinite(w)).any()):
+            raise ValueError("cgls: weights must be >= 0 and finite")
+    if x0 is None:
+        x = torch.zeros(scan.dims, device=projections.device, dtype=torch.float32)
+        r = projections.clone()
+    else:
+        _abi.check_volume(x0, "cgls", "x0")
+        projector.check_geometry(x0, geo)
+        x = x0.clone()
+        r = projections - projector.project_scan(x, geo, angles, views_per_call=views_per_call)
+    transpose = {"method": _method(deterministic), "scan": scan}
+    if deterministic:
+        transpose["workspace"] = projector.gather_workspace(scan.N, scan.H, scan.W, projections.device)
+    ws = K.Workspace(max(r.numel(), x.numel()), n_iter, projections.device)
+    y = r.clone() if w is None else w * r
+    s = sart.backproject_scan(y, geo, angles, None, num=torch.zeros_like(x), **transpose)
+    p = s.clone()
+    K.wdot(s, None, K.SLOT_GAMMA[0], ws)
+    stopped = None
+    for k in range(n_iter):
+        q = projector.project_scan(p, geo, angles, views_per_call=views_per_call)
+        K.wdot(q, w, K.SLOT_DELTA, ws)
+        K.residual_step(r, q, w, y, k, ws)
+        sart.backproject_scan(y, geo, angles, None, num=s.zero_(), **transpose)
+        K.wdot(s, None, K.SLOT_GAMMA[(k + 1) & 1], ws)
+        K.direction_step(x, p, s, k, ws)
+        if callback is not None:
+            stopped = ws.stopped_at()
+            if stopped is not None:
+                break
+            callback(k, x, math.sqrt(float(ws.history()[k])))
+    history = ws.scalars.tolist()                               # the one read-back of a solve without a callback
+    mark = int(history[K.SLOT_STOPPED])
+    stopped = mark - 1 if mark > 0 else None
+    kept = n_iter if stopped is None else stopped + 1
+    norms = [math.sqrt(v) if v >= 0 else math.nan for v in history[K.HISTORY:K.HISTORY + kept]]
+    if info is not None:
+        info["stopped_at"] = stopped
+    if nonneg:
+        x.clamp_(min=0)
+    return x, norms
+
+
+def ray_length_weights(geo, angles, device, views_per_call=None):
+    """R = 1 / (A 1) where A 1 > 0, else 0: float32 [N, H, W] on `device`, the ray weights of SIRT and of FISTA-TV's data term."""
+    import torch
+
+    from . import projector
+    ones = torch.ones(tuple(int(v) for v in geo.nVoxel), device=device, dtype=torch.float32)
+    row = projector.project_scan(ones, geo, angles, views_per_call=views_per_call)
+    return torch.where(row > 0, 1.0 / torch.where(row > 0, row, torch.ones_like(row)), torch.zeros_like(row))
+
+
+def pwls_weights(projections):
+    """exp(-b): the expected photon count of a ray relative to the unattenuated beam under `dataset.add_noise`'s transmission
+    model, which is the inverse variance of the line integral up to one factor (penalised weighted least squares)."""
+    xp, _ = _namespace(projections)
+    return xp.exp(-projections)
 
 
 def fdk_weights(geo, angles, filter="ram-lak"):
