@@ -557,6 +557,35 @@ int naf_backproject_scan_gather(const float *values, const uint32_t *view_index,
                                 float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel, float step,
                                 float *volume, float *den, void *workspace, size_t workspace_bytes, void *stream);
 
+/* P6  ray-voxel intersection ("Siddon") forward projector: the second forward model beside P1, the one TIGRE's `Ax` takes by
+ * default (bit-parity with TIGRE is not pinned).  The volume is piecewise constant: voxel (i, j, k) is the box
+ *   [-h_a + i_a * dvoxel_a, -h_a + (i_a + 1) * dvoxel_a] per axis,  h_a = fp32(n_a * dvoxel_a / 2) as in P1,
+ * the value is volume[i, j, k] inside it and zero outside the volume.  volume, dvoxel, dims, rays, poses and the detector arguments
+ * are P1's; there is no sample step (TIGRE's geo.accuracy plays no part).
+ * A ray (o, d, near, far) is clipped exactly as P1 clips it: the same float32 slab test intersected with [near, far] in the same
+ * order, p0 = fma(t0, d, o), s_end = t1 - t0.  The result is
+ *     sum over voxels of  volume[voxel] * (length of the clipped segment inside that voxel):  exact chord lengths.
+ *   an empty span returns 0;  a non-finite p0 or s_end returns NaN;  a ray lying exactly in a voxel plane has measure zero and is
+ *   attributed to one of the two neighbours (the upper one; the last voxel on the face +h_a).
+ * Traversal (csrc/siddon_device.h), all in fp32, parametrised from p0 so that s runs over [0, s_end]:
+ *   i0_a, i1_a = floor((p_a + h_a) * (1 / dvoxel_a)) of the two end points p0 and fma(s_end, d, p0), clamped to [0, n_a - 1];
+ *   axis a has |i1_a - i0_a| plane crossings and the walk rem_x + rem_y + rem_z + 1 steps, fixed before the first of them;
+ *   plane m of axis a is crossed at s = (fma((float)m, dvoxel_a, -h_a) - p0_a) / d_a, computed from m itself;
+ *   each step takes the smallest next crossing among the axes that have crossings left (x before y before z on a tie; the others
+ *   of a tie follow as zero-length segments), clamps it to [s_prev, s_end], loads the current voxel once and adds
+ *   volume[voxel] * ((s_next - s_prev) * |d|) to an fp32 sum in traversal order;  the last step runs to s_end.
+ * INVARIANT: float comparisons only choose which axis WITH crossings left steps next.  No comparison moves an index past i1_a or
+ * adds a step, so a NaN or a rounding error cannot cause an out-of-range load or an unbounded loop.
+ * No atomics: two calls on the same inputs return the same bits.  All volume offsets are 64-bit.
+ * naf_project_rays_siddon: rays f32 [n_rays, 8] (16-byte aligned) -> out f32 [n_rays].
+ * naf_project_scan_siddon: out f32 [n_projections, det_h, det_w]; pixel (p, row, col) integrates the ray naf_generate_rays makes for
+ *   it, as in naf_project_scan.  Both refuse what their P1 counterparts refuse, before any launch; empty batches return NAF_OK. */
+int naf_project_rays_siddon(const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, const float *rays,
+                            uint64_t n_rays, float *out, void *stream);
+int naf_project_scan_siddon(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_projections,
+                            uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
+                            int parallel, float *out, void *stream);
+
 /* M1  3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
  * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
  * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.

@@ -1,0 +1,212 @@
+// siddon_device.h -- the per-ray traversal of the ray-voxel intersection ("Siddon") projector (include/naf_hip.h P6, DESIGN.md
+// section 20): the volume is constant inside a voxel, and a ray's integral is the sum over voxels of value x chord length.  It
+// includes nothing of HIP, so a host compiler reads it too: tools/siddon_host_check.cpp walks these very functions on the CPU under
+// AddressSanitizer / UBSan over heap volumes of exactly n1 n2 n3 floats.  The library and the host check are built with
+// -ffp-contract=off: every fused multiply-add here is asked for by name, everything else is one IEEE operation in the order written.
+//
+// INVARIANT.  Before the loop the entry and the exit voxel of the clipped segment are fixed per axis as integers i0_a, i1_a, each
+// clamped to [0, n_a - 1].  Axis a then has rem_a = |i1_a - i0_a| plane crossings left, its index moves by sign(i1_a - i0_a) per
+// crossing, and the loop makes exactly rem_x + rem_y + rem_z + 1 steps (rounded up to whole groups of kSiddonGroup; the walk's state
+// after the last step is a fixed point that yields zero-length segments of the exit voxel).  Float comparisons only choose WHICH axis
+// with rem_a > 0 crosses next; an axis with rem_a == 0 is never chosen, whatever the floats hold (NaN included), so every index
+// stays between i0_a and i1_a, every load is inside the volume, and the trip count is an integer known before the first step.
+// A rounding error can only reorder crossings that nearly coincide or shorten a segment; it cannot move an index out of range or
+// extend the loop.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define NAF_SIDDON_HD __host__ __device__ __forceinline__
+#else
+#define NAF_SIDDON_HD inline
+#endif
+#if defined(__clang__)
+#define NAF_SIDDON_UNROLL _Pragma("unroll")
+#else
+#define NAF_SIDDON_UNROLL
+#endif
+
+namespace naf {
+
+constexpr uint32_t kSiddonGroup = 4;   // steps whose loads are issued together, before the first of them is used
+
+struct SiddonGrid {
+    uint32_t n[3];
+    uint64_t stride[3];                // n2 * n3, n3, 1
+    float half[3];                     // fp32(n_a * dvoxel_a / 2), P1's h_a
+    float dvox[3];                     // dvoxel_a
+    float inv_d[3];                    // 1 / dvoxel_a
+};
+
+// Host: the grid of a [n1, n2, n3] volume; the same h_a and 1 / dvoxel_a as P1's make_volume.  Arguments are checked by the caller.
+inline void siddon_grid(uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, SiddonGrid *g) {
+    const uint32_t n[3] = {n1, n2, n3};
+    for (int a = 0; a < 3; ++a) {
+        g->n[a] = n[a];
+        g->half[a] = (float)((double)n[a] * (double)dvoxel[a] / 2.0);
+        g->dvox[a] = dvoxel[a];
+        g->inv_d[a] = 1.0f / dvoxel[a];
+    }
+    g->stride[0] = (uint64_t)n2 * n3;
+    g->stride[1] = n3;
+    g->stride[2] = 1;
+}
+
+// The clipped segment of a ray: P1's ray_span without the sample count -- the same float32 operations in the same order.
+struct SiddonSpan {
+    float p0[3], d[3];                 // p0 = fma(t0, d, o)
+    float s_end;                       // t1 - t0
+    float dn;                          // |d|
+};
+
+enum SiddonKind { kSiddonEmpty = 0, kSiddonOk = 1, kSiddonNotFinite = 2 };
+
+NAF_SIDDON_HD bool siddon_finite(float x) { return (x - x) == 0.0f; }   // false for NaN and +-infinity
+
+NAF_SIDDON_HD SiddonKind siddon_span(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, SiddonSpan &s) {
+    float t0 = near, t1 = far;
+    NAF_SIDDON_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        if (d[k] == 0.0f) {
+            if (o[k] < -g.half[k] || o[k] > g.half[k]) t1 = -INFINITY;    // parallel to the slab and outside it
+            continue;
+        }
+        const float ta = (-g.half[k] - o[k]) / d[k], tb = (g.half[k] - o[k]) / d[k];
+        const float lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
+        t0 = lo > t0 ? lo : t0;
+        t1 = hi < t1 ? hi : t1;
+    }
+    if (!(t1 > t0)) return kSiddonEmpty;
+    s.dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    s.s_end = t1 - t0;
+    bool finite = siddon_finite(s.s_end);
+    NAF_SIDDON_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        s.d[k] = d[k];
+        s.p0[k] = fmaf(t0, d[k], o[k]);
+        finite = finite && siddon_finite(s.p0[k]);
+    }
+    return finite ? kSiddonOk : kSiddonNotFinite;
+}
+
+// Voxel index of coordinate p on axis a, clamped to [0, n_a - 1].  The clamp is made on the float (fmaxf / fminf drop a NaN), so the
+// conversion to an integer is defined for every input.
+NAF_SIDDON_HD int32_t siddon_index(const SiddonGrid &g, int a, float p) {
+    float u = floorf((p + g.half[a]) * g.inv_d[a]);
+    u = fminf(fmaxf(u, 0.0f), (float)(g.n[a] - 1u));
+    return (int32_t)u;
+}
+
+// Parameter s (from p0) at which the ray crosses plane m of axis a: from m itself, never by increments.
+NAF_SIDDON_HD float siddon_crossing(const SiddonGrid &g, const SiddonSpan &r, int a, int32_t m) {
+    return (fmaf((float)m, g.dvox[a], -g.half[a]) - r.p0[a]) / r.d[a];
+}
+
+// State of a walk: the current voxel (as a 64-bit element offset), the crossings left per axis and each axis' next crossing.
+struct SiddonWalk {
+    int32_t idx[3], dir[3];            // current index; +1 / -1 / 0 per crossing
+    uint32_t rem[3];                   // crossings left
+    int64_t jump[3];                   // dir_a * stride_a
+    float next[3];                     // parameter of the next crossing (unused once rem_a == 0)
+    uint64_t offset;
+    float s_prev;
+};
+
+// Returns the number of steps: rem_x + rem_y + rem_z + 1.
+NAF_SIDDON_HD uint32_t siddon_begin(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w) {
+    uint32_t steps = 1;
+    w.offset = 0;
+    w.s_prev = 0.0f;
+    NAF_SIDDON_UNROLL
+    for (int a = 0; a < 3; ++a) {
+        const int32_t i0 = siddon_index(g, a, r.p0[a]);
+        const int32_t i1 = siddon_index(g, a, fmaf(r.s_end, r.d[a], r.p0[a]));
+        w.idx[a] = i0;
+        w.dir[a] = i1 > i0 ? 1 : (i1 < i0 ? -1 : 0);       // 0 for d_a == 0 and for n_a == 1: both ends clamp to one index
+        w.rem[a] = (uint32_t)(i1 > i0 ? i1 - i0 : i0 - i1);
+        w.jump[a] = (int64_t)w.dir[a] * (int64_t)g.stride[a];
+        w.next[a] = siddon_crossing(g, r, a, i0 + (w.dir[a] > 0 ? 1 : 0));
+        w.offset += (uint64_t)i0 * g.stride[a];
+        steps += w.rem[a];
+    }
+    return steps;
+}
+
+// One step: the offset of the current voxel and the length (in s) of the segment inside it, then the move across the nearest plane.
+// With no crossing left the segment runs to s_end, and every later step is a zero-length segment of the same voxel.
+NAF_SIDDON_HD void siddon_step(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w, uint64_t &offset, float &ds) {
+    const float dx = r.d[0], dy = r.d[1], dz = r.d[2];
+    const bool ax = w.rem[0] > 0u, ay = w.rem[1] > 0u, az = w.rem[2] > 0u;
+    // the smallest of the next crossings; an exhausted axis counts as +infinity: it is never chosen (integer tests gate every choice)
+    const bool px = ax && (!ay || w.next[0] <= w.next[1]) && (!az || w.next[0] <= w.next[2]);
+    const bool py = !px && ay && (!az || w.next[1] <= w.next[2]);
+    const bool pz = !px && !py && az;
+    const bool pick[3] = {px, py, pz};
+    float s = px ? w.next[0] : (py ? w.next[1] : (pz ? w.next[2] : r.s_end));
+    s = fminf(fmaxf(s, w.s_prev), r.s_end);                // simultaneous crossings follow as zero-length segments
+    offset = w.offset;
+    ds = s - w.s_prev;
+    w.s_prev = s;
+    // the move, without a branch: the picked axis steps, and its next crossing comes from its new plane by one division
+    NAF_SIDDON_UNROLL
+    for (int a = 0; a < 3; ++a) {
+        w.idx[a] += pick[a] ? w.dir[a] : 0;
+        w.rem[a] -= pick[a] ? 1u : 0u;
+        w.offset = (uint64_t)((int64_t)w.offset + (pick[a] ? w.jump[a] : (int64_t)0));
+    }
+    float num[3];
+    NAF_SIDDON_UNROLL
+    for (int a = 0; a < 3; ++a) num[a] = fmaf((float)(w.idx[a] + (w.dir[a] > 0 ? 1 : 0)), g.dvox[a], -g.half[a]) - r.p0[a];
+    const float c = (px ? num[0] : (py ? num[1] : num[2])) / (px ? dx : (py ? dy : dz));   // siddon_crossing of the picked axis
+    NAF_SIDDON_UNROLL
+    for (int a = 0; a < 3; ++a) w.next[a] = pick[a] ? c : w.next[a];
+}
+
+// Line integral of one ray (o, d, near, far) through the piecewise-constant volume `load` reads (load(offset) -> float, one call per
+// step).  fp32 sum in traversal order of value * ((s_next - s_prev) * |d|).  The loads of a group of steps are issued before the
+// first of them is used: the indices depend on one another, the loads do not.
+template <class Load>
+NAF_SIDDON_HD float siddon_line_integral(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, Load load) {
+    SiddonSpan r;
+    const SiddonKind kind = siddon_span(g, o, d, near, far, r);
+    if (kind == kSiddonEmpty) return 0.0f;
+    if (kind == kSiddonNotFinite) return __builtin_nanf("");
+    SiddonWalk w;
+    const uint32_t steps = siddon_begin(g, r, w);
+    // group n + 1 is stepped and its loads are issued before group n's values are used, so the loads of two groups are in flight
+    // while the next indices are computed
+    float acc = 0.0f, len[kSiddonGroup], f[kSiddonGroup];
+    uint64_t offset[kSiddonGroup];
+    NAF_SIDDON_UNROLL
+    for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+        float ds;
+        siddon_step(g, r, w, offset[j], ds);
+        len[j] = ds * r.dn;
+    }
+    NAF_SIDDON_UNROLL
+    for (uint32_t j = 0; j < kSiddonGroup; ++j) f[j] = load(offset[j]);
+    for (uint32_t k = kSiddonGroup; k < steps; k += kSiddonGroup) {
+        float len_next[kSiddonGroup], f_next[kSiddonGroup];
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+            float ds;
+            siddon_step(g, r, w, offset[j], ds);
+            len_next[j] = ds * r.dn;
+        }
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) f_next[j] = load(offset[j]);
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+            acc += f[j] * len[j];
+            f[j] = f_next[j];
+            len[j] = len_next[j];
+        }
+    }
+    NAF_SIDDON_UNROLL
+    for (uint32_t j = 0; j < kSiddonGroup; ++j) acc += f[j] * len[j];
+    return acc;
+}
+
+}  // namespace naf

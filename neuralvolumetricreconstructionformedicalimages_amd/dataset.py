@@ -231,9 +231,11 @@ NOISE_I0 = 1e5          # photons per pixel of the noise model of scan_from_volu
 
 
 def scan_from_volume(image, geometry, n_train, n_val, total_angle=180, start_angle=0, random_angle=False, noise=0, seed=0,
-                     device="cuda"):
+                     device="cuda", projector="interpolated"):
     """A complete scan with the pickle schema, projected from a CT volume by the HIP forward projector (projector.py): the
-    step dataGenerator/generateData.py:153-211 of the reference does with TIGRE's `Ax`.
+    step dataGenerator/generateData.py:153-211 of the reference does with TIGRE's `Ax`.  `projector` is `project_scan`'s `kind`:
+    "interpolated" (the default: trilinear samples) or "siddon" (piecewise-constant voxels, exact chord lengths: the kind `Ax`
+    takes by default, and a forward model that is not the one the baselines reconstruct with).
 
     `image` [n1, n2, n3] (axis 0 = x, voxel centres on the get_voxels grid) and the scanner dict `geometry` (pickle schema,
     millimetres) -> the dict `synthetic_scan` returns, which `TIGREDataset` loads unchanged; `image` is stored as given.
@@ -244,8 +246,9 @@ def scan_from_volume(image, geometry, n_train, n_val, total_angle=180, start_ang
     `noise > 0` adds a seeded transmission noise model to both splits: counts I = Poisson(I0 exp(-p)) + Normal(0, noise) with
     I0 = 1e5, then p = -ln(max(I, 1) / I0); negative training values are set to 0 (generateData.py:182).  Parity with
     TIGRE's CTnoise is not pinned."""
-    from .projector import project_scan
+    from .projector import check_kind, project_scan
 
+    check_kind(projector, "scan_from_volume")
     data = dict(geometry)
     geo = ConeGeometry(data)
     rng = np.random.RandomState(seed)
@@ -262,7 +265,8 @@ def scan_from_volume(image, geometry, n_train, n_val, total_angle=180, start_ang
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
     for name, angles in (("train", train_angles), ("val", val_angles)):
-        projs = project_scan(volume, geo, angles)
+        # the default is the call as it has always been made
+        projs = project_scan(volume, geo, angles) if projector == "interpolated" else project_scan(volume, geo, angles, kind=projector)
         if noise > 0:
             projs = add_noise(projs, noise, gen)
             if name == "train":

@@ -1,10 +1,15 @@
-"""Forward projector: line integrals of a voxel volume through libnaf_hip.so (`naf_project_rays`, `naf_project_scan`).
+"""Forward projector: line integrals of a voxel volume through libnaf_hip.so (`naf_project_rays`, `naf_project_scan` and their
+`_siddon` counterparts).
 
 This is what TIGRE's `tigre.Ax` does for the reference's dataGenerator/generateData.py:178,189: it turns a CT volume into the
 projections of a scan.  The projection is defined in include/naf_hip.h (P1) and DESIGN.md section 10: trilinear interpolation,
 clamp-to-edge inside the box and zero outside, midpoint rule with `n = max(1, ceil(len / (accuracy * min(dVoxel))))` samples
 over the part of the ray inside the box.  Pixel (p, row, col) of `project_scan` integrates the very ray `RayGenerator` makes for
 that pixel, so projections and training rays agree by construction (no TIGRE axis flips).  Bit-parity with TIGRE is not pinned.
+
+`kind="siddon"` selects the other discretisation (P6): the volume constant inside each voxel and exact chord
+lengths, the ray-voxel intersection projector TIGRE's `Ax` takes by default.  It has no sample step, so `accuracy` plays no part.
+The default everywhere is `kind="interpolated"`; the transposes and the solvers stay on the interpolated pair.
 
 There is no CPU fallback, like the rest of the hot path.
 """
@@ -24,6 +29,7 @@ MAX_PIXELS_PER_CALL = 1 << 26
 GATHER_SPAN_BYTES = 40
 GATHER_WORKSPACE_CAP = 32 << 20
 METHODS = ("scatter", "gather")
+KINDS = ("interpolated", "siddon")
 
 
 def _check_volume(volume):
@@ -45,8 +51,16 @@ def _dvoxel(dvoxel):
     return (ctypes.c_float * 3)(*[float(v) for v in d])
 
 
-def project_rays(volume, dvoxel, rays, accuracy=0.5, out=None):
-    """Line integrals of `volume` [n1, n2, n3] (voxel size `dvoxel` in metres) along `rays` [n, 8] -> float32 [n]."""
+def check_kind(kind, who):
+    if kind not in KINDS:
+        raise ValueError(f"{who}: kind must be one of {KINDS}, got {kind!r}")
+    return kind
+
+
+def project_rays(volume, dvoxel, rays, accuracy=0.5, out=None, kind="interpolated"):
+    """Line integrals of `volume` [n1, n2, n3] (voxel size `dvoxel` in metres) along `rays` [n, 8] -> float32 [n].
+    `kind="siddon"` integrates exact chord lengths through piecewise-constant voxels (P6); `accuracy` is ignored then."""
+    check_kind(kind, "project_rays")
     _check_volume(volume)
     if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device != volume.device:
         raise RuntimeError("project_rays: rays must be a CUDA/HIP tensor on the volume's device")
@@ -60,6 +74,10 @@ def project_rays(volume, dvoxel, rays, accuracy=0.5, out=None):
     elif out.shape != (n,) or out.dtype != torch.float32 or out.device != volume.device or not out.is_contiguous():
         raise ValueError("project_rays: out must be a contiguous float32 [n] tensor on the volume's device")
     n1, n2, n3 = volume.shape
+    if kind == "siddon":
+        _abi.check(_abi.lib().naf_project_rays_siddon(_abi.ptr(volume), n1, n2, n3, ctypes.byref(_dvoxel(dvoxel)), _abi.ptr(rays), n,
+                                                      _abi.ptr(out), _abi.stream_ptr()), "project_rays_siddon")
+        return out
     _abi.check(_abi.lib().naf_project_rays(_abi.ptr(volume), n1, n2, n3, ctypes.byref(_dvoxel(dvoxel)), _abi.ptr(rays), n,
                                            sample_step(dvoxel, accuracy), _abi.ptr(out), _abi.stream_ptr()), "project_rays")
     return out
@@ -74,9 +92,11 @@ def check_geometry(volume, geo):
         raise ValueError(f"projector: volume shape {tuple(volume.shape)} does not match nVoxel {want}")
 
 
-def project_scan(volume, geo, angles, views_per_call=None):
+def project_scan(volume, geo, angles, views_per_call=None, kind="interpolated"):
     """Projections of `volume` for the scan geometry `geo` (ConeGeometry) at `angles` (radians) -> float32 [N, H, W] on the
-    volume's device.  Views go to the kernel in groups of `views_per_call` (default: as many as fit MAX_PIXELS_PER_CALL)."""
+    volume's device.  Views go to the kernel in groups of `views_per_call` (default: as many as fit MAX_PIXELS_PER_CALL).
+    `kind="siddon"` integrates exact chord lengths through piecewise-constant voxels (P6); `geo.accuracy` is ignored then."""
+    check_kind(kind, "project_scan")
     _check_volume(volume)
     check_geometry(volume, geo)
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)
@@ -92,6 +112,13 @@ def project_scan(volume, geo, angles, views_per_call=None):
     lib = _abi.lib()
     for first in range(0, N, per_call):
         count = min(per_call, N - first)
+        if kind == "siddon":
+            _abi.check(lib.naf_project_scan_siddon(
+                _abi.ptr(volume), ctypes.byref(dims), ctypes.byref(dv), _abi.ptr(raygen.poses[first:first + count]), count, W, H,
+                float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]),
+                float(geo.DSD), float(raygen.near), float(raygen.far), int(geo.mode == "parallel"),
+                _abi.ptr(out[first:first + count]), _abi.stream_ptr()), "project_scan_siddon")
+            continue
         _abi.check(lib.naf_project_scan(
             _abi.ptr(volume), ctypes.byref(dims), ctypes.byref(dv), _abi.ptr(raygen.poses[first:first + count]), count, W, H,
             float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]), float(geo.DSD),

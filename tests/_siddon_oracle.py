@@ -1,0 +1,366 @@
+"""Float64 numpy oracle of the ray-voxel intersection ("Siddon") projector (include/naf_hip.h P6), its
+per-ray error bound, a float32 restatement of the kernel's traversal, and the ray sets the tests share -- not a test module.
+
+A ray enters as the kernel's float32 p0, d, s_end and |d| (formed in the kernel's operation order, like _projector_oracle.py);
+the oracle then takes x(s) = p0 + s d, s in [0, s_end], as exact: it collects every interior plane crossing in float64, sorts them,
+attributes each interval to the voxel of its midpoint and sums.
+
+Bound (derivation in DESIGN.md section 20), u = 2^-24:
+    |kernel - oracle| <= |d| * sum_c delta_c * J_c + (K + 2) * u * sum_i |f_i| * l_i
+    delta_c = 1.001 u (2 |P| + 2 |P - p0_a| + 3 |P + h_a|) / |d_a|    for the crossing of plane P of axis a
+    J_c = |f+ - f-| of the crossing, or max(volume) - min(volume) where another crossing lies within delta_c + delta_c'
+    K = number of crossings + 1 (the trip count), f_i, l_i the value and length of interval i."""
+import numpy as np
+
+from _projector_oracle import half_extent
+
+f32, f64 = np.float32, np.float64
+U = 2.0 ** -24
+EMPTY, OK, NOT_FINITE = 0, 1, 2
+
+
+def _fma32(a, b, c):
+    """fma(a, b, c) of float32 arrays: the product is exact in float64, the sum rounds to 53 bits and then to 24."""
+    return (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(f32)
+
+
+def spans(rays, dims, dvoxel):
+    """rays [n, 8] -> float32 p0 [n, 3], d [n, 3], s_end [n], |d| [n] and kind [n] in the kernel's order (siddon_span)."""
+    r = np.asarray(rays, dtype=f32)
+    o, d = r[:, 0:3], r[:, 3:6]
+    t0, t1 = r[:, 6].copy(), r[:, 7].copy()
+    half = half_extent(dims, dvoxel)
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            ok, dk, h = o[:, k], d[:, k], half[k]
+            flat = dk == 0
+            outside = flat & ((ok < -h) | (ok > h))
+            ta, tb = (f32(-h) - ok) / dk, (h - ok) / dk
+            lo, hi = np.where(ta < tb, ta, tb), np.where(ta < tb, tb, ta)
+            t0 = np.where(~flat & (lo > t0), lo, t0)
+            t1 = np.where(~flat & (hi < t1), hi, t1)
+            t1 = np.where(outside, f32(-np.inf), t1)
+        hit = t1 > t0
+        dn = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        s_end = (t1 - t0).astype(f32)
+        p0 = _fma32(t0[:, None], d, o)
+        finite = np.isfinite(s_end) & np.isfinite(p0).all(1)
+    kind = np.where(hit, np.where(finite, OK, NOT_FINITE), EMPTY)
+    return p0, d.copy(), s_end, dn.astype(f32), kind
+
+
+def project_rays(volume, dvoxel, rays, chunk=512):
+    """-> (value float64 [n], bound float64 [n]): 0 / 0 for an empty span, NaN / NaN for a non-finite one."""
+    vol = np.asarray(volume, dtype=f64)
+    dims = vol.shape
+    spread = float(vol.max() - vol.min())
+    p0, d, s_end, dn, kind = (a.astype(f64) if a.dtype == f32 else a for a in spans(rays, dims, dvoxel))
+    half = half_extent(dims, dvoxel).astype(f64)
+    dv = np.asarray(dvoxel, dtype=f32).astype(f64)
+    # interior planes 1 .. n_a - 1 of every axis
+    axis = np.concatenate([np.full(max(n - 1, 0), a) for a, n in enumerate(dims)]).astype(np.int64)
+    plane = np.concatenate([-half[a] + np.arange(1, n) * dv[a] for a, n in enumerate(dims)]) if axis.size else np.zeros(0)
+    value, bound = np.zeros(len(p0)), np.zeros(len(p0))
+    for s0 in range(0, len(p0), chunk):
+        sl = slice(s0, s0 + chunk)
+        ok = kind[sl] == OK
+        P0, D, SE, DN = np.where(ok[:, None], p0[sl], 0.0), np.where(ok[:, None], d[sl], 1.0), np.where(ok, s_end[sl], 0.0), dn[sl]
+        R = len(P0)
+        with np.errstate(all="ignore"):
+            sc = (plane[None, :] - P0[:, axis]) / D[:, axis]
+            delta = 1.001 * U * (2 * np.abs(plane)[None, :] + 2 * np.abs(plane[None, :] - P0[:, axis])
+                                 + 3 * np.abs(plane + half[axis])[None, :]) / np.abs(D[:, axis])
+        valid = np.isfinite(sc) & (sc > 0) & (sc < SE[:, None])
+        sc = np.where(valid, sc, SE[:, None])                       # invalid crossings sort to the end as zero-length intervals
+        order = np.argsort(sc, axis=1, kind="stable")
+        sc, valid, delta = (np.take_along_axis(a, order, 1) for a in (sc, valid, delta))
+        edges = np.concatenate([np.zeros((R, 1)), sc, SE[:, None]], 1)
+        length = np.diff(edges, axis=1)
+        mid = 0.5 * (edges[:, 1:] + edges[:, :-1])
+        idx = []
+        for a in range(3):
+            x = P0[:, a, None] + mid * D[:, a, None]
+            idx.append(np.clip(np.floor((x + half[a]) / dv[a]), 0, dims[a] - 1).astype(np.int64))
+        f = vol[idx[0], idx[1], idx[2]]
+        with np.errstate(invalid="ignore"):
+            total = (f * length).sum(1) * DN
+        jump = np.abs(f[:, 1:] - f[:, :-1])                         # crossing j separates intervals j and j + 1
+        dd = np.where(valid, delta, 0.0)
+        gap = np.abs(sc[:, :, None] - sc[:, None, :]) <= dd[:, :, None] + dd[:, None, :]
+        gap &= valid[:, :, None] & valid[:, None, :] & ~np.eye(sc.shape[1], dtype=bool)[None]
+        jump = np.where(gap.any(2), spread, jump)
+        K = valid.sum(1) + 1
+        with np.errstate(invalid="ignore"):
+            b = DN * (dd * jump).sum(1) + (K + 2) * U * (np.abs(f) * length).sum(1) * DN
+        value[sl] = np.where(ok, total, np.where(kind[sl] == NOT_FINITE, np.nan, 0.0))
+        bound[sl] = np.where(ok, b, np.where(kind[sl] == NOT_FINITE, np.nan, 0.0))
+    return value, bound
+
+
+def use(got, want, bound):
+    """|got - want| / bound per ray; 0 where both are exactly equal (empty spans) or both NaN, inf where got is not finite alone."""
+    got, want, bound = (np.asarray(a, dtype=f64) for a in (got, want, bound))
+    out = np.full(got.shape, np.inf)
+    same = (got == want) | (np.isnan(got) & np.isnan(want))
+    out[same] = 0.0
+    rest = ~same & np.isfinite(got) & np.isfinite(want) & (bound > 0)
+    out[rest] = np.abs(got[rest] - want[rest]) / bound[rest]
+    return out
+
+
+DEFECTS = ("tie_drop", "neg_plane", "drop_last", "no_clamp_hi")
+
+
+def walk_f32(volume, dvoxel, rays, defect=None):
+    """The kernel's traversal (csrc/siddon_device.h) in float32 numpy, all rays at once -> float32 [n].  A load outside the
+    volume reads NaN.  `defect` injects one of DEFECTS."""
+    assert defect is None or defect in DEFECTS
+    vol = np.asarray(volume, dtype=f32)
+    dims = vol.shape
+    pad = np.full(tuple(n + 2 for n in dims), np.nan, dtype=f32)
+    pad[1:-1, 1:-1, 1:-1] = vol
+    p0, d, s_end, dn, kind = spans(rays, dims, dvoxel)
+    half = half_extent(dims, dvoxel)
+    dv = np.asarray(dvoxel, dtype=f32)
+    inv = (f32(1) / dv).astype(f32)
+    R = len(p0)
+    ok = kind == OK
+    p0 = np.where(ok[:, None], p0, f32(0))
+    s_end = np.where(ok, s_end, f32(0))
+    hi = np.asarray(dims, dtype=f32) - f32(1)
+
+    def index(p, entry):
+        with np.errstate(all="ignore"):
+            u = np.floor((p + half[None, :]) * inv[None, :])
+        top = hi + f32(1) if (entry and defect == "no_clamp_hi") else hi
+        u = np.fmin(np.fmax(u, f32(0)), top[None, :])
+        return u.astype(np.int64)
+
+    def crossing(m):
+        with np.errstate(all="ignore"):
+            q = _fma32(m.astype(f32), dv[None, :], -half[None, :])
+            return ((q - p0) / d).astype(f32)
+
+    i0, i1 = index(p0, True), index(_fma32(s_end[:, None], d, p0), False)
+    idx = i0.copy()
+    dirn = np.sign(i1 - i0)
+    rem = np.abs(i1 - i0)
+    plane_of = (lambda i: i + 1) if defect == "neg_plane" else (lambda i: i + (dirn > 0))
+    nxt = crossing(plane_of(idx))
+    steps = rem.sum(1) + 1 - (1 if defect == "drop_last" else 0)
+    s_prev = np.zeros(R, dtype=f32)
+    acc = np.zeros(R, dtype=f32)
+    for k in range(int(steps.max()) if R else 0):
+        live = ok & (k < steps)
+        ax, ay, az = rem[:, 0] > 0, rem[:, 1] > 0, rem[:, 2] > 0
+        with np.errstate(invalid="ignore"):
+            px = ax & (~ay | (nxt[:, 0] <= nxt[:, 1])) & (~az | (nxt[:, 0] <= nxt[:, 2]))
+            py = ~px & ay & (~az | (nxt[:, 1] <= nxt[:, 2]))
+        pz = ~px & ~py & az
+        pick = np.stack([px, py, pz], 1)
+        s = np.where(px, nxt[:, 0], np.where(py, nxt[:, 1], np.where(pz, nxt[:, 2], s_end)))
+        s = np.fmin(np.fmax(s, s_prev), s_end).astype(f32)
+        f = pad[idx[:, 0] + 1, idx[:, 1] + 1, idx[:, 2] + 1]
+        with np.errstate(invalid="ignore"):
+            term = (f * ((s - s_prev).astype(f32) * dn).astype(f32)).astype(f32)
+            acc = np.where(live, (acc + term).astype(f32), acc)
+        if defect == "tie_drop":                                    # a tie steps one axis and forgets the other's crossing
+            chosen = np.where(px, nxt[:, 0], np.where(py, nxt[:, 1], nxt[:, 2]))
+            with np.errstate(invalid="ignore"):
+                tied = ~pick & (rem > 0) & (nxt == chosen[:, None]) & pick.any(1)[:, None]
+            rem = rem - (tied & live[:, None])
+        move = pick & live[:, None]
+        idx = idx + np.where(move, dirn, 0)
+        rem = rem - move
+        nxt = np.where(move, crossing(plane_of(idx)), nxt)
+        s_prev = np.where(live, s, s_prev)
+    return np.where(ok, acc, np.where(kind == NOT_FINITE, f32(np.nan), f32(0))).astype(f32)
+
+
+# ---- the cases the CPU tests, the GPU tests and tools/siddon_host_check.py share ----------------------------------------------
+DIMS, DVOXEL_MM = (17, 9, 33), (1.0, 0.7, 1.3)
+DIMS_FLAT = (5, 1, 8)                                               # a constant axis
+DIMS_CUBE, DVOXEL_CUBE_MM = (8, 8, 8), (1.0, 1.0, 1.0)
+
+
+def metres(dvoxel_mm):
+    return np.asarray(dvoxel_mm, dtype=f64) / 1000
+
+
+def volume(dims, seed=5):
+    return np.random.default_rng(seed).random(dims).astype(f32)
+
+
+def scan_geometry(mode, dims=DIMS, dvoxel_mm=DVOXEL_MM):
+    """(a) cone: DSO 1 m, DSD 1.5 m; (b) parallel at tilt_angle 29, the scanner close enough for [near, far] to hold the chord."""
+    data = {"DSD": 1500.0, "DSO": 1000.0, "nDetector": [24, 24], "dDetector": [1.5, 3.0] if mode == "cone" else [1.0, 2.2],
+            "nVoxel": list(dims), "dVoxel": list(dvoxel_mm), "offOrigin": [0, 0, 0], "offDetector": [0.4, -0.7], "accuracy": 0.5,
+            "mode": mode, "filter": None}
+    if mode == "parallel":
+        data["tilt_angle"], data["DSO"], data["DSD"] = 29, 100.0, 150.0
+    return data
+
+
+SCAN_ANGLES = np.linspace(0.1, 3.0, 8)
+
+
+def scan_rays(mode, dims=DIMS, dvoxel_mm=DVOXEL_MM):
+    from neuralvolumetricreconstructionformedicalimages_amd.dataset import _rays_cpu
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    geo = ConeGeometry(scan_geometry(mode, dims, dvoxel_mm))
+    return np.concatenate([_rays_cpu(geo, a).numpy() for a in SCAN_ANGLES]).astype(f32)
+
+
+def random_rays(dims, dvoxel_mm, n=4096, seed=9):
+    """(c) rays that start inside the volume; [near, far] cuts the segment inside voxels."""
+    rng = np.random.default_rng(seed)
+    h = np.asarray(dims) * metres(dvoxel_mm) / 2
+    o = rng.uniform(-0.98, 0.98, (n, 3)) * h
+    d = rng.standard_normal((n, 3))
+    d *= (rng.uniform(0.5, 2.0, n) / np.linalg.norm(d, axis=1))[:, None]
+    near = rng.uniform(0.0005, 0.003, n)
+    far = near + rng.uniform(0.002, 0.03, n)
+    return np.concatenate([o, d, near[:, None], far[:, None]], 1).astype(f32)
+
+
+def centre(dims, dvoxel_mm, ijk):
+    return (np.asarray(ijk) + 0.5) * metres(dvoxel_mm) - np.asarray(dims) * metres(dvoxel_mm) / 2
+
+
+def axis_rays(dims, dvoxel_mm, ijk):
+    """(d) axis-parallel rays through the centre of voxel ijk, one per axis and sign."""
+    c = centre(dims, dvoxel_mm, ijk)
+    rays = []
+    for a in range(3):
+        for sign in (1.0, -1.0):
+            o, d = c.copy(), np.zeros(3)
+            o[a], d[a] = -sign * 0.1, sign
+            rays.append(np.concatenate([o, d, [0.0, 1.0]]))
+    return np.asarray(rays, dtype=f32)
+
+
+def diagonal_rays():
+    """(e) the body diagonal of the 8^3 cube, both directions: o and d have three equal components, so every operation gives the
+    same float on the three axes and all three crossings tie exactly at every corner."""
+    return np.asarray([[-0.05] * 3 + [1.0] * 3 + [0.0, 1.0], [0.05] * 3 + [-1.0] * 3 + [0.0, 1.0],
+                       [-0.05] * 3 + [0.7] * 3 + [0.01, 0.0789]], dtype=f32)
+
+
+def miss_and_graze_rays(dims, dvoxel_mm):
+    """(f) rays that miss the volume, and rays that cut a corner with a chord shorter than a voxel."""
+    h = np.asarray(dims) * metres(dvoxel_mm) / 2
+    rays = [np.concatenate([[0.5, 0.5, 0.5], [1.0, 0.2, 0.1], [0.0, 2.0]]),            # points away
+            np.concatenate([[-0.2, 2 * h[1], 0.0], [1.0, 0.0, 0.0], [0.0, 1.0]]),      # parallel to a slab, outside it
+            np.concatenate([[-0.2, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.1]]),           # [near, far] ends before the volume
+            np.concatenate([[-0.2, 0.0, 0.0], [1.0, 0.0, 0.0], [0.5, 0.1]])]           # far < near
+    for sx in (1, -1):
+        for sy in (1, -1):
+            for sz in (1, -1):
+                corner = h * [sx, sy, sz]
+                inside = corner * (1 - np.array([2e-2, 5e-2, 1e-2]))                  # less than a voxel from the corner
+                d = np.array([sx * 1.0, -sy * 0.8, sz * 0.1])
+                rays.append(np.concatenate([inside - 0.07 * d, d, [0.0, 1.0]]))
+    return np.asarray(rays, dtype=f32)
+
+
+def zero_component_rays(dims, dvoxel_mm):
+    """(g) rays with a zero component in d, off every voxel plane, and one lying in the face +h_x (attributed to the last voxel)."""
+    h = half_extent(dims, metres(dvoxel_mm))
+    c = centre(dims, dvoxel_mm, [n // 2 for n in dims]) + metres(dvoxel_mm) * [0.21, -0.13, 0.37]
+    rays = []
+    for d in ([0.3, 0.7, 0.0], [0.0, 1.0, -0.4], [1.0, 0.0, 0.2], [-0.6, 0.0, 0.0], [0.0, 0.0, 1.3], [0.0, -0.9, 0.0]):
+        d = np.asarray(d)
+        rays.append(np.concatenate([c - 0.06 * d / np.linalg.norm(d) ** 2 * np.linalg.norm(d), d, [0.0, 1.0]]))
+    face = np.concatenate([[float(h[0]), c[1], -0.1], [0.0, 0.0, 1.0], [0.0, 1.0]])
+    rays.append(face)
+    out = np.asarray(rays, dtype=f32)
+    out[-1, 0] = h[0]
+    return out
+
+
+def ray_sets():
+    """name -> (dims, dvoxel in metres, volume, rays) for the sets (a)-(g); the random group repeats on the constant-axis dims."""
+    dv, vol = metres(DVOXEL_MM), volume(DIMS)
+    dv_cube = metres(DVOXEL_CUBE_MM)
+    interior = [n // 2 for n in DIMS]
+    sets = {
+        "a cone scan": (DIMS, dv, vol, scan_rays("cone")),
+        "b parallel tilt 29": (DIMS, dv, vol, scan_rays("parallel")),
+        "c random": (DIMS, dv, vol, random_rays(DIMS, DVOXEL_MM)),
+        "c random, constant axis": (DIMS_FLAT, dv, volume(DIMS_FLAT, 6), random_rays(DIMS_FLAT, DVOXEL_MM, seed=10)),
+        "d axis-parallel": (DIMS, dv, vol, np.concatenate([axis_rays(DIMS, DVOXEL_MM, interior), axis_rays(DIMS, DVOXEL_MM, (0, 0, 0)),
+                                                            axis_rays(DIMS, DVOXEL_MM, [n - 1 for n in DIMS])])),
+        "e cube diagonal": (DIMS_CUBE, dv_cube, volume(DIMS_CUBE, 7), diagonal_rays()),
+        "f miss and graze": (DIMS, dv, vol, miss_and_graze_rays(DIMS, DVOXEL_MM)),
+        "g zero component": (DIMS, dv, vol, zero_component_rays(DIMS, DVOXEL_MM)),
+    }
+    return sets
+
+
+def hot_voxels(dims):
+    """The hot-voxel cases: both extreme corners, a face centre and the interior."""
+    n1, n2, n3 = dims
+    return [(0, 0, 0), (n1 - 1, n2 - 1, n3 - 1), (0, n2 // 2, n3 // 2), (n1 // 2, n2 // 2, n3 // 2)]
+
+
+def hot_volume(dims, ijk):
+    vol = np.zeros(dims, dtype=f32)
+    vol[tuple(ijk)] = 1.0
+    return vol
+
+
+def box_chord(p0, d, s_end, dn, lo, hi):
+    """Length of the part of x(s) = p0 + s d, s in [0, s_end], inside the box [lo, hi]: the float64 slab test."""
+    p0, d = np.asarray(p0, f64), np.asarray(d, f64)
+    a, b = np.zeros(len(p0)), np.asarray(s_end, f64).copy()
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            ta, tb = (lo[k] - p0[:, k]) / d[:, k], (hi[k] - p0[:, k]) / d[:, k]
+            flat = d[:, k] == 0
+            inside = (p0[:, k] >= lo[k]) & (p0[:, k] <= hi[k])
+            a = np.where(flat, np.where(inside, a, np.inf), np.maximum(a, np.minimum(ta, tb)))
+            b = np.where(flat, b, np.minimum(b, np.maximum(ta, tb)))
+    return np.maximum(b - a, 0.0) * np.asarray(dn, f64)
+
+
+def voxel_box(dims, dvoxel, ijk):
+    half = half_extent(dims, dvoxel).astype(f64)
+    dv = np.asarray(dvoxel, dtype=f32).astype(f64)
+    lo = -half + np.asarray(ijk) * dv
+    return lo, lo + dv
+
+
+def non_finite_rays(rays):
+    """The first rays of `rays` with a NaN or an Inf in o or d: the definition returns 0 (empty span) or NaN for each."""
+    out = np.asarray(rays[:12], dtype=f32).copy()
+    for i, (col, bad) in enumerate([(0, np.nan), (1, np.inf), (2, -np.inf), (3, np.nan), (4, np.inf), (5, -np.inf), (0, np.inf),
+                                    (3, np.inf), (4, np.nan), (5, np.nan), (1, np.nan), (2, np.inf)]):
+        out[i, col] = bad
+    return out
+
+
+def orientation_case(n=32, views=8, det=24):
+    """synthetic_scan's analytic phantom at n^3 and the rays of a `views`-view cone scan on a det x det detector that covers the
+    volume -> (geometry dict, geo, phantom volume float32 [n, n, n], rays [views * det * det, 8], analytic line integrals)."""
+    import torch
+    from neuralvolumetricreconstructionformedicalimages_amd import phantom
+    from neuralvolumetricreconstructionformedicalimages_amd.dataset import _rays_cpu
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
+    data = phantom.scan_geometry(n)
+    pitch = 0.3 * 1.5 * 1000 / det
+    data["nDetector"], data["dDetector"] = [det, det], [pitch, pitch]
+    geo = ConeGeometry(data)
+    table = phantom.ellipsoid_table(seed=0, extent=float(geo.sVoxel[0]) / 2)
+    angles = np.linspace(0, np.pi, views + 1)[:-1]
+    rays = torch.cat([_rays_cpu(geo, a) for a in angles])
+    exact = phantom.line_integrals(rays, table).double().numpy()
+    return data, geo, phantom.volume(geo, table).numpy(), rays.numpy().astype(f32), exact, angles
+
+
+def orientation_errors(project, vol, exact):
+    """Relative L2 distance to the analytic integrals of `project(volume)` for the volume as it is, with x / y swapped and with
+    z flipped."""
+    out = []
+    for v in (vol, np.ascontiguousarray(vol.transpose(1, 0, 2)), np.ascontiguousarray(vol[:, :, ::-1])):
+        out.append(float(np.linalg.norm(project(v) - exact) / np.linalg.norm(exact)))
+    return out

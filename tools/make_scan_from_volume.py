@@ -12,7 +12,8 @@ rescale_intercept, normalize) and the scan (numTrain, numVal, totalAngle, startA
 `--volume` is a `.npy` array [n1, n2, n3] (axis 0 = x) or a MATLAB `.mat` file holding `img`.  A volume of another shape is
 resized to nVoxel on the GPU (volume.prepare_volume: the cubic B-spline of scipy.ndimage.zoom, order 3, no prefilter, like
 loadImage), so only reading `.mat` files needs scipy.  `--resize scipy` prepares the volume on the host with
-scipy.ndimage.zoom itself instead.
+scipy.ndimage.zoom itself instead.  `--projector siddon` projects with the ray-voxel intersection projector (exact chord lengths
+through piecewise-constant voxels, the kind TIGRE's `Ax` takes by default) instead of the interpolated one; the pickle is the same.
 """
 import argparse
 import os
@@ -87,7 +88,7 @@ def prepare_volume(image, n_voxel, convert, rescale_slope, rescale_intercept, no
     return np.ascontiguousarray(image, dtype=np.float32)
 
 
-def make_scan(volume_path, config_path, device="cuda", seed=0, resize="device"):
+def make_scan(volume_path, config_path, device="cuda", seed=0, resize="device", projector="interpolated"):
     from neuralvolumetricreconstructionformedicalimages_amd.dataset import scan_from_volume
     config = read_config(config_path)
     args = (read_volume(volume_path), config["nVoxel"], config["convert"], config["rescale_slope"], config["rescale_intercept"],
@@ -101,7 +102,7 @@ def make_scan(volume_path, config_path, device="cuda", seed=0, resize="device"):
         raise ValueError(f"resize must be 'device' or 'scipy', got {resize!r}")
     data = scan_from_volume(image, geometry_of(config), config["numTrain"], config["numVal"], total_angle=config["totalAngle"],
                             start_angle=config["startAngle"], random_angle=bool(config["randomAngle"]),
-                            noise=float(config["noise"] or 0), seed=seed, device=device)
+                            noise=float(config["noise"] or 0), seed=seed, device=device, projector=projector)
     for k in VOLUME_KEYS + ("totalAngle", "startAngle", "randomAngle", "noise"):
         data[k] = config[k]                      # the reference's pickle keeps the whole config
     return data
@@ -116,8 +117,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seeds the random angles and the noise")
     ap.add_argument("--resize", choices=("device", "scipy"), default="device",
                     help="prepare the volume on the GPU (default) or on the host with scipy.ndimage.zoom")
+    ap.add_argument("--projector", choices=("interpolated", "siddon"), default="interpolated",
+                    help="forward model: trilinear samples (default) or exact chord lengths through constant voxels")
     args = ap.parse_args(argv)
-    data = make_scan(args.volume, args.config, args.device, args.seed, args.resize)
+    data = make_scan(args.volume, args.config, args.device, args.seed, args.resize, args.projector)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "wb") as handle:
         pickle.dump(data, handle, pickle.HIGHEST_PROTOCOL)
