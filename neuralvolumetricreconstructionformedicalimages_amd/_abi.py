@@ -236,6 +236,27 @@ def check_volume(t, who, name="volume"):
         raise ValueError(f"{who}: {name} must be contiguous")
 
 
+def check_stack(t, shape, like, who, name):
+    """A stack of views or another array argument: a contiguous float32 CUDA/HIP tensor of `shape`, on `like`'s device if given."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{who}: {name} must be a CUDA/HIP tensor (no CPU path)")
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} must be float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+    if like is not None and t.device != like.device:
+        raise ValueError(f"{who}: {name} must be on the device of the other arguments")
+
+
+def check_rays(rays, like, who, whose):
+    """Rays of the library: a float32 [n, 8] CUDA/HIP tensor on the device of `like` (named `whose` in the message) -> n."""
+    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device != like.device:
+        raise RuntimeError(f"{who}: rays must be a CUDA/HIP tensor on the {whose} device")
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError(f"{who}: rays must be float32 [n, 8], got {rays.dtype} {tuple(rays.shape)}")
+    return rays.shape[0]
+
+
 def stream_ptr():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 

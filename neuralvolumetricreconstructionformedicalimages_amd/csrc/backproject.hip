@@ -3,13 +3,13 @@
 // summation order: the segment, the samples and the trilinear cell of every sample come from project_device.h, the code the forward
 // kernel runs.  Defined in include/naf_hip.h (P2) and DESIGN.md section 13.
 //
-// Layout: the forward's.  One lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave, so the 64 lanes of a wave at
-// equal k add into a small neighbourhood of the volume.  The sample spacing is half a voxel, so consecutive samples of a ray often
+// Layout of the scan kernel: scan_launch.h's, the forward's, so the 64 lanes of a wave at equal k add into a small neighbourhood of
+// the volume.  The sample spacing is half a voxel, so consecutive samples of a ray often
 // share their cell: the eight corner weights are summed in registers while the cell stays the same and go out as eight fp32 hardware
 // atomics when it changes (backproject_device.h, shared with sart.hip).  Built with -DNAF_BACKPROJECT_PER_SAMPLE every sample sends
 // its own eight atomics (the A/B of section 13).
 #include "backproject_device.h"
-#include "draw_device.h"
+#include "scan_launch.h"
 
 namespace naf {
 
@@ -24,19 +24,14 @@ backproject_rays_kernel(ProjVolume v, float *__restrict__ volume, const float *_
     scatter_ray(v, r[0], r[1], DepositValue{volume, values[i]});
 }
 
-// blockIdx.x = projection * tiles_per_projection + tile, as in project_scan_kernel.
 __global__ void __launch_bounds__(256)
 backproject_scan_kernel(ProjVolume v, float *__restrict__ volume, const float *__restrict__ projections, const float *__restrict__ poses,
-                        RayGeo g, uint32_t tiles_x, uint32_t tiles_per_proj) {
-    const uint32_t proj = blockIdx.x / tiles_per_proj, tile = blockIdx.x - proj * tiles_per_proj;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    uint32_t row, col;
-    tile_pixel(tx, ty, threadIdx.x, row, col);
-    if (row >= g.H || col >= g.W) return;
-    const uint64_t flat = (uint64_t)proj * g.W * g.H + (uint64_t)row * g.W + col;
+                        RayGeo g, uint32_t tiles_x, uint32_t tiles_per_view) {
+    ScanPixel p;
+    if (!scan_pixel(tiles_x, tiles_per_view, g, p)) return;
     float4 r[2];
-    make_ray(poses, flat, g, r);
-    scatter_ray(v, r[0], r[1], DepositValue{volume, projections[flat]});
+    make_pixel_ray(poses + (size_t)p.j * 12, p.row, p.col, g, r);
+    scatter_ray(v, r[0], r[1], DepositValue{volume, projections[(uint64_t)p.j * g.W * g.H + p.pixel]});
 }
 
 }  // namespace
@@ -65,20 +60,12 @@ extern "C" int naf_backproject_scan(const float *projections, const uint32_t *di
                                     uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
                                     float DSD, float near, float far, int parallel, float step, float *volume, void *stream) {
     if (n_projections == 0) return NAF_OK;
-    if (!dims) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: null pointer");
-    ProjVolume v;
-    const int rc = make_volume("backproject_scan", volume, dims[0], dims[1], dims[2], dvoxel, step, &v);
+    ScanLaunch s;
+    const int rc = make_scan_launch("backproject_scan", volume, {projections}, dims, dvoxel, poses, n_projections, det_w, det_h, du, dv,
+                                    ou, ov, DSD, near, far, parallel, step, &s);
     if (rc != NAF_OK) return rc;
-    if (!poses || !projections) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: null pointer");
-    if (det_w == 0 || det_h == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: empty detector");
-    if (!parallel && !(DSD > 0.0f)) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: DSD must be > 0 for a cone beam");
-    const uint32_t tiles_x = (det_w + kProjTile - 1u) / kProjTile, tiles_y = (det_h + kProjTile - 1u) / kProjTile;
-    const uint64_t per_proj = (uint64_t)tiles_x * tiles_y;
-    if (per_proj * n_projections > 0x7fffffffull)
-        return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan: too many pixels for one call");
-    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
     { ProfScope prof_("backproject_scan_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(backproject_scan_kernel, dim3((uint32_t)(per_proj * n_projections)), dim3(256), 0, (hipStream_t)stream, v,
-                         volume, projections, poses, g, tiles_x, (uint32_t)per_proj); }
+      hipLaunchKernelGGL(backproject_scan_kernel, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream, s.v, volume,
+                         projections, poses, s.g, s.tiles_x, s.tiles_per_view); }
     return check_launch("backproject_scan_kernel");
 }

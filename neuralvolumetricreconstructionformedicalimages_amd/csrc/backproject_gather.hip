@@ -7,9 +7,9 @@
 // Layout: one lane per voxel, a wave owns a 4 x 4 x 4 brick (its lanes' footprints overlap, so they read the same few rays), a
 // workgroup four bricks along z.  Per view a lane walks its footprint rectangle in (row, col) order, takes each pixel's span -- from
 // the table a pre-pass wrote into the caller's workspace, or recomputed when there is none: the same floats either way -- and sums
-// the weights of the samples of its k-range in k order.  One plain load and one plain store per voxel and output; no LDS.
-#include "project_device.h"
-#include "draw_device.h"
+// the weights of the samples of its k-range in k order.  One plain load and one plain store per voxel and output; no LDS.  The
+// checks of a scan call, its RayGeo and the view list are scan_launch.h's.
+#include "scan_launch.h"
 #include "backproject_gather_device.h"
 
 namespace naf {
@@ -25,17 +25,16 @@ struct GatherSpan {                  // what the gather needs of a RaySpan: NAF_
 static_assert(sizeof(GatherSpan) == NAF_GATHER_SPAN_BYTES, "span record size is part of the ABI");
 
 struct GatherViews {
-    const uint32_t *__restrict__ index;   // device u32, or null: the identity
+    const uint32_t *__restrict__ index;   // a ViewList's two fields
     uint32_t n_scan_views;
     uint32_t first, count;                // launch views [first, first + count) of the call
 };
 
 __device__ __forceinline__ uint32_t gather_scan_view(const GatherViews &l, uint32_t j) {
-    const uint32_t view = l.index ? l.index[j] : j;
-    return view < l.n_scan_views ? view : l.n_scan_views;
+    return scan_view(ViewList{l.index, l.n_scan_views}, l.first + j);
 }
 
-// The span of pixel (row, col) of scan view `view`, as the scatter gets it: make_ray -> ray_span.  n = 0 when it adds nothing.
+// The span of pixel (row, col) of scan view `view`, as the scatter gets it: make_pixel_ray -> ray_span.  n = 0 when it adds nothing.
 __device__ __forceinline__ void pixel_span(const ProjVolume &v, const float *__restrict__ poses, uint32_t view, uint32_t row,
                                            uint32_t col, const RayGeo &g, GatherSpan &out) {
     float4 ray[2];
@@ -60,7 +59,7 @@ gather_spans_kernel(ProjVolume v, const float *__restrict__ poses, RayGeo g, Gat
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= per_view * list.count) return;
     const uint32_t j = (uint32_t)(i / per_view), pixel = (uint32_t)(i - (uint64_t)j * per_view);
-    const uint32_t view = gather_scan_view(list, list.first + j);
+    const uint32_t view = gather_scan_view(list, j);
     GatherSpan s;
     s.n = 0u;
     if (view < list.n_scan_views) pixel_span(v, poses, view, pixel / g.W, pixel % g.W, g, s);
@@ -93,7 +92,7 @@ backproject_gather_kernel(ProjVolume v, GatherGrid grid, float *__restrict__ num
     const uint64_t per_view = (uint64_t)g.W * g.H;
     float acc = num[voxel], dacc = kDen ? den[voxel] : 0.0f;
     for (uint32_t j = 0; j < list.count; ++j) {
-        const uint32_t view = gather_scan_view(list, list.first + j);
+        const uint32_t view = gather_scan_view(list, j);
         if (view >= list.n_scan_views) continue;
         const GatherRect r = gather_footprint(lo, hi, poses + (size_t)view * 12, det);
         float s_num = 0.0f, s_den = 0.0f;
@@ -153,19 +152,16 @@ extern "C" int naf_backproject_scan_gather(const float *values, const uint32_t *
                                            size_t workspace_bytes, void *stream) {
     if (n_sub == 0) return NAF_OK;
     const char *who = "backproject_scan_gather";
-    if (!dims) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_scan_gather: null pointer");
-    ProjVolume v;
-    const int rc = make_volume(who, volume, dims[0], dims[1], dims[2], dvoxel, step, &v);
+    ScanLaunch s;
+    const int rc = make_scan_launch(who, volume, {values}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou, ov, DSD, near, far,
+                                    parallel, step, &s, kScanVoxels, view_index, n_scan_views);
     if (rc != NAF_OK) return rc;
+    const ProjVolume &v = s.v;
+    const RayGeo &g = s.g;
     const uint64_t per_view = (uint64_t)det_w * det_h;
     const uint64_t bricks_x = (dims[0] + 3u) / 4u, bricks_y = (dims[1] + 3u) / 4u, blocks_z = (dims[2] + 15u) / 16u;
     const char *what = nullptr;
-    if (!poses || !values) what = "null pointer";
-    else if (det_w == 0 || det_h == 0) what = "empty detector";
-    else if (!parallel && !(DSD > 0.0f)) what = "DSD must be > 0 for a cone beam";
-    else if (!(du != 0.0f) || !(dv != 0.0f) || !std::isfinite(du) || !std::isfinite(dv)) what = "pixel pitch must be finite and not 0";
-    else if (!view_index && n_sub > n_scan_views) what = "without a view list n_sub must be <= n_scan_views";
-    else if (n_scan_views == 0) what = "a scan of zero views";
+    if (!(du != 0.0f) || !(dv != 0.0f) || !std::isfinite(du) || !std::isfinite(dv)) what = "pixel pitch must be finite and not 0";
     else if (den == volume) what = "volume and den must be two volumes";
     else if (per_view > 0x7fffffffull) what = "too many pixels in a view";
     else if (bricks_x * bricks_y * blocks_z > 0x7fffffffull) what = "too many voxels for one call";
@@ -176,7 +172,6 @@ extern "C" int naf_backproject_scan_gather(const float *values, const uint32_t *
         std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
         return fail(NAF_ERR_INVALID_ARGUMENT, msg);
     }
-    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
     GatherGrid grid;
     for (int a = 0; a < 3; ++a) {
         grid.n[a] = v.n[a];

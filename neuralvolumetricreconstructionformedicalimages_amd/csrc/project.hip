@@ -2,12 +2,9 @@
 // pixel ray of a scan (naf_project_scan).  It makes training scans from CT volumes, the job TIGRE's `Ax` does for the reference's
 // dataGenerator/generateData.py.  The projection it computes is defined in include/naf_hip.h and DESIGN.md section 10.
 //
-// Layout: one lane per detector pixel, and a wave's 64 pixels form an 8 x 8 patch of the detector (a workgroup of four waves
-// covers 16 x 16 pixels), so that the samples of neighbouring rays at equal k land in the same or neighbouring cache lines.
-// Built with -DNAF_PROJECT_ROW_STRIP the scan kernel takes 256 consecutive pixels of a detector row per workgroup instead
-// (the layout A/B of DESIGN.md section 10).
-#include "draw_device.h"
-#include "project_device.h"
+// Layout of the scan kernel: scan_launch.h's.  Built with -DNAF_PROJECT_ROW_STRIP it takes 256 consecutive pixels of a detector row
+// per workgroup instead (the layout A/B of DESIGN.md section 10).
+#include "scan_launch.h"
 
 namespace naf {
 
@@ -31,33 +28,21 @@ project_rays_kernel(ProjVolume v, const float *__restrict__ rays, float *__restr
     out[i] = line_integral(v, r[0], r[1]);
 }
 
-constexpr uint32_t kTile = kProjTile; // 2-D layout: 16 x 16 pixels per workgroup, 8 x 8 per wave
-constexpr uint32_t kStrip = 256;     // row-strip layout: 256 pixels of one row per workgroup
-
 #ifdef NAF_PROJECT_ROW_STRIP
-constexpr bool kRowStrip = true;
+constexpr ScanLayout kLayout = kScanRowStrip;
 #else
-constexpr bool kRowStrip = false;
+constexpr ScanLayout kLayout = kScanTiles;
 #endif
 
-// blockIdx.x = projection * tiles_per_projection + tile; the projection's poses and output come pre-offset per launch.
+// The launch's poses and output come pre-offset to its first view.
 __global__ void __launch_bounds__(256)
 project_scan_kernel(ProjVolume v, const float *__restrict__ poses, RayGeo g, float *__restrict__ out, uint32_t tiles_x,
-                    uint32_t tiles_per_proj) {
-    const uint32_t proj = blockIdx.x / tiles_per_proj, tile = blockIdx.x - proj * tiles_per_proj;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    uint32_t row, col;
-    if (kRowStrip) {
-        row = ty;
-        col = tx * kStrip + threadIdx.x;
-    } else {
-        tile_pixel(tx, ty, threadIdx.x, row, col);
-    }
-    if (row >= g.H || col >= g.W) return;
-    const uint64_t flat = (uint64_t)proj * g.W * g.H + (uint64_t)row * g.W + col;
+                    uint32_t tiles_per_view) {
+    ScanPixel p;
+    if (!scan_pixel<kLayout>(tiles_x, tiles_per_view, g, p)) return;
     float4 r[2];
-    make_ray(poses, flat, g, r);
-    out[flat] = line_integral(v, r[0], r[1]);
+    make_pixel_ray(poses + (size_t)p.j * 12, p.row, p.col, g, r);
+    out[(uint64_t)p.j * g.W * g.H + p.pixel] = line_integral(v, r[0], r[1]);
 }
 
 }  // namespace
@@ -85,20 +70,12 @@ extern "C" int naf_project_scan(const float *volume, const uint32_t *dims, const
                                 uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
                                 float DSD, float near, float far, int parallel, float step, float *out, void *stream) {
     if (n_projections == 0) return NAF_OK;
-    if (!dims) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan: null pointer");
-    ProjVolume v;
-    const int rc = make_volume("project_scan", volume, dims[0], dims[1], dims[2], dvoxel, step, &v);
+    ScanLaunch s;
+    const int rc = make_scan_launch("project_scan", volume, {out}, dims, dvoxel, poses, n_projections, det_w, det_h, du, dv, ou, ov, DSD,
+                                    near, far, parallel, step, &s, kLayout);
     if (rc != NAF_OK) return rc;
-    if (!poses || !out) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan: null pointer");
-    if (det_w == 0 || det_h == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan: empty detector");
-    if (!parallel && !(DSD > 0.0f)) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan: DSD must be > 0 for a cone beam");
-    const uint32_t tiles_x = kRowStrip ? (det_w + kStrip - 1u) / kStrip : (det_w + kTile - 1u) / kTile;
-    const uint32_t tiles_y = kRowStrip ? det_h : (det_h + kTile - 1u) / kTile;
-    const uint64_t per_proj = (uint64_t)tiles_x * tiles_y;
-    if (per_proj * n_projections > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan: too many pixels for one call");
-    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
     { ProfScope prof_("project_scan_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(project_scan_kernel, dim3((uint32_t)(per_proj * n_projections)), dim3(256), 0, (hipStream_t)stream, v, poses, g,
-                         out, tiles_x, (uint32_t)per_proj); }
+      hipLaunchKernelGGL(project_scan_kernel, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream, s.v, poses,
+                         s.g, out, s.tiles_x, s.tiles_per_view); }
     return check_launch("project_scan_kernel");
 }

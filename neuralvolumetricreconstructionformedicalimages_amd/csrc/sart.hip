@@ -5,47 +5,29 @@
 // The forward half is project.hip's (project_device.h: ray_span, span_point, span_sum), the transpose half backproject.hip's
 // (backproject_device.h: scatter_ray with the paired deposit), so a subset step is A and A^T of P1 / P2 restricted to the list.
 //
-// Layout of the two scan kernels: P1's.  One lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave; launch view j
-// is scan view view_index[j] (j itself without a list), whose pose, pixel rays and measured values are read in place from the whole
-// scan, so no subset is ever gathered.
+// Layout of the two scan kernels: scan_launch.h's.  Launch view j is scan view view_index[j] (j itself without a list), whose pose,
+// pixel rays and measured values are read in place from the whole scan, so no subset is ever gathered.
 #include "backproject_device.h"
-#include "draw_device.h"
+#include "scan_launch.h"
 
 namespace naf {
 
 namespace {
 
-struct ViewList {
-    const uint32_t *__restrict__ index;   // device u32 [n_sub], or null: the identity
-    uint32_t n_scan_views;
-};
-
-// Scan view of launch view j, or n_scan_views (no such view) when the list holds an index outside the scan.
-__device__ __forceinline__ uint32_t scan_view(const ViewList &l, uint32_t j) {
-    const uint32_t view = l.index ? l.index[j] : j;
-    return view < l.n_scan_views ? view : l.n_scan_views;
-}
-
-// blockIdx.x = launch view * tiles_per_projection + tile, as in project_scan_kernel.
 __global__ void __launch_bounds__(256)
 sart_residual_scan_kernel(ProjVolume v, const float *__restrict__ poses, RayGeo g, ViewList list,
                           const float *__restrict__ projections, float *__restrict__ y, float *__restrict__ r, uint32_t tiles_x,
-                          uint32_t tiles_per_proj) {
-    const uint32_t j = blockIdx.x / tiles_per_proj, tile = blockIdx.x - j * tiles_per_proj;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    uint32_t row, col;
-    tile_pixel(tx, ty, threadIdx.x, row, col);
-    if (row >= g.H || col >= g.W) return;
-    const uint64_t per_view = (uint64_t)g.W * g.H, pixel = (uint64_t)row * g.W + col;
-    const uint64_t out = (uint64_t)j * per_view + pixel;
-    const uint32_t view = scan_view(list, j);
+                          uint32_t tiles_per_view) {
+    ScanPixel p;
+    if (!scan_pixel(tiles_x, tiles_per_view, g, p)) return;
+    const uint64_t per_view = (uint64_t)g.W * g.H;
+    const uint32_t view = scan_view(list, p.j);
     const float nan = __builtin_nanf("");
     float res = nan, weighted = nan;                          // a view outside the scan: nothing is read through it
     if (view < list.n_scan_views) {
-        const uint64_t flat = (uint64_t)view * per_view + pixel;
-        const float b = projections[flat];
+        const float b = projections[(uint64_t)view * per_view + p.pixel];
         float4 ray[2];
-        make_ray(poses, flat, g, ray);
+        make_pixel_ray(poses + (size_t)view * 12, p.row, p.col, g, ray);
         RaySpan s;
         const SpanKind kind = ray_span(v, ray[0], ray[1], s);
         if (kind == kSpanEmpty) {
@@ -56,24 +38,21 @@ sart_residual_scan_kernel(ProjVolume v, const float *__restrict__ poses, RayGeo 
             weighted = res / s.len;
         }
     }
+    const uint64_t out = (uint64_t)p.j * per_view + p.pixel;
     y[out] = weighted;
     if (r) r[out] = res;
 }
 
 __global__ void __launch_bounds__(256)
 sart_backproject_scan_kernel(ProjVolume v, float *__restrict__ num, float *__restrict__ den, const float *__restrict__ y,
-                             const float *__restrict__ poses, RayGeo g, ViewList list, uint32_t tiles_x, uint32_t tiles_per_proj) {
-    const uint32_t j = blockIdx.x / tiles_per_proj, tile = blockIdx.x - j * tiles_per_proj;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    uint32_t row, col;
-    tile_pixel(tx, ty, threadIdx.x, row, col);
-    if (row >= g.H || col >= g.W) return;
-    const uint32_t view = scan_view(list, j);
+                             const float *__restrict__ poses, RayGeo g, ViewList list, uint32_t tiles_x, uint32_t tiles_per_view) {
+    ScanPixel p;
+    if (!scan_pixel(tiles_x, tiles_per_view, g, p)) return;
+    const uint32_t view = scan_view(list, p.j);
     if (view >= list.n_scan_views) return;
-    const uint64_t per_view = (uint64_t)g.W * g.H, pixel = (uint64_t)row * g.W + col;
     float4 ray[2];
-    make_ray(poses, (uint64_t)view * per_view + pixel, g, ray);
-    scatter_ray(v, ray[0], ray[1], DepositPair{num, den, y[(uint64_t)j * per_view + pixel]});
+    make_pixel_ray(poses + (size_t)view * 12, p.row, p.col, g, ray);
+    scatter_ray(v, ray[0], ray[1], DepositPair{num, den, y[(uint64_t)p.j * g.W * g.H + p.pixel]});
 }
 
 struct UpdateArgs {
@@ -124,35 +103,6 @@ sart_update_kernel(float *__restrict__ x, float *__restrict__ num, float *__rest
     }
 }
 
-// The checks and the launch grid the two scan kernels share.  `volume` is any of the call's volume pointers (checked for null).
-int scan_launch(const char *who, const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses,
-                const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views, uint32_t det_w, uint32_t det_h, float DSD,
-                int parallel, float step, ProjVolume *v, uint32_t *tiles_x, uint32_t *per_proj) {
-    char msg[160];
-    if (!dims) {
-        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    const int rc = make_volume(who, volume, dims[0], dims[1], dims[2], dvoxel, step, v);
-    if (rc != NAF_OK) return rc;
-    const char *what = nullptr;
-    const uint32_t tx = (det_w + kProjTile - 1u) / kProjTile, ty = (det_h + kProjTile - 1u) / kProjTile;
-    const uint64_t tiles = (uint64_t)tx * ty;
-    if (!poses) what = "null pointer";
-    else if (det_w == 0 || det_h == 0) what = "empty detector";
-    else if (!parallel && !(DSD > 0.0f)) what = "DSD must be > 0 for a cone beam";
-    else if (!view_index && n_sub > n_scan_views) what = "without a view list n_sub must be <= n_scan_views";
-    else if (n_scan_views == 0) what = "a scan of zero views";
-    else if (tiles * n_sub > 0x7fffffffull) what = "too many pixels for one call";
-    if (what) {
-        std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    *tiles_x = tx;
-    *per_proj = (uint32_t)tiles;
-    return NAF_OK;
-}
-
 }  // namespace
 
 }  // namespace naf
@@ -164,16 +114,13 @@ extern "C" int naf_sart_residual_scan(const float *volume, const uint32_t *dims,
                                       float far, int parallel, float step, const uint32_t *view_index, uint32_t n_scan_views,
                                       const float *projections, float *y, float *r, void *stream) {
     if (n_sub == 0) return NAF_OK;
-    ProjVolume v;
-    uint32_t tiles_x, per_proj;
-    const int rc = scan_launch("sart_residual_scan", volume, dims, dvoxel, poses, view_index, n_sub, n_scan_views, det_w, det_h, DSD,
-                               parallel, step, &v, &tiles_x, &per_proj);
+    ScanLaunch s;
+    const int rc = make_scan_launch("sart_residual_scan", volume, {projections, y}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou,
+                                    ov, DSD, near, far, parallel, step, &s, kScanTiles, view_index, n_scan_views);
     if (rc != NAF_OK) return rc;
-    if (!projections || !y) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_residual_scan: null pointer");
-    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
     { ProfScope prof_("sart_residual_scan_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(sart_residual_scan_kernel, dim3(per_proj * n_sub), dim3(256), 0, (hipStream_t)stream, v, poses, g,
-                         ViewList{view_index, n_scan_views}, projections, y, r, tiles_x, per_proj); }
+      hipLaunchKernelGGL(sart_residual_scan_kernel, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream, s.v, poses, s.g,
+                         ViewList{view_index, n_scan_views}, projections, y, r, s.tiles_x, s.tiles_per_view); }
     return check_launch("sart_residual_scan_kernel");
 }
 
@@ -182,17 +129,14 @@ extern "C" int naf_sart_backproject_scan(const float *y, const uint32_t *view_in
                                          float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel,
                                          float step, float *num, float *den, void *stream) {
     if (n_sub == 0) return NAF_OK;
-    ProjVolume v;
-    uint32_t tiles_x, per_proj;
-    const int rc = scan_launch("sart_backproject_scan", num, dims, dvoxel, poses, view_index, n_sub, n_scan_views, det_w, det_h, DSD,
-                               parallel, step, &v, &tiles_x, &per_proj);
+    ScanLaunch s;
+    const int rc = make_scan_launch("sart_backproject_scan", num, {y}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou, ov, DSD,
+                                    near, far, parallel, step, &s, kScanTiles, view_index, n_scan_views);
     if (rc != NAF_OK) return rc;
-    if (!y) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_backproject_scan: null pointer");
     if (den == num) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_backproject_scan: num and den must be two volumes");
-    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
     { ProfScope prof_("sart_backproject_scan_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(sart_backproject_scan_kernel, dim3(per_proj * n_sub), dim3(256), 0, (hipStream_t)stream, v, num, den, y, poses,
-                         g, ViewList{view_index, n_scan_views}, tiles_x, per_proj); }
+      hipLaunchKernelGGL(sart_backproject_scan_kernel, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream, s.v, num, den,
+                         y, poses, s.g, ViewList{view_index, n_scan_views}, s.tiles_x, s.tiles_per_view); }
     return check_launch("sart_backproject_scan_kernel");
 }
 

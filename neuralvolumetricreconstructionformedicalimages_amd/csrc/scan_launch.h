@@ -1,0 +1,98 @@
+// scan_launch.h -- what the six scan entry points (naf_project_scan, naf_project_scan_siddon, naf_backproject_scan,
+// naf_sart_residual_scan, naf_sart_backproject_scan, naf_backproject_scan_gather) share: the host checks of "a scan is ..." with the
+// launch grid, the view list, and the decode of a workgroup into a detector pixel.
+//
+// Layout of the five tile kernels: one lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave, so that the samples of
+// neighbouring rays at equal k land in the same or neighbouring cache lines; blockIdx.x = launch view * tiles_per_view + tile.  The
+// gather launches over voxels and takes only the checks and the RayGeo from here.
+#pragma once
+
+#include <initializer_list>
+
+#include "draw_device.h"
+#include "project_device.h"
+
+namespace naf {
+
+struct ViewList {
+    const uint32_t *__restrict__ index;   // device u32 [n_sub], or null: the identity
+    uint32_t n_scan_views;
+};
+
+// Scan view of launch view j, or n_scan_views (no such view: it adds nothing) when the list holds an index outside the scan.
+__device__ __forceinline__ uint32_t scan_view(const ViewList &l, uint32_t j) {
+    const uint32_t view = l.index ? l.index[j] : j;
+    return view < l.n_scan_views ? view : l.n_scan_views;
+}
+
+enum ScanLayout {
+    kScanTiles,      // 16 x 16 pixels per workgroup
+    kScanRowStrip,   // 256 consecutive pixels of one detector row per workgroup (project.hip's A/B)
+    kScanVoxels,     // no pixel grid: the launch is over the volume
+};
+constexpr uint32_t kScanStrip = 256;
+
+struct ScanLaunch {
+    ProjVolume v;
+    RayGeo g;
+    uint32_t tiles_x, tiles_per_view;   // the grid is tiles_per_view * n_sub workgroups of 256
+};
+
+// Host: the checks of a scan call and what its launch needs.  `volume` is any of the call's volume pointers and `others` its
+// further device pointers, all checked for null.  Without a view list, launch view j is scan view j.
+inline int make_scan_launch(const char *who, const float *volume, std::initializer_list<const void *> others, const uint32_t *dims,
+                            const float *dvoxel, const float *poses, uint32_t n_sub, uint32_t det_w, uint32_t det_h, float du, float dv,
+                            float ou, float ov, float DSD, float near, float far, int parallel, float step, ScanLaunch *s,
+                            ScanLayout layout = kScanTiles, const uint32_t *view_index = nullptr, uint32_t n_scan_views = 0xffffffffu) {
+    char msg[160];
+    if (!dims) {
+        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    const int rc = make_volume(who, volume, dims[0], dims[1], dims[2], dvoxel, step, &s->v);
+    if (rc != NAF_OK) return rc;
+    const uint32_t tile_w = layout == kScanRowStrip ? kScanStrip : kProjTile, tile_h = layout == kScanRowStrip ? 1u : kProjTile;
+    const uint32_t tx = (det_w + tile_w - 1u) / tile_w, ty = (det_h + tile_h - 1u) / tile_h;
+    const uint64_t tiles = layout == kScanVoxels ? 0u : (uint64_t)tx * ty;
+    const char *what = nullptr;
+    bool null = !poses;
+    for (const void *p : others) null |= !p;
+    if (null) what = "null pointer";
+    else if (det_w == 0 || det_h == 0) what = "empty detector";
+    else if (!parallel && !(DSD > 0.0f)) what = "DSD must be > 0 for a cone beam";
+    else if (!view_index && n_sub > n_scan_views) what = "without a view list n_sub must be <= n_scan_views";
+    else if (n_scan_views == 0) what = "a scan of zero views";
+    else if (tiles * n_sub > 0x7fffffffull) what = "too many pixels for one call";
+    if (what) {
+        std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    s->g = RayGeo{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
+    s->tiles_x = tx;
+    s->tiles_per_view = (uint32_t)tiles;
+    return NAF_OK;
+}
+
+struct ScanPixel {
+    uint32_t j, row, col;   // launch view, detector row and column
+    uint64_t pixel;         // row * W + col
+};
+
+// Device: the pixel of this lane, from blockIdx.x and threadIdx.x.  False outside the detector (a ragged last tile).
+template <ScanLayout kLayout = kScanTiles>
+__device__ __forceinline__ bool scan_pixel(uint32_t tiles_x, uint32_t tiles_per_view, const RayGeo &g, ScanPixel &p) {
+    p.j = blockIdx.x / tiles_per_view;
+    const uint32_t tile = blockIdx.x - p.j * tiles_per_view;
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    if (kLayout == kScanRowStrip) {
+        p.row = ty;
+        p.col = tx * kScanStrip + threadIdx.x;
+    } else {
+        tile_pixel(tx, ty, threadIdx.x, p.row, p.col);
+    }
+    if (p.row >= g.H || p.col >= g.W) return false;
+    p.pixel = (uint64_t)p.row * g.W + p.col;
+    return true;
+}
+
+}  // namespace naf

@@ -3,10 +3,8 @@
 // model beside project.hip's interpolated one: exact chord lengths per voxel, no sampling step.  The projection is defined in
 // include/naf_hip.h (P6) and DESIGN.md section 20; the traversal is csrc/siddon_device.h.
 //
-// Layout: project.hip's.  One lane per detector pixel, a wave's 64 pixels an 8 x 8 patch of the detector (16 x 16 per workgroup),
-// rays made in registers by make_ray: neighbouring lanes walk neighbouring voxels.
-#include "draw_device.h"
-#include "project_device.h"
+// Layout of the scan kernel: scan_launch.h's, rays made in registers: neighbouring lanes walk neighbouring voxels.
+#include "scan_launch.h"
 #include "siddon_device.h"
 
 namespace naf {
@@ -32,19 +30,15 @@ siddon_rays_kernel(SiddonVolume v, const float *__restrict__ rays, float *__rest
     out[i] = siddon_ray(v, r[0], r[1]);
 }
 
-// blockIdx.x = projection * tiles_per_projection + tile; the projection's poses and output come pre-offset per launch.
+// The launch's poses and output come pre-offset to its first view.
 __global__ void __launch_bounds__(256)
 siddon_scan_kernel(SiddonVolume v, const float *__restrict__ poses, RayGeo g, float *__restrict__ out, uint32_t tiles_x,
-                   uint32_t tiles_per_proj) {
-    const uint32_t proj = blockIdx.x / tiles_per_proj, tile = blockIdx.x - proj * tiles_per_proj;
-    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    uint32_t row, col;
-    tile_pixel(tx, ty, threadIdx.x, row, col);
-    if (row >= g.H || col >= g.W) return;
-    const uint64_t flat = (uint64_t)proj * g.W * g.H + (uint64_t)row * g.W + col;
+                   uint32_t tiles_per_view) {
+    ScanPixel p;
+    if (!scan_pixel(tiles_x, tiles_per_view, g, p)) return;
     float4 r[2];
-    make_ray(poses, flat, g, r);
-    out[flat] = siddon_ray(v, r[0], r[1]);
+    make_pixel_ray(poses + (size_t)p.j * 12, p.row, p.col, g, r);
+    out[(uint64_t)p.j * g.W * g.H + p.pixel] = siddon_ray(v, r[0], r[1]);
 }
 
 // The argument checks of P1's make_volume (there is no sample step here).
@@ -83,20 +77,14 @@ extern "C" int naf_project_scan_siddon(const float *volume, const uint32_t *dims
                                        uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
                                        float DSD, float near, float far, int parallel, float *out, void *stream) {
     if (n_projections == 0) return NAF_OK;
-    if (!dims) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan_siddon: null pointer");
-    SiddonVolume v;
-    const int rc = make_siddon_volume("project_scan_siddon", volume, dims[0], dims[1], dims[2], dvoxel, &v);
+    ScanLaunch s;                                               // there is no sample step here: any valid one passes the checks
+    const int rc = make_scan_launch("project_scan_siddon", volume, {out}, dims, dvoxel, poses, n_projections, det_w, det_h, du, dv, ou,
+                                    ov, DSD, near, far, parallel, 1.0f, &s);
     if (rc != NAF_OK) return rc;
-    if (!poses || !out) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan_siddon: null pointer");
-    if (det_w == 0 || det_h == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan_siddon: empty detector");
-    if (!parallel && !(DSD > 0.0f)) return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan_siddon: DSD must be > 0 for a cone beam");
-    const uint32_t tiles_x = (det_w + kProjTile - 1u) / kProjTile, tiles_y = (det_h + kProjTile - 1u) / kProjTile;
-    const uint64_t per_proj = (uint64_t)tiles_x * tiles_y;
-    if (per_proj * n_projections > 0x7fffffffull)
-        return fail(NAF_ERR_INVALID_ARGUMENT, "project_scan_siddon: too many pixels for one call");
-    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
+    SiddonVolume v{volume};
+    siddon_grid(dims[0], dims[1], dims[2], dvoxel, &v.grid);
     { ProfScope prof_("siddon_scan_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(siddon_scan_kernel, dim3((uint32_t)(per_proj * n_projections)), dim3(256), 0, (hipStream_t)stream, v, poses, g,
-                         out, tiles_x, (uint32_t)per_proj); }
+      hipLaunchKernelGGL(siddon_scan_kernel, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream, v, poses, s.g,
+                         out, s.tiles_x, s.tiles_per_view); }
     return check_launch("siddon_scan_kernel");
 }

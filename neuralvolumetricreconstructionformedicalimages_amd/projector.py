@@ -57,18 +57,100 @@ def check_kind(kind, who):
     return kind
 
 
+class Scan:
+    """What every call on one scan shares, made once: the poses of all views on the device and the geometry arguments, with one
+    method per scan entry point of the library that owns its argument list."""
+
+    def __init__(self, geo, angles, device):
+        self.geo = geo
+        self.angles = np.asarray(angles, dtype=np.float64).reshape(-1)
+        self.raygen = RayGenerator(geo, self.angles, device)
+        self.device = self.raygen.poses.device              # with its index, as tensors report it
+        self.N, self.H, self.W = len(self.angles), self.raygen.H, self.raygen.W
+        self.dims = tuple(int(v) for v in geo.nVoxel)
+        self._cdims = (ctypes.c_uint32 * 3)(*self.dims)
+        self._dvoxel = _dvoxel(geo.dVoxel)
+        self._step = sample_step(geo.dVoxel, geo.accuracy)
+
+    def detector_args(self):
+        g = self.geo
+        return (self.W, self.H, float(g.dDetector[0]), float(g.dDetector[1]), float(g.offDetector[0]), float(g.offDetector[1]),
+                float(g.DSD), float(self.raygen.near), float(self.raygen.far), int(g.mode == "parallel"), self._step)
+
+    def _grid_and_poses(self, first=0):
+        return ctypes.byref(self._cdims), ctypes.byref(self._dvoxel), _abi.ptr(self.raygen.poses[first:])
+
+    def project(self, volume, out, first, count, kind):
+        """out[first:first + count] = A volume for those views."""
+        args = (_abi.ptr(volume), *self._grid_and_poses(first), count, *self.detector_args())
+        dst = _abi.ptr(out[first:first + count])
+        if kind == "siddon":                                    # no sample step
+            _abi.check(_abi.lib().naf_project_scan_siddon(*args[:-1], dst, _abi.stream_ptr()), "project_scan_siddon")
+        else:
+            _abi.check(_abi.lib().naf_project_scan(*args, dst, _abi.stream_ptr()), "project_scan")
+
+    def backproject(self, projections, out, first, count):
+        """out += A^T projections over the views [first, first + count), by the scatter."""
+        _abi.check(_abi.lib().naf_backproject_scan(
+            _abi.ptr(projections[first:first + count]), *self._grid_and_poses(first), count, *self.detector_args(), _abi.ptr(out),
+            _abi.stream_ptr()), "backproject_scan")
+
+    def residual(self, volume, views, m, projections, y, r):
+        _abi.check(_abi.lib().naf_sart_residual_scan(
+            _abi.ptr(volume), *self._grid_and_poses(), m, *self.detector_args(), _index_ptr(views), self.N, _abi.ptr(projections),
+            _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr()), "sart_residual_scan")
+
+    def backproject_views(self, y, views, m, num, den):
+        _abi.check(_abi.lib().naf_sart_backproject_scan(
+            _abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self.detector_args(), _abi.ptr(num), _abi.ptr(den),
+            _abi.stream_ptr()), "sart_backproject_scan")
+
+    def gather(self, values, views, m, num, den, workspace, first=0, n_scan_views=None):
+        """The gather transpose of `m` launch views: a view list into the whole scan, or without one the views from `first` on."""
+        _abi.check(_abi.lib().naf_backproject_scan_gather(
+            _abi.ptr(values), _index_ptr(views), m, self.N if n_scan_views is None else n_scan_views, *self._grid_and_poses(first),
+            *self.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.ptr(workspace), 0 if workspace is None else workspace.numel(),
+            _abi.stream_ptr()), "backproject_scan_gather")
+
+
+class ViewList:
+    """A list of views of an N-view scan, checked on the host (every index in [0, N)) and held on the device as well."""
+
+    def __init__(self, views, n_views, device):
+        idx = np.asarray(views).reshape(-1)
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError(f"sart: view indices must be integers, got {idx.dtype}")
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= n_views):
+            raise ValueError(f"sart: view index out of range for a scan of {n_views} views: {idx.tolist()}")
+        self.host, self.n_views = idx, int(n_views)
+        self.device = torch.tensor(idx.astype(np.int32), device=device) if idx.size else None      # the same bits as u32
+
+    def __len__(self):
+        return int(self.host.size)
+
+
+def _index_ptr(views):
+    return None if views is None else _abi.ptr(views.device)
+
+
+def scan_for(geo, angles, device, scan, who):
+    """`scan` if given (it must be of this `geo` and `device`), else a new Scan."""
+    if scan is None:
+        return Scan(geo, angles, device)
+    if scan.geo is not geo or scan.device != device:
+        raise ValueError(f"{who}: `scan` was made for another geometry or device")
+    return scan
+
+
 def project_rays(volume, dvoxel, rays, accuracy=0.5, out=None, kind="interpolated"):
     """Line integrals of `volume` [n1, n2, n3] (voxel size `dvoxel` in metres) along `rays` [n, 8] -> float32 [n].
     `kind="siddon"` integrates exact chord lengths through piecewise-constant voxels (P6); `accuracy` is ignored then."""
     check_kind(kind, "project_rays")
     _check_volume(volume)
-    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device != volume.device:
-        raise RuntimeError("project_rays: rays must be a CUDA/HIP tensor on the volume's device")
-    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-        raise ValueError(f"project_rays: rays must be float32 [n, 8], got {rays.dtype} {tuple(rays.shape)}")
+    n = _abi.check_rays(rays, volume, "project_rays", "volume's")
     if not rays.is_contiguous():
         raise ValueError("project_rays: rays must be contiguous")
-    n = rays.shape[0]
     if out is None:
         out = torch.empty(n, device=volume.device, dtype=torch.float32)
     elif out.shape != (n,) or out.dtype != torch.float32 or out.device != volume.device or not out.is_contiguous():
@@ -92,42 +174,24 @@ def check_geometry(volume, geo):
         raise ValueError(f"projector: volume shape {tuple(volume.shape)} does not match nVoxel {want}")
 
 
-def project_scan(volume, geo, angles, views_per_call=None, kind="interpolated"):
+def project_scan(volume, geo, angles, views_per_call=None, kind="interpolated", scan=None):
     """Projections of `volume` for the scan geometry `geo` (ConeGeometry) at `angles` (radians) -> float32 [N, H, W] on the
     volume's device.  Views go to the kernel in groups of `views_per_call` (default: as many as fit MAX_PIXELS_PER_CALL).
-    `kind="siddon"` integrates exact chord lengths through piecewise-constant voxels (P6); `geo.accuracy` is ignored then."""
+    `kind="siddon"` integrates exact chord lengths through piecewise-constant voxels (P6); `geo.accuracy` is ignored then.
+    `scan` is a `Scan` of the same `geo` and `angles` to reuse across calls."""
     check_kind(kind, "project_scan")
     _check_volume(volume)
     check_geometry(volume, geo)
-    angles = np.asarray(angles, dtype=np.float64).reshape(-1)
-    raygen = RayGenerator(geo, angles, volume.device)
-    N, H, W = len(angles), raygen.H, raygen.W
+    scan = scan_for(geo, angles, volume.device, scan, "projector")
+    N, H, W = scan.N, scan.H, scan.W
     out = torch.empty(N, H, W, device=volume.device, dtype=torch.float32)
-    if N == 0:
-        return out
     per_call = views_per_call or max(1, MAX_PIXELS_PER_CALL // (H * W))
-    dims = (ctypes.c_uint32 * 3)(*[int(v) for v in volume.shape])
-    dv = _dvoxel(geo.dVoxel)
-    step = sample_step(geo.dVoxel, geo.accuracy)
-    lib = _abi.lib()
     for first in range(0, N, per_call):
-        count = min(per_call, N - first)
-        if kind == "siddon":
-            _abi.check(lib.naf_project_scan_siddon(
-                _abi.ptr(volume), ctypes.byref(dims), ctypes.byref(dv), _abi.ptr(raygen.poses[first:first + count]), count, W, H,
-                float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]),
-                float(geo.DSD), float(raygen.near), float(raygen.far), int(geo.mode == "parallel"),
-                _abi.ptr(out[first:first + count]), _abi.stream_ptr()), "project_scan_siddon")
-            continue
-        _abi.check(lib.naf_project_scan(
-            _abi.ptr(volume), ctypes.byref(dims), ctypes.byref(dv), _abi.ptr(raygen.poses[first:first + count]), count, W, H,
-            float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]), float(geo.DSD),
-            float(raygen.near), float(raygen.far), int(geo.mode == "parallel"), step, _abi.ptr(out[first:first + count]),
-            _abi.stream_ptr()), "project_scan")
+        scan.project(volume, out, first, min(per_call, N - first), kind)
     return out
 
 
-def _check_out(out, shape, like, who):
+def check_out(out, shape, like, who):
     """`out=None` allocates zeros; a given `out` is accumulated into."""
     if out is None:
         return torch.zeros(shape, device=like.device, dtype=torch.float32)
@@ -144,11 +208,7 @@ def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None):
     (`backproject_scan(..., method="gather")`) exists for scans."""
     if not isinstance(values, torch.Tensor) or not values.is_cuda:
         raise RuntimeError("backproject_rays: values must be a CUDA/HIP tensor (no CPU path)")
-    if not isinstance(rays, torch.Tensor) or not rays.is_cuda or rays.device != values.device:
-        raise RuntimeError("backproject_rays: rays must be a CUDA/HIP tensor on the values' device")
-    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-        raise ValueError(f"backproject_rays: rays must be float32 [n, 8], got {rays.dtype} {tuple(rays.shape)}")
-    n = rays.shape[0]
+    n = _abi.check_rays(rays, values, "backproject_rays", "values'")
     if values.dtype != torch.float32 or tuple(values.shape) != (n,):
         raise ValueError(f"backproject_rays: values must be float32 [{n}], got {values.dtype} {tuple(values.shape)}")
     if not rays.is_contiguous() or not values.is_contiguous():
@@ -156,7 +216,7 @@ def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None):
     dims = tuple(int(v) for v in dims)
     if len(dims) != 3 or min(dims) < 1:
         raise ValueError(f"backproject_rays: dims must be three positive extents, got {dims}")
-    out = _check_out(out, dims, values, "backproject_rays")
+    out = check_out(out, dims, values, "backproject_rays")
     _abi.check(_abi.lib().naf_backproject_rays(_abi.ptr(values), _abi.ptr(rays), n, dims[0], dims[1], dims[2],
                                                ctypes.byref(_dvoxel(dvoxel)), sample_step(dvoxel, accuracy), _abi.ptr(out),
                                                _abi.stream_ptr()), "backproject_rays")
@@ -179,45 +239,27 @@ def gather_workspace(n_views, H, W, device, span_table=True):
     return torch.empty(views * per_view, device=device, dtype=torch.uint8)
 
 
-def backproject_scan(projections, geo, angles, views_per_call=None, out=None, method="scatter", span_table=True):
+def backproject_scan(projections, geo, angles, views_per_call=None, out=None, method="scatter", span_table=True, scan=None):
     """Transpose of `project_scan`: adds `projections` [N, H, W] of the scan geometry `geo` at `angles` into a volume on the voxel
     grid of `geo` -> float32 nVoxel.  Views go to the kernel in groups of `views_per_call` like `project_scan`'s.
     `method="scatter"` (the default) is the ray scatter on fp32 atomics, equal to A^T y up to summation order; `method="gather"`
     is the same operator evaluated per voxel in a fixed order with no atomics (naf_hip.h P5): two calls return the same bits,
-    whatever `views_per_call` and `span_table` (whether the rays' spans are tabulated by a pre-pass or recomputed) are."""
+    whatever `views_per_call` and `span_table` (whether the rays' spans are tabulated by a pre-pass or recomputed) are.  `scan` is a `Scan` of the same `geo` and `angles` to reuse across calls."""
     check_method(method, "backproject_scan")
-    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
-        raise RuntimeError("backproject_scan: projections must be a CUDA/HIP tensor (no CPU path)")
-    dims = tuple(int(v) for v in geo.nVoxel)
-    out = _check_out(out, dims, projections, "backproject_scan")
-    check_geometry(out, geo)
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)
     N, H, W = len(angles), int(geo.nDetector[1]), int(geo.nDetector[0])
-    if projections.dtype != torch.float32 or tuple(projections.shape) != (N, H, W):
-        raise ValueError(f"backproject_scan: projections must be float32 {(N, H, W)}, got {projections.dtype} "
-                         f"{tuple(projections.shape)}")
-    if not projections.is_contiguous():
-        raise ValueError("backproject_scan: projections must be contiguous")
+    _abi.check_stack(projections, (N, H, W), None, "backproject_scan", "projections")
+    out = check_out(out, tuple(int(v) for v in geo.nVoxel), projections, "backproject_scan")
+    check_geometry(out, geo)
     if N == 0:
         return out
-    raygen = RayGenerator(geo, angles, projections.device)
+    scan = scan_for(geo, angles, projections.device, scan, "projector")
     per_call = views_per_call or max(1, MAX_PIXELS_PER_CALL // (H * W))
-    cdims = (ctypes.c_uint32 * 3)(*dims)
-    dv = _dvoxel(geo.dVoxel)
-    step = sample_step(geo.dVoxel, geo.accuracy)
-    lib = _abi.lib()
-    detector = (W, H, float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]),
-                float(geo.DSD), float(raygen.near), float(raygen.far), int(geo.mode == "parallel"), step)
     work = gather_workspace(min(per_call, N), H, W, projections.device, span_table) if method == "gather" else None
     for first in range(0, N, per_call):
         count = min(per_call, N - first)
         if method == "gather":
-            _abi.check(lib.naf_backproject_scan_gather(
-                _abi.ptr(projections[first:first + count]), None, count, count, ctypes.byref(cdims), ctypes.byref(dv),
-                _abi.ptr(raygen.poses[first:first + count]), *detector, _abi.ptr(out), None, _abi.ptr(work),
-                0 if work is None else work.numel(), _abi.stream_ptr()), "backproject_scan_gather")
-            continue
-        _abi.check(lib.naf_backproject_scan(
-            _abi.ptr(projections[first:first + count]), ctypes.byref(cdims), ctypes.byref(dv),
-            _abi.ptr(raygen.poses[first:first + count]), count, *detector, _abi.ptr(out), _abi.stream_ptr()), "backproject_scan")
+            scan.gather(projections[first:first + count], None, count, out, None, work, first, count)
+        else:
+            scan.backproject(projections, out, first, count)
     return out

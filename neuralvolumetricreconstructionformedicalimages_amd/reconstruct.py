@@ -113,14 +113,23 @@ def _namespace(a):
     return np, np.clip
 
 
+def _check_n_iter(who, n_iter):
+    n_iter = int(n_iter)
+    if n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be >= 0, got {n_iter}")
+    return n_iter
+
+
+def _inverse_where_positive(a, xp):
+    return xp.where(a > 0, 1.0 / xp.where(a > 0, a, xp.ones_like(a)), xp.zeros_like(a))
+
+
 def _weights_and_start(A, AT, b, x0, xp):
     """R = 1 / (A 1), C = 1 / (A^T 1) (0 where the sum is not > 0) and the start volume: zeros, or a copy of `x0`."""
     col = AT(xp.ones_like(b))                                   # A^T 1, which also gives the volume's shape
     row = A(xp.ones_like(col))                                  # A 1
-    R = xp.where(row > 0, 1.0 / xp.where(row > 0, row, xp.ones_like(row)), xp.zeros_like(row))
-    C = xp.where(col > 0, 1.0 / xp.where(col > 0, col, xp.ones_like(col)), xp.zeros_like(col))
     x = xp.zeros_like(col) if x0 is None else x0 + xp.zeros_like(col)      # a copy: the caller's x0 stays as it is
-    return R, C, x
+    return _inverse_where_positive(row, xp), _inverse_where_positive(col, xp), x
 
 
 def _norm(d, xp):
@@ -134,9 +143,7 @@ def sirt_operators(A, AT, b, n_iter, relax=1.0, nonneg=True, x0=None, callback=N
     relax = float(relax)
     if not (0.0 < relax <= 1.0):
         raise ValueError(f"sirt: relax must be in (0, 1], got {relax}")
-    n_iter = int(n_iter)
-    if n_iter < 0:
-        raise ValueError(f"sirt: n_iter must be >= 0, got {n_iter}")
+    n_iter = _check_n_iter("sirt", n_iter)
     xp, clamp = _namespace(b)
     R, C, x = _weights_and_start(A, AT, b, x0, xp)
     norms = []
@@ -157,20 +164,48 @@ def _method(deterministic):
     return "gather" if deterministic else "scatter"
 
 
+def _scan_operators(geo, angles, views_per_call, deterministic, device):
+    """(A, AT) of a scan on the kernels: `projector.project_scan` and `projector.backproject_scan` over one `Scan`."""
+    from . import projector
+    common = {"views_per_call": views_per_call, "scan": projector.Scan(geo, angles, device)}
+
+    def A(x):
+        return projector.project_scan(x, geo, angles, **common)
+
+    def AT(y):
+        return projector.backproject_scan(y, geo, angles, method=_method(deterministic), **common)
+
+    return A, AT
+
+
+def _device_solve_setup(who, projections, geo, angles, x0, deterministic, workspace_views=None):
+    """What the solvers that run on the subset kernels start from -> (scan, x, transpose): the `Scan`, the start volume (zeros, or
+    a copy of `x0`) and the keyword arguments of `sart.backproject_scan`, with a span table for calls of up to `workspace_views`
+    views (default: all) if `deterministic`."""
+    import torch
+
+    from . import _abi, projector
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError(f"{who}: projections must be a CUDA/HIP tensor (no CPU path)")
+    scan = projector.Scan(geo, angles, projections.device)
+    if x0 is None:
+        x = torch.zeros(scan.dims, device=projections.device, dtype=torch.float32)
+    else:
+        _abi.check_volume(x0, who, "x0")
+        projector.check_geometry(x0, geo)
+        x = x0.clone()
+    transpose = {"method": _method(deterministic), "scan": scan}
+    if deterministic:
+        transpose["workspace"] = projector.gather_workspace(workspace_views or scan.N, scan.H, scan.W, projections.device)
+    return scan, x, transpose
+
+
 def sirt(projections, geo, angles, n_iter=50, relax=1.0, nonneg=True, x0=None, callback=None, views_per_call=None,
          deterministic=False):
     """SIRT reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, residual norms).  See the module docstring for the iteration.
     `deterministic=True` takes the atomic-free transpose: two runs return the same bits."""
-    from . import projector
-    method = _method(deterministic)
-
-    def A(x):
-        return projector.project_scan(x, geo, angles, views_per_call=views_per_call)
-
-    def AT(y):
-        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call, method=method)
-
+    A, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device)
     return sirt_operators(A, AT, projections, n_iter, relax=relax, nonneg=nonneg, x0=x0, callback=callback)
 
 
@@ -211,17 +246,11 @@ def subset_order(angles, n_subsets, order="angular-distance", seed=0):
 
 
 def _check_os_sart(relax, relax_red, n_iter):
-    relax, relax_red, n_iter = float(relax), float(relax_red), int(n_iter)
+    relax, relax_red = float(relax), float(relax_red)
     for name, value in (("relax", relax), ("relax_red", relax_red)):
         if not (0.0 < value <= 1.0):
             raise ValueError(f"os_sart: {name} must be in (0, 1], got {value}")
-    if n_iter < 0:
-        raise ValueError(f"os_sart: n_iter must be >= 0, got {n_iter}")
-    return relax, relax_red, n_iter
-
-
-def _inverse_where_positive(a, xp):
-    return xp.where(a > 0, 1.0 / xp.where(a > 0, a, xp.ones_like(a)), xp.zeros_like(a))
+    return relax, relax_red, _check_n_iter("os_sart", n_iter)
 
 
 def os_sart_operators(A, AT, b, subsets, n_iter, relax=1.0, relax_red=1.0, nonneg=True, x0=None, callback=None):
@@ -268,24 +297,13 @@ def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-
     import numpy as np
     import torch
 
-    from . import _abi, projector, sart
+    from . import sart
     relax, relax_red, n_iter = _check_os_sart(relax, relax_red, n_iter)
-    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
-        raise RuntimeError("os_sart: projections must be a CUDA/HIP tensor (no CPU path)")
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)
     subsets = subset_order(angles, len(angles) if n_subsets is None else n_subsets, order, seed)
-    scan = sart.Scan(geo, angles, projections.device)
-    if x0 is None:
-        x = torch.zeros(scan.dims, device=projections.device, dtype=torch.float32)
-    else:
-        _abi.check_volume(x0, "os_sart", "x0")
-        projector.check_geometry(x0, geo)
-        x = x0.clone()
+    most = max(len(s) for s in subsets)
+    scan, x, transpose = _device_solve_setup("os_sart", projections, geo, angles, x0, deterministic, most)
     lists = [sart.ViewList(s, scan.N, projections.device) for s in subsets]
-    most = max(len(v) for v in lists)
-    transpose = {"method": _method(deterministic), "scan": scan}
-    if deterministic:
-        transpose["workspace"] = projector.gather_workspace(most, scan.H, scan.W, projections.device)
     y = torch.empty(most, scan.H, scan.W, device=x.device, dtype=torch.float32)
     r = torch.empty_like(y)
     num = torch.zeros_like(x)
@@ -328,11 +346,10 @@ def asd_pocs_operators(A, AT, b, n_iter, tv_descent, relax=1.0, relax_red=0.99, 
             raise ValueError(f"asd_pocs: {name} must be in (0, 1], got {value}")
     if not (alpha > 0.0) or not math.isfinite(alpha):
         raise ValueError(f"asd_pocs: alpha must be > 0 and finite, got {alpha}")
-    tv_steps, n_iter = int(tv_steps), int(n_iter)
+    tv_steps = int(tv_steps)
     if tv_steps < 0:
         raise ValueError(f"asd_pocs: tv_steps must be >= 0, got {tv_steps}")
-    if n_iter < 0:
-        raise ValueError(f"asd_pocs: n_iter must be >= 0, got {n_iter}")
+    n_iter = _check_n_iter("asd_pocs", n_iter)
     xp, clamp = _namespace(b)
     R, C, x = _weights_and_start(A, AT, b, x0, xp)
     beta, dtvg, history = relax, 0.0, []
@@ -364,15 +381,8 @@ def asd_pocs(projections, geo, angles, n_iter=50, relax=1.0, relax_red=0.99, alp
     (float32 volume of geo.nVoxel on the projections' device, history).  The data step is `sirt`'s update, the TV step
     `tv.tv_descent` with `tv_eps`; see the module docstring and `asd_pocs_operators`.  `deterministic=True` takes the atomic-free
     transpose: two runs return the same bits and the same history."""
-    from . import projector, tv
-    method = _method(deterministic)
-
-    def A(x):
-        return projector.project_scan(x, geo, angles, views_per_call=views_per_call)
-
-    def AT(y):
-        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call, method=method)
-
+    from . import tv
+    A, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device)
     scratch = []
 
     def descend(x, step, n_steps):
@@ -387,9 +397,7 @@ def asd_pocs(projections, geo, angles, n_iter=50, relax=1.0, relax_red=0.99, alp
 
 
 def _check_fista_tv(n_iter, lam):
-    n_iter, lam = int(n_iter), float(lam)
-    if n_iter < 0:
-        raise ValueError(f"fista_tv: n_iter must be >= 0, got {n_iter}")
+    n_iter, lam = _check_n_iter("fista_tv", n_iter), float(lam)
     if not math.isfinite(lam) or lam < 0.0:
         raise ValueError(f"fista_tv: lam must be >= 0 and finite, got {lam}")
     return n_iter, lam
@@ -438,23 +446,12 @@ def fista_tv(projections, geo, angles, n_iter=30, lam=DEFAULT_FISTA_TV_LAMBDA, t
     `deterministic=True` takes the atomic-free transpose: two runs return the same bits and the same norms."""
     import torch
 
-    from . import _abi, projector, sart, tv
+    from . import sart, tv
     n_iter, lam = _check_fista_tv(n_iter, lam)
     tv_iters = int(tv_iters)
     if tv_iters < 0:
         raise ValueError(f"fista_tv: tv_iters must be >= 0, got {tv_iters}")
-    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
-        raise RuntimeError("fista_tv: projections must be a CUDA/HIP tensor (no CPU path)")
-    scan = sart.Scan(geo, angles, projections.device)
-    if x0 is None:
-        x = torch.zeros(scan.dims, device=projections.device, dtype=torch.float32)
-    else:
-        _abi.check_volume(x0, "fista_tv", "x0")
-        projector.check_geometry(x0, geo)
-        x = x0.clone()
-    transpose = {"method": _method(deterministic), "scan": scan}
-    if deterministic:
-        transpose["workspace"] = projector.gather_workspace(scan.N, scan.H, scan.W, projections.device)
+    scan, x, transpose = _device_solve_setup("fista_tv", projections, geo, angles, x0, deterministic)
     yw = torch.empty(scan.N, scan.H, scan.W, device=x.device, dtype=torch.float32)
     res = torch.empty_like(yw)
     num = torch.zeros_like(x)
@@ -481,19 +478,12 @@ def fista_tv(projections, geo, angles, n_iter=30, lam=DEFAULT_FISTA_TV_LAMBDA, t
     return x, [math.sqrt(float(v)) for v in norms]
 
 
-def _check_cgls(n_iter):
-    n_iter = int(n_iter)
-    if n_iter < 0:
-        raise ValueError(f"cgls: n_iter must be >= 0, got {n_iter}")
-    return n_iter
-
-
 def cgls_operators(A, AT, b, n_iter, weights=None, x0=None, nonneg=True, callback=None):
     """CGLS on 1/2 ||b - A x||_W^2 over `A`, `AT` (as in `sirt_operators`); `weights` is an array of `b`'s kind with one weight
     >= 0 per ray, None for all ones.  See the module docstring for the iteration.  `callback(k, x, residual_norm)` runs after every
     iteration that took a step.  Returns (x, norms) with norms[k] = ||r_k||_W, r the recurred residual; the list ends with the norm
     of the iteration that stopped, if one did (gamma or delta not > 0)."""
-    n_iter = _check_cgls(n_iter)
+    n_iter = _check_n_iter("cgls", n_iter)
     xp, clamp = _namespace(b)
     w = weights
 
@@ -548,27 +538,19 @@ def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True
     import torch
 
     from . import _abi, cgls_kernels as K, projector, sart
-    n_iter = _check_cgls(n_iter)
-    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
-        raise RuntimeError("cgls: projections must be a CUDA/HIP tensor (no CPU path)")
-    scan = sart.Scan(geo, angles, projections.device)
-    sart._check_stack(projections, (scan.N, scan.H, scan.W), None, "cgls", "projections")
+    n_iter = _check_n_iter("cgls", n_iter)
+    scan, x, transpose = _device_solve_setup("cgls", projections, geo, angles, x0, deterministic)
+    _abi.check_stack(projections, (scan.N, scan.H, scan.W), None, "cgls", "projections")
     w = weights
     if w is not None:
-        sart._check_stack(w, (scan.N, scan.H, scan.W), projections, "cgls", "weights")
+        _abi.check_stack(w, (scan.N, scan.H, scan.W), projections, "cgls", "weights")
         if bool(((w < 0) | ~torch.isfinite(w)).any()):
             raise ValueError("cgls: weights must be >= 0 and finite")
-    if x0 is None:
-        x = torch.zeros(scan.dims, device=projections.device, dtype=torch.float32)
-        r = projections.clone()
-    else:
-        _abi.check_volume(x0, "cgls", "x0")
-        projector.check_geometry(x0, geo)
-        x = x0.clone()
-        r = projections - projector.project_scan(x, geo, angles, views_per_call=views_per_call)
-    transpose = {"method": _method(deterministic), "scan": scan}
-    if deterministic:
-        transpose["workspace"] = projector.gather_workspace(scan.N, scan.H, scan.W, projections.device)
+
+    def A(v):
+        return projector.project_scan(v, geo, angles, views_per_call=views_per_call, scan=scan)
+
+    r = projections.clone() if x0 is None else projections - A(x)
     ws = K.Workspace(max(r.numel(), x.numel()), n_iter, projections.device)
     y = r.clone() if w is None else w * r
     s = sart.backproject_scan(y, geo, angles, None, num=torch.zeros_like(x), **transpose)
@@ -576,7 +558,7 @@ def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True
     K.wdot(s, None, K.SLOT_GAMMA[0], ws)
     stopped = None
     for k in range(n_iter):
-        q = projector.project_scan(p, geo, angles, views_per_call=views_per_call)
+        q = A(p)
         K.wdot(q, w, K.SLOT_DELTA, ws)
         K.residual_step(r, q, w, y, k, ws)
         sart.backproject_scan(y, geo, angles, None, num=s.zero_(), **transpose)
@@ -605,8 +587,7 @@ def ray_length_weights(geo, angles, device, views_per_call=None):
 
     from . import projector
     ones = torch.ones(tuple(int(v) for v in geo.nVoxel), device=device, dtype=torch.float32)
-    row = projector.project_scan(ones, geo, angles, views_per_call=views_per_call)
-    return torch.where(row > 0, 1.0 / torch.where(row > 0, row, torch.ones_like(row)), torch.zeros_like(row))
+    return _inverse_where_positive(projector.project_scan(ones, geo, angles, views_per_call=views_per_call), torch)
 
 
 def pwls_weights(projections):
@@ -657,8 +638,7 @@ def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call
     the same bits."""
     import torch
 
-    from . import filter as F, projector
-    method = _method(deterministic)
+    from . import filter as F
 
     def on_device(a):
         return None if a is None else torch.tensor(a, device=projections.device)
@@ -666,7 +646,5 @@ def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call
     def rows(b, taps, pre, post, view_scale):
         return F.filter_rows(b, on_device(taps), on_device(pre), on_device(post), on_device(view_scale))
 
-    def AT(y):
-        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call, method=method)
-
+    _, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device)
     return fdk_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=nonneg)

@@ -10,58 +10,10 @@ on top.  There is no CPU fallback, like the rest of the hot path.
 """
 from __future__ import annotations
 
-import ctypes
-
-import numpy as np
 import torch
 
 from . import _abi, projector
-from .geometry import RayGenerator
-
-
-class Scan:
-    """What every call on one scan shares, made once: the poses of all views on the device and the geometry arguments."""
-
-    def __init__(self, geo, angles, device):
-        self.geo = geo
-        self.angles = np.asarray(angles, dtype=np.float64).reshape(-1)
-        self.raygen = RayGenerator(geo, self.angles, device)
-        self.device = self.raygen.poses.device              # with its index, as tensors report it
-        self.N, self.H, self.W = len(self.angles), self.raygen.H, self.raygen.W
-        self.dims = tuple(int(v) for v in geo.nVoxel)
-        self._cdims = (ctypes.c_uint32 * 3)(*self.dims)
-        self._dvoxel = projector._dvoxel(geo.dVoxel)
-        self._step = projector.sample_step(geo.dVoxel, geo.accuracy)
-
-    def detector_args(self):
-        g = self.geo
-        return (self.W, self.H, float(g.dDetector[0]), float(g.dDetector[1]), float(g.offDetector[0]), float(g.offDetector[1]),
-                float(g.DSD), float(self.raygen.near), float(self.raygen.far), int(g.mode == "parallel"), self._step)
-
-
-class ViewList:
-    """A list of views of an N-view scan, checked on the host (every index in [0, N)) and held on the device as well."""
-
-    def __init__(self, views, n_views, device):
-        idx = np.asarray(views).reshape(-1)
-        if idx.size and not np.issubdtype(idx.dtype, np.integer):
-            raise ValueError(f"sart: view indices must be integers, got {idx.dtype}")
-        idx = idx.astype(np.int64)
-        if idx.size and (idx.min() < 0 or idx.max() >= n_views):
-            raise ValueError(f"sart: view index out of range for a scan of {n_views} views: {idx.tolist()}")
-        self.host, self.n_views = idx, int(n_views)
-        self.device = torch.tensor(idx.astype(np.int32), device=device) if idx.size else None      # the same bits as u32
-
-    def __len__(self):
-        return int(self.host.size)
-
-
-def _scan(geo, angles, device, scan):
-    if scan is None:
-        return Scan(geo, angles, device)
-    if scan.geo is not geo or scan.device != device:
-        raise ValueError("sart: `scan` was made for another geometry or device")
-    return scan
+from .projector import Scan, ViewList                       # where they live; `sart.Scan` and `sart.ViewList` are the same objects
 
 
 def _views(views, scan):
@@ -75,21 +27,6 @@ def _views(views, scan):
     return views, len(views)
 
 
-def _check_stack(t, shape, like, who, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{who}: {name} must be a CUDA/HIP tensor (no CPU path)")
-    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{who}: {name} must be float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be contiguous")
-    if like is not None and t.device != like.device:
-        raise ValueError(f"{who}: {name} must be on the device of the other arguments")
-
-
-def _index_ptr(views):
-    return None if views is None else _abi.ptr(views.device)
-
-
 def residual_scan(volume, projections, geo, angles, views=None, y=None, r=None, want_r=True, scan=None):
     """Weighted residual of the views `views` (indices into the scan; None: all, in order) of the scan `projections` [N, H, W] for
     the volume `volume` -> (y, r), float32 [len(views), H, W]: r = b - A x and y = r / len (0 on a ray that misses the volume).
@@ -98,25 +35,22 @@ def residual_scan(volume, projections, geo, angles, views=None, y=None, r=None, 
     who = "sart.residual_scan"
     _abi.check_volume(volume, who)
     projector.check_geometry(volume, geo)
-    scan = _scan(geo, angles, volume.device, scan)
-    _check_stack(projections, (scan.N, scan.H, scan.W), volume, who, "projections")
+    scan = projector.scan_for(geo, angles, volume.device, scan, "sart")
+    _abi.check_stack(projections, (scan.N, scan.H, scan.W), volume, who, "projections")
     views, m = _views(views, scan)
     shape = (m, scan.H, scan.W)
     if y is None:
         y = torch.empty(shape, device=volume.device, dtype=torch.float32)
     else:
-        _check_stack(y, shape, volume, who, "y")
+        _abi.check_stack(y, shape, volume, who, "y")
     if not want_r:
         r = None
     elif r is None:
         r = torch.empty(shape, device=volume.device, dtype=torch.float32)
     else:
-        _check_stack(r, shape, volume, who, "r")
+        _abi.check_stack(r, shape, volume, who, "r")
     if m:
-        _abi.check(_abi.lib().naf_sart_residual_scan(
-            _abi.ptr(volume), ctypes.byref(scan._cdims), ctypes.byref(scan._dvoxel), _abi.ptr(scan.raygen.poses), m,
-            *scan.detector_args(), _index_ptr(views), scan.N, _abi.ptr(projections), _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr()),
-            "sart_residual_scan")
+        scan.residual(volume, views, m, projections, y, r)
     return y, r
 
 
@@ -129,10 +63,10 @@ def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None, 
     projector.check_method(method, who)
     if not isinstance(y, torch.Tensor) or not y.is_cuda:
         raise RuntimeError(f"{who}: y must be a CUDA/HIP tensor (no CPU path)")
-    scan = _scan(geo, angles, y.device, scan)
+    scan = projector.scan_for(geo, angles, y.device, scan, "sart")
     views, m = _views(views, scan)
-    _check_stack(y, (m, scan.H, scan.W), None, who, "y")
-    num = projector._check_out(num, scan.dims, y, who)
+    _abi.check_stack(y, (m, scan.H, scan.W), None, who, "y")
+    num = projector.check_out(num, scan.dims, y, who)
     projector.check_geometry(num, geo)
     if den is not None:
         _abi.check_volume(den, who, "den")
@@ -149,15 +83,9 @@ def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None, 
               or not workspace.is_contiguous() or workspace.device != y.device):
             raise ValueError(f"{who}: workspace must be a contiguous uint8 [bytes] tensor on the input's device "
                              "(projector.gather_workspace), None or False")
-        _abi.check(_abi.lib().naf_backproject_scan_gather(
-            _abi.ptr(y), _index_ptr(views), m, scan.N, ctypes.byref(scan._cdims), ctypes.byref(scan._dvoxel),
-            _abi.ptr(scan.raygen.poses), *scan.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.ptr(workspace),
-            0 if workspace is None else workspace.numel(), _abi.stream_ptr()), "backproject_scan_gather")
+        scan.gather(y, views, m, num, den, workspace)
     elif m:
-        _abi.check(_abi.lib().naf_sart_backproject_scan(
-            _abi.ptr(y), _index_ptr(views), m, scan.N, ctypes.byref(scan._cdims), ctypes.byref(scan._dvoxel),
-            _abi.ptr(scan.raygen.poses), *scan.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.stream_ptr()),
-            "sart_backproject_scan")
+        scan.backproject_views(y, views, m, num, den)
     return num
 
 
