@@ -586,7 +586,28 @@ int naf_project_scan_siddon(const float *volume, const uint32_t *dims, const flo
                             uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
                             int parallel, float *out, void *stream);
 
-/* M1  3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
+/* P7  the transpose of P6.  Let A be P6's linear map volume -> projections.  Its entry for ray r and voxel v
+ * is the fp32 number P6's walk itself forms for that step, a_rv = fl(fl(s_next - s_prev) * |d|); a ray visits a voxel at most once
+ * with positive length.  These entry points add A^T y into `volume`, A^T the transpose of exactly that matrix.
+ *   values / projections  f32, one value y_r per ray: [n_rays], or [n_projections, det_h, det_w] with the rays of P6's scan
+ *   volume  f32 [n1, n2, n3] as in P6, ACCUMULATED INTO (+=): the caller zeroes it, as in P2
+ * Ray r takes P6's own span, end-point indices, trip count, crossings and tie order (siddon_span, siddon_begin and siddon_step of
+ * csrc/siddon_device.h, the functions the forward kernel runs), and each step adds fl(y_r * a_rv) to volume[v] with one fp32
+ * hardware atomic.  What sends nothing:
+ *   a step whose length is exactly 0, whatever y_r is (ties, the padding of the last group, the exit voxel's fixed point);
+ *   a ray with y_r == 0;  an empty span;  a ray for which P6 returns NaN (non-finite p0 or s_end), as in P2.
+ * A NaN or Inf y_r on a valid ray reaches exactly the voxels of positive chord length.
+ * The result equals A^T y up to rounding and SUMMATION ORDER; like P2 it is not bit-reproducible.  All offsets are 64-bit.
+ * P6's INVARIANT carries over: no float comparison moves an index or adds a step, so no atomic can land outside the volume.
+ * Both refuse what naf_project_rays_siddon / naf_project_scan_siddon refuse, before any launch; empty batches (n_rays == 0,
+ * n_projections == 0) return NAF_OK without examining the pointers.  The argument lists are P2's without the sample step. */
+int naf_backproject_rays_siddon(const float *values, const float *rays, uint64_t n_rays, uint32_t n1, uint32_t n2, uint32_t n3,
+                                const float *dvoxel, float *volume, void *stream);
+int naf_backproject_scan_siddon(const float *projections, const uint32_t *dims, const float *dvoxel, const float *poses,
+                                uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
+                                float DSD, float near, float far, int parallel, float *volume, void *stream);
+
+/* M1 3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
  * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
  * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.
  *   x, y  f32 [n1, n2, n3] C-contiguous, converted to fp64 on load; all arithmetic in fp64

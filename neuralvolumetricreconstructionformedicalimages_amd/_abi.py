@@ -147,6 +147,9 @@ SIGNATURES = {
     "naf_backproject_rays": (_i32, [_vp, _vp, _u64, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _f32, _vp, _vp]),
     "naf_backproject_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
                                     _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),
+    "naf_backproject_rays_siddon": (_i32, [_vp, _vp, _u64, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _vp]),
+    "naf_backproject_scan_siddon": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32,
+                                           _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
     "naf_filter_rows": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "naf_sart_residual_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
                                       _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _u32, _vp, _vp, _vp, _vp]),

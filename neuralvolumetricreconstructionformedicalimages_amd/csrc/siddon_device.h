@@ -209,4 +209,31 @@ NAF_SIDDON_HD float siddon_line_integral(const SiddonGrid &g, const float o[3], 
     return acc;
 }
 
+// The transpose of that map for one ray (include/naf_hip.h P7): the same span, end-point indices, trip count,
+// crossings and tie order, and for every step of positive length one call add(offset, y * ((s_next - s_prev) * |d|)), the factor
+// in brackets being the very float siddon_line_integral multiplies the voxel by.  Steps of length 0 (ties, the padding of the last
+// group, the exit voxel's fixed point) send nothing whatever y is, and neither does y == 0, an empty span or a non-finite one.
+// A group is stepped first and sent after: nothing here waits for what `add` does.
+template <class Add>
+NAF_SIDDON_HD void siddon_scatter(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, float y, Add add) {
+    if (y == 0.0f) return;
+    SiddonSpan r;
+    if (siddon_span(g, o, d, near, far, r) != kSiddonOk) return;
+    SiddonWalk w;
+    const uint32_t steps = siddon_begin(g, r, w);
+    for (uint32_t k = 0; k < steps; k += kSiddonGroup) {
+        float len[kSiddonGroup];
+        uint64_t offset[kSiddonGroup];
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+            float ds;
+            siddon_step(g, r, w, offset[j], ds);
+            len[j] = ds * r.dn;
+        }
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j)
+            if (len[j] > 0.0f) add(offset[j], y * len[j]);
+    }
+}
+
 }  // namespace naf

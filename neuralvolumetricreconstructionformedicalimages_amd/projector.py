@@ -1,5 +1,5 @@
-"""Forward projector: line integrals of a voxel volume through libnaf_hip.so (`naf_project_rays`, `naf_project_scan` and their
-`_siddon` counterparts).
+"""Forward projector and its transpose: line integrals of a voxel volume through libnaf_hip.so (`naf_project_rays`,
+`naf_project_scan`, `naf_backproject_rays`, `naf_backproject_scan` and their `_siddon` counterparts).
 
 This is what TIGRE's `tigre.Ax` does for the reference's dataGenerator/generateData.py:178,189: it turns a CT volume into the
 projections of a scan.  The projection is defined in include/naf_hip.h (P1) and DESIGN.md section 10: trilinear interpolation,
@@ -9,7 +9,10 @@ that pixel, so projections and training rays agree by construction (no TIGRE axi
 
 `kind="siddon"` selects the other discretisation (P6): the volume constant inside each voxel and exact chord
 lengths, the ray-voxel intersection projector TIGRE's `Ax` takes by default.  It has no sample step, so `accuracy` plays no part.
-The default everywhere is `kind="interpolated"`; the transposes and the solvers stay on the interpolated pair.
+`backproject_rays` and `backproject_scan` take the same `kind`: with "siddon" they add the exact transpose of that projector (P7,
+DESIGN.md section 21), one fp32 atomic per voxel a ray crosses, so A and A^T of either kind are a matched pair.  The Siddon transpose
+has the scatter form only.  The default everywhere is `kind="interpolated"`; `reconstruct.sirt`, `asd_pocs` and `cgls` take `kind`
+as well, the solvers on the fused subset kernels and FDK stay on the interpolated pair.
 
 There is no CPU fallback, like the rest of the hot path.
 """
@@ -89,8 +92,13 @@ class Scan:
         else:
             _abi.check(_abi.lib().naf_project_scan(*args, dst, _abi.stream_ptr()), "project_scan")
 
-    def backproject(self, projections, out, first, count):
-        """out += A^T projections over the views [first, first + count), by the scatter."""
+    def backproject(self, projections, out, first, count, kind="interpolated"):
+        """out += A^T projections over the views [first, first + count), by the scatter of that `kind`."""
+        if kind == "siddon":                                    # no sample step
+            _abi.check(_abi.lib().naf_backproject_scan_siddon(
+                _abi.ptr(projections[first:first + count]), *self._grid_and_poses(first), count, *self.detector_args()[:-1],
+                _abi.ptr(out), _abi.stream_ptr()), "backproject_scan_siddon")
+            return
         _abi.check(_abi.lib().naf_backproject_scan(
             _abi.ptr(projections[first:first + count]), *self._grid_and_poses(first), count, *self.detector_args(), _abi.ptr(out),
             _abi.stream_ptr()), "backproject_scan")
@@ -201,11 +209,13 @@ def check_out(out, shape, like, who):
     return out
 
 
-def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None):
+def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None, kind="interpolated"):
     """Transpose of `project_rays`: adds `values` [n] along `rays` [n, 8] into a volume of `dims` = (n1, n2, n3) voxels of size
     `dvoxel` -> float32 [n1, n2, n3].  Sums are fp32 atomics: equal to A^T values up to summation order (naf_hip.h, P2).
     Arbitrary rays lie on no pixel lattice, so this entry point keeps the scatter only: the atomic-free gather form
-    (`backproject_scan(..., method="gather")`) exists for scans."""
+    (`backproject_scan(..., method="gather")`) exists for scans.  `kind="siddon"` is the transpose of `project_rays(kind="siddon")`
+    (P7): values times exact chord lengths, one atomic per voxel crossed; `accuracy` is ignored then."""
+    check_kind(kind, "backproject_rays")
     if not isinstance(values, torch.Tensor) or not values.is_cuda:
         raise RuntimeError("backproject_rays: values must be a CUDA/HIP tensor (no CPU path)")
     n = _abi.check_rays(rays, values, "backproject_rays", "values'")
@@ -217,6 +227,11 @@ def backproject_rays(values, dvoxel, rays, dims, accuracy=0.5, out=None):
     if len(dims) != 3 or min(dims) < 1:
         raise ValueError(f"backproject_rays: dims must be three positive extents, got {dims}")
     out = check_out(out, dims, values, "backproject_rays")
+    if kind == "siddon":
+        _abi.check(_abi.lib().naf_backproject_rays_siddon(_abi.ptr(values), _abi.ptr(rays), n, dims[0], dims[1], dims[2],
+                                                          ctypes.byref(_dvoxel(dvoxel)), _abi.ptr(out), _abi.stream_ptr()),
+                   "backproject_rays_siddon")
+        return out
     _abi.check(_abi.lib().naf_backproject_rays(_abi.ptr(values), _abi.ptr(rays), n, dims[0], dims[1], dims[2],
                                                ctypes.byref(_dvoxel(dvoxel)), sample_step(dvoxel, accuracy), _abi.ptr(out),
                                                _abi.stream_ptr()), "backproject_rays")
@@ -239,13 +254,25 @@ def gather_workspace(n_views, H, W, device, span_table=True):
     return torch.empty(views * per_view, device=device, dtype=torch.uint8)
 
 
-def backproject_scan(projections, geo, angles, views_per_call=None, out=None, method="scatter", span_table=True, scan=None):
+def check_kind_and_method(kind, method, who):
+    """The Siddon transpose exists as a scatter only: there is no atomic-free (gather) form of it."""
+    check_kind(kind, who)
+    check_method(method, who)
+    if kind == "siddon" and method == "gather":
+        raise ValueError(f"{who}: kind='siddon' has no method='gather': the Siddon transpose sums with atomics only, and the "
+                         "atomic-free gather exists for the interpolated pair")
+
+
+def backproject_scan(projections, geo, angles, views_per_call=None, out=None, method="scatter", span_table=True, scan=None,
+                     kind="interpolated"):
     """Transpose of `project_scan`: adds `projections` [N, H, W] of the scan geometry `geo` at `angles` into a volume on the voxel
     grid of `geo` -> float32 nVoxel.  Views go to the kernel in groups of `views_per_call` like `project_scan`'s.
     `method="scatter"` (the default) is the ray scatter on fp32 atomics, equal to A^T y up to summation order; `method="gather"`
     is the same operator evaluated per voxel in a fixed order with no atomics (naf_hip.h P5): two calls return the same bits,
-    whatever `views_per_call` and `span_table` (whether the rays' spans are tabulated by a pre-pass or recomputed) are.  `scan` is a `Scan` of the same `geo` and `angles` to reuse across calls."""
-    check_method(method, "backproject_scan")
+    whatever `views_per_call` and `span_table` (whether the rays' spans are tabulated by a pre-pass or recomputed) are.  `scan` is a `Scan` of the same `geo` and `angles` to reuse across calls.
+    `kind="siddon"` is the transpose of `project_scan(kind="siddon")` (P7), a scatter on fp32 atomics; it has no gather form, so
+    with `method="gather"` it raises ValueError."""
+    check_kind_and_method(kind, method, "backproject_scan")
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)
     N, H, W = len(angles), int(geo.nDetector[1]), int(geo.nDetector[0])
     _abi.check_stack(projections, (N, H, W), None, "backproject_scan", "projections")
@@ -261,5 +288,5 @@ def backproject_scan(projections, geo, angles, views_per_call=None, out=None, me
         if method == "gather":
             scan.gather(projections[first:first + count], None, count, out, None, work, first, count)
         else:
-            scan.backproject(projections, out, first, count)
+            scan.backproject(projections, out, first, count, kind)
     return out

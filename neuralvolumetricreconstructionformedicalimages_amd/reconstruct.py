@@ -5,6 +5,12 @@ back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that 
 kernels and the TV proximal map (`tv.tv_prox`), and CGLS with per-ray weights over the same pair and the vector kernels of `cgls_kernels`.
 They are the baselines the reference took from TIGRE, which has no ROCm build.  DESIGN.md sections 13 to 19.
 
+`sirt`, `asd_pocs`, `cgls` and `ray_length_weights` take `kind`: "interpolated" (the default) is the pair above, "siddon" the
+ray-voxel intersection projector and its exact transpose (include/naf_hip.h P6 / P7, DESIGN.md sections 20 and 21), the matched
+pair for scans made with `project_scan(kind="siddon")`.  A and A^T are always bound to the same kind.  The Siddon transpose sums
+with fp32 atomics and has no atomic-free form, so `kind="siddon"` with `deterministic=True` raises ValueError.  `os_sart`,
+`fista_tv` (the fused subset kernels) and `fdk` (its weights are derived for the interpolated A^T) have no such parameter.
+
 SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the element-wise product):
 
     R = 1 / (A 1)    where A 1 > 0, else 0          (inverse row sums: one weight per ray)
@@ -164,10 +170,23 @@ def _method(deterministic):
     return "gather" if deterministic else "scatter"
 
 
-def _scan_operators(geo, angles, views_per_call, deterministic, device):
-    """(A, AT) of a scan on the kernels: `projector.project_scan` and `projector.backproject_scan` over one `Scan`."""
+def _check_kind(who, kind, deterministic):
+    """`kind` names the projector pair.  The Siddon transpose sums with fp32 atomics and has no atomic-free form, so it cannot be
+    combined with `deterministic=True`."""
     from . import projector
-    common = {"views_per_call": views_per_call, "scan": projector.Scan(geo, angles, device)}
+    projector.check_kind(kind, who)
+    if kind == "siddon" and deterministic:
+        raise ValueError(f"{who}: kind='siddon' cannot be deterministic: its transpose sums with fp32 atomics in hardware order, and "
+                         "the atomic-free gather transpose exists for the interpolated pair only")
+    return kind
+
+
+def _scan_operators(geo, angles, views_per_call, deterministic, device, kind="interpolated", who="reconstruct"):
+    """(A, AT) of a scan on the kernels: `projector.project_scan` and `projector.backproject_scan` over one `Scan`, both of the
+    same `kind`, so that AT is the transpose of A."""
+    from . import projector
+    _check_kind(who, kind, deterministic)
+    common = {"views_per_call": views_per_call, "scan": projector.Scan(geo, angles, device), "kind": kind}
 
     def A(x):
         return projector.project_scan(x, geo, angles, **common)
@@ -201,11 +220,12 @@ def _device_solve_setup(who, projections, geo, angles, x0, deterministic, worksp
 
 
 def sirt(projections, geo, angles, n_iter=50, relax=1.0, nonneg=True, x0=None, callback=None, views_per_call=None,
-         deterministic=False):
+         deterministic=False, kind="interpolated"):
     """SIRT reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, residual norms).  See the module docstring for the iteration.
-    `deterministic=True` takes the atomic-free transpose: two runs return the same bits."""
-    A, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device)
+    `deterministic=True` takes the atomic-free transpose: two runs return the same bits.  `kind="siddon"` runs A and A^T on the
+    ray-voxel intersection pair (naf_hip.h P6 / P7) instead of the interpolated one; it cannot be deterministic."""
+    A, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device, kind, "sirt")
     return sirt_operators(A, AT, projections, n_iter, relax=relax, nonneg=nonneg, x0=x0, callback=callback)
 
 
@@ -376,13 +396,14 @@ def asd_pocs_operators(A, AT, b, n_iter, tv_descent, relax=1.0, relax_red=0.99, 
 
 
 def asd_pocs(projections, geo, angles, n_iter=50, relax=1.0, relax_red=0.99, alpha=0.002, alpha_red=0.95, rmax=0.95, tv_steps=20,
-             tv_eps=1e-8, nonneg=True, x0=None, callback=None, views_per_call=None, deterministic=False):
+             tv_eps=1e-8, nonneg=True, x0=None, callback=None, views_per_call=None, deterministic=False, kind="interpolated"):
     """ASD-POCS reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, history).  The data step is `sirt`'s update, the TV step
     `tv.tv_descent` with `tv_eps`; see the module docstring and `asd_pocs_operators`.  `deterministic=True` takes the atomic-free
-    transpose: two runs return the same bits and the same history."""
+    transpose: two runs return the same bits and the same history.  `kind="siddon"` runs the data step on the ray-voxel
+    intersection pair (naf_hip.h P6 / P7); it cannot be deterministic."""
     from . import tv
-    A, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device)
+    A, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device, kind, "asd_pocs")
     scratch = []
 
     def descend(x, step, n_steps):
@@ -525,7 +546,7 @@ def cgls_operators(A, AT, b, n_iter, weights=None, x0=None, nonneg=True, callbac
 
 
 def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True, callback=None, views_per_call=None,
-         deterministic=False, info=None):
+         deterministic=False, info=None, kind="interpolated"):
     """CGLS reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, residual norms ||r_k||_W).  The iteration of `cgls_operators`:
     A is `projector.project_scan`, A^T `sart.backproject_scan` over all views into a zeroed volume, and the rest three HIP launches
@@ -534,11 +555,15 @@ def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True
     when a `callback(k, x, residual_norm)` is given (it sees the live, unclamped volume).  `weights` is a float32 [N, H, W] tensor
     on the projections' device, >= 0 and finite (`ray_length_weights`, `pwls_weights`, a mask, or their product).  The norms are cut
     at the iteration that stopped, if one did; `info`, a dict, receives `stopped_at` (that iteration, or None).
-    `deterministic=True` takes the atomic-free transpose: with the fixed-order fp64 sums two runs return the same bits and norms."""
+    `deterministic=True` takes the atomic-free transpose: with the fixed-order fp64 sums two runs return the same bits and norms.
+    `kind="siddon"` takes the ray-voxel intersection pair (naf_hip.h P6 / P7): A is `projector.project_scan(kind="siddon")` and A^T
+    `projector.backproject_scan(kind="siddon")` into a zeroed volume, the exact transpose CGLS rests on; the three vector launches
+    and the single read-back stay as they are.  It cannot be deterministic."""
     import torch
 
     from . import _abi, cgls_kernels as K, projector, sart
     n_iter = _check_n_iter("cgls", n_iter)
+    _check_kind("cgls", kind, deterministic)
     scan, x, transpose = _device_solve_setup("cgls", projections, geo, angles, x0, deterministic)
     _abi.check_stack(projections, (scan.N, scan.H, scan.W), None, "cgls", "projections")
     w = weights
@@ -548,12 +573,17 @@ def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True
             raise ValueError("cgls: weights must be >= 0 and finite")
 
     def A(v):
-        return projector.project_scan(v, geo, angles, views_per_call=views_per_call, scan=scan)
+        return projector.project_scan(v, geo, angles, views_per_call=views_per_call, scan=scan, kind=kind)
+
+    def AT(v, zeroed):
+        if kind == "siddon":
+            return projector.backproject_scan(v, geo, angles, views_per_call=views_per_call, out=zeroed, scan=scan, kind=kind)
+        return sart.backproject_scan(v, geo, angles, None, num=zeroed, **transpose)
 
     r = projections.clone() if x0 is None else projections - A(x)
     ws = K.Workspace(max(r.numel(), x.numel()), n_iter, projections.device)
     y = r.clone() if w is None else w * r
-    s = sart.backproject_scan(y, geo, angles, None, num=torch.zeros_like(x), **transpose)
+    s = AT(y, torch.zeros_like(x))
     p = s.clone()
     K.wdot(s, None, K.SLOT_GAMMA[0], ws)
     stopped = None
@@ -561,7 +591,7 @@ def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True
         q = A(p)
         K.wdot(q, w, K.SLOT_DELTA, ws)
         K.residual_step(r, q, w, y, k, ws)
-        sart.backproject_scan(y, geo, angles, None, num=s.zero_(), **transpose)
+        AT(y, s.zero_())
         K.wdot(s, None, K.SLOT_GAMMA[(k + 1) & 1], ws)
         K.direction_step(x, p, s, k, ws)
         if callback is not None:
@@ -581,13 +611,15 @@ def cgls(projections, geo, angles, n_iter=15, weights=None, x0=None, nonneg=True
     return x, norms
 
 
-def ray_length_weights(geo, angles, device, views_per_call=None):
-    """R = 1 / (A 1) where A 1 > 0, else 0: float32 [N, H, W] on `device`, the ray weights of SIRT and of FISTA-TV's data term."""
+def ray_length_weights(geo, angles, device, views_per_call=None, kind="interpolated"):
+    """R = 1 / (A 1) where A 1 > 0, else 0: float32 [N, H, W] on `device`, the ray weights of SIRT and of FISTA-TV's data term.
+    A is the projector of `kind`; with "siddon" A 1 is the ray's chord length through the volume."""
     import torch
 
     from . import projector
+    projector.check_kind(kind, "ray_length_weights")
     ones = torch.ones(tuple(int(v) for v in geo.nVoxel), device=device, dtype=torch.float32)
-    return _inverse_where_positive(projector.project_scan(ones, geo, angles, views_per_call=views_per_call), torch)
+    return _inverse_where_positive(projector.project_scan(ones, geo, angles, views_per_call=views_per_call, kind=kind), torch)
 
 
 def pwls_weights(projections):

@@ -5,6 +5,7 @@ the chest shape (50 x 512^2 pixels, 256^3 volume, accuracy 0.5) and a 1024^3 vol
     python tools/backproject_bench.py                         # both shapes, one JSON line each
     python tools/backproject_bench.py --shape chest --lib lib/ab/per_sample.so      # an A/B variant of libnaf_hip.so
     python tools/backproject_bench.py --gather --shape chest  # the gather form next to the scatter
+    python tools/backproject_bench.py --siddon                # the Siddon transpose next to both, same run
 
 With `--gather` (shapes chest, step: one 512^2 view into 256^3, the OS-SART subset step, and small: 50 x 256^2 into 128^3) the line
 also holds the gather transpose's time with and without the span table, its ratio to the scatter, whether two calls returned the
@@ -69,6 +70,66 @@ def gather_columns(geo, angles, y, scatter, scatter_ms, warmup, iters, windows, 
     return out
 
 
+ATOMIC_BYTES_PER_S = 1.3e12        # chip-wide rate of fp32 atomic adds, in added bytes (4 per add)
+
+
+def run_siddon(shape, warmup, iters, windows):
+    """The Siddon transpose, the interpolated scatter and the gather at one shape, timed in alternating windows of `iters` calls
+    each (device events after warm-up), with the two forward kernels for the cost of a pair A + A^T of each kind.  The atomic floor
+    is the steps of the walk (project_bench.siddon_steps: one fp32 atomic per step of positive length, so the zero-length steps of
+    ties make this a slight over-count of the sent terms) times 4 bytes over ATOMIC_BYTES_PER_S."""
+    from project_bench import SHAPES, siddon_steps
+    from neuralvolumetricreconstructionformedicalimages_amd import phantom, projector
+    from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry, RayGenerator
+    nv, det, views, pitch, vox = SHAPES[shape]
+    data = phantom.scan_geometry(256)
+    data.update(nVoxel=[nv] * 3, dVoxel=[vox] * 3, nDetector=[det, det], dDetector=[pitch, pitch])
+    geo = ConeGeometry(data)
+    table = phantom.ellipsoid_table(seed=0, extent=float(geo.sVoxel[0]) / 2)
+    x = phantom.volume(geo, table, device="cuda", slab=max(1, (1 << 22) // (nv * nv)))
+    angles = np.linspace(0, np.pi, views + 1)[:-1]
+    scan = projector.Scan(geo, angles, "cuda")
+    y = projector.project_scan(x, geo, angles, kind="siddon", scan=scan)
+    acc = torch.zeros_like(x)
+    calls = {"siddon": lambda: projector.backproject_scan(y, geo, angles, out=acc, kind="siddon", scan=scan),
+             "scatter": lambda: projector.backproject_scan(y, geo, angles, out=acc, scan=scan),
+             "gather": lambda: projector.backproject_scan(y, geo, angles, out=acc, method="gather", scan=scan),
+             "forward_siddon": lambda: projector.project_scan(x, geo, angles, kind="siddon", scan=scan),
+             "forward_interpolated": lambda: projector.project_scan(x, geo, angles, scan=scan)}
+    for fn in calls.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in calls}
+    for _ in range(windows):
+        for name, fn in calls.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            times[name].append(a.elapsed_time(b) / iters)
+    raygen = RayGenerator(geo, angles, "cuda")
+    steps = sum(siddon_steps(raygen.rays_for_projection(i), x.shape, geo.dVoxel) for i in range(views))
+    aty = projector.backproject_scan(y, geo, angles, kind="siddon", scan=scan)
+    lhs, rhs = float((y.double() * y.double()).sum()), float((x.double() * aty.double()).sum())
+    res = {"shape": shape, "volume": [nv] * 3, "detector": [det, det], "views": views, "windows": windows, "calls_per_window": iters}
+    for name in calls:
+        t = sorted(times[name])
+        res[name] = {"median_ms": round(t[len(t) // 2], 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4)}
+    floor_ms = steps * 4 / ATOMIC_BYTES_PER_S * 1e3
+    ms = res["siddon"]["median_ms"]
+    res["siddon"].update({"steps": steps, "atomic_GB_per_s": steps * 4 / ms * 1e-6, "atomic_floor_ms": round(floor_ms, 3),
+                          "time_over_floor": round(ms / floor_ms, 2)})
+    res["siddon_over_scatter_time"] = round(ms / res["scatter"]["median_ms"], 4)
+    res["siddon_over_gather_time"] = round(ms / res["gather"]["median_ms"], 4)
+    res["pair_ms"] = {"siddon": round(ms + res["forward_siddon"]["median_ms"], 3),
+                      "interpolated": round(res["scatter"]["median_ms"] + res["forward_interpolated"]["median_ms"], 3)}
+    res["adjoint_mismatch_siddon"] = abs(lhs - rhs) / lhs
+    return res
+
+
 def run(shape, warmup, iters, windows, gather=False, count_voxels=0):
     from project_bench import SHAPES, segments
     SHAPES = {**SHAPES, **GATHER_SHAPES}
@@ -104,6 +165,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=["chest", "big", "step", "small", "all"], default="all")
     ap.add_argument("--gather", action="store_true", help="also time the gather transpose (with and without its span table)")
+    ap.add_argument("--siddon", action="store_true",
+                    help="time the Siddon transpose next to the scatter and the gather in alternating windows (shapes chest, big)")
     ap.add_argument("--count-voxels", type=int, default=64, help="voxels of the per-voxel visit counts of --gather (0: none)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--iters", type=int, default=2)
@@ -114,7 +177,10 @@ def main():
         from neuralvolumetricreconstructionformedicalimages_amd import build
         build.LIB_PATH = os.path.abspath(args.lib)
     for shape in (["chest", "big"] if args.shape == "all" else [args.shape]):
-        res = run(shape, args.warmup, args.iters, args.windows, args.gather, args.count_voxels if args.gather else 0)
+        if args.siddon:
+            res = run_siddon(shape, args.warmup, args.iters, args.windows)
+        else:
+            res = run(shape, args.warmup, args.iters, args.windows, args.gather, args.count_voxels if args.gather else 0)
         if args.lib:
             res["lib"] = os.path.basename(args.lib)
         print(json.dumps(res), flush=True)

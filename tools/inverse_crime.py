@@ -4,7 +4,8 @@
 The analytic phantom at 64^3 and 50 views gives three training sets for one voxel volume: its projections by the interpolated
 projector (the operator the baselines reconstruct with), by the Siddon projector (another discretisation)
 and the phantom's analytic line integrals.  `reconstruct.sirt` (50 iterations) and `reconstruct.cgls` (15 iterations) run on
-each; printed are psnr_3d and ssim_3d against the voxel volume.  A measurement, not a test.
+each, once on the interpolated pair and once on the Siddon pair (kind="siddon": that projector and its exact transpose, DESIGN.md
+section 21); printed are psnr_3d and ssim_3d against the voxel volume.  A measurement, not a test.
 
     python tools/inverse_crime.py [--n 64] [--views 50]
 """
@@ -39,15 +40,17 @@ def main():
             "siddon": projector.project_scan(volume, geo, angles, kind="siddon"),
             "analytic": torch.stack([phantom.line_integrals(gen.rays_for_projection(i), table).reshape(H, W)
                                      for i in range(len(angles))]).contiguous()}
-    print(f"| data | solver | psnr_3d | ssim_3d |\n|---|---|---|---|")
-    for name, projections in sets.items():
-        for solver, run in (("sirt", lambda b: reconstruct.sirt(b, geo, angles, n_iter=args.sirt_iters)),
-                            ("cgls", lambda b: reconstruct.cgls(b, geo, angles, n_iter=args.cgls_iters))):
-            x = run(projections)
-            x = x[0] if isinstance(x, tuple) else x
-            row = {"data": name, "solver": solver, "psnr_3d": float(get_psnr_3d(x, volume)), "ssim_3d": float(metrics.ssim_3d(x, volume))}
-            print(f"| {name} | {solver} | {row['psnr_3d']:.2f} | {row['ssim_3d']:.4f} |", flush=True)
-            print(json.dumps(row), flush=True)
+    print(f"| data | pair | solver | psnr_3d | ssim_3d |\n|---|---|---|---|---|")
+    for kind in projector.KINDS:
+        for name, projections in sets.items():
+            for solver, run in (("sirt", lambda b: reconstruct.sirt(b, geo, angles, n_iter=args.sirt_iters, kind=kind)),
+                                ("cgls", lambda b: reconstruct.cgls(b, geo, angles, n_iter=args.cgls_iters, kind=kind))):
+                x = run(projections)
+                x = x[0] if isinstance(x, tuple) else x
+                row = {"data": name, "pair": kind, "solver": solver, "psnr_3d": float(get_psnr_3d(x, volume)),
+                       "ssim_3d": float(metrics.ssim_3d(x, volume))}
+                print(f"| {name} | {kind} | {solver} | {row['psnr_3d']:.2f} | {row['ssim_3d']:.4f} |", flush=True)
+                print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
