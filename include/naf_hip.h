@@ -607,6 +607,34 @@ int naf_backproject_scan_siddon(const float *projections, const uint32_t *dims, 
                                 uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
                                 float DSD, float near, float far, int parallel, float *volume, void *stream);
 
+/* P8  the subset step of OS-SART on the Siddon pair (reconstruct.os_sart(kind="siddon")): P4's step with A
+ * = P6 and A^T = P7 restricted to a list of views.  view_index, n_sub, n_scan_views, poses, projections, y and r are P4's (the whole
+ * scan read in place, y and r indexed by launch view); the argument lists are P4's without the sample step.  All arithmetic is fp32,
+ * all offsets are 64-bit.  naf_sart_update is the third launch, unchanged: it knows nothing of the projector.
+ * naf_sart_residual_scan_siddon: pixel (j, row, col) takes the ray naf_generate_rays makes for (v, row, col) and walks it once as P6
+ *   does (the same span, steps, grouped loads and order of additions), keeping beside  acc += volume[voxel] * a  the row sum
+ *   row += a,  a = fl(fl(s_next - s_prev) * |d|).  acc has the bits naf_project_scan_siddon returns for the pixel and row the bits it
+ *   returns on a volume of ones, so
+ *     r = b - acc  (r may be NULL)  and  y = row > 0 ? r / row : 0,   b = projections[v, row, col]
+ *   is R (.) (b - A x) with R = 1 / (A 1) of the fp32 matrix P7 defines, and no A 1 is stored or computed in a pass of its own.  An
+ *   empty span gives r = b and y = 0; a non-finite span, or a view index >= n_scan_views, gives NaN in both, and nothing is read
+ *   through such an index.  No atomics: two calls return the same bits.  `projections` is only read.
+ * naf_sart_backproject_scan_siddon: the transpose over the same list.  Every step of positive length of the ray of pixel
+ *   (j, row, col) adds fl(y * a) to num[voxel] when y = y[j, row, col] != 0 and, where den is not NULL, a to den[voxel], one no-return
+ *   fp32 hardware atomic each.  A ray with y == 0 still sends its a to den.  A step of length 0, an empty or non-finite span and an
+ *   out-of-range view send nothing.  num, den  f32 [n1, n2, n3], two different volumes (den == num is refused), ACCUMULATED INTO.
+ *   With den == NULL the numerator has P7's terms; whether den is given changes no term sent to num.  Sums are exact up to rounding
+ *   and summation order, as in P7.  P6's INVARIANT carries over: no atomic can land outside the volume.
+ * Both refuse what their P4 counterparts refuse, before any launch; n_sub == 0 returns NAF_OK without examining the pointers. */
+int naf_sart_residual_scan_siddon(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub,
+                                  uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near,
+                                  float far, int parallel, const uint32_t *view_index, uint32_t n_scan_views, const float *projections,
+                                  float *y, float *r, void *stream);
+int naf_sart_backproject_scan_siddon(const float *y, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
+                                     const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h,
+                                     float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel,
+                                     float *num, float *den, void *stream);
+
 /* M1 3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),
  * i.e. skimage.metrics.structural_similarity 0.19.3 with its defaults on the whole 3-D volume (the reference's three transposed
  * views are equal up to rounding: a cubic window makes S invariant under axis permutation).  DESIGN.md section 11.

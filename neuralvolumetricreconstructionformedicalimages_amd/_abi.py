@@ -156,6 +156,11 @@ SIGNATURES = {
     "naf_sart_backproject_scan": (_i32, [_vp, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),
                                          _vp, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp, _vp]),
     "naf_sart_update": (_i32, [_vp, _vp, _vp, _u64, _f32, _i32, _i32, _i32, _vp]),
+    "naf_sart_residual_scan_siddon": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32,
+                                             _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "naf_sart_backproject_scan_siddon": (_i32, [_vp, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint32 * 3),
+                                                ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32,
+                                                _f32, _i32, _vp, _vp, _vp]),
     "naf_backproject_scan_gather": (_i32, [_vp, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),
                                            _vp, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp, _vp,
                                            ctypes.c_size_t, _vp]),

@@ -236,4 +236,88 @@ NAF_SIDDON_HD void siddon_scatter(const SiddonGrid &g, const float o[3], const f
     }
 }
 
+// The forward walk of the OS-SART subset step on this pair (include/naf_hip.h P8): siddon_line_integral with
+// the ray's row sum kept beside the integral.  The same span, the same grouped stepping with the loads of group n + 1 issued before
+// group n is used, the same order of additions; next to acc += f * len it keeps row += len.  acc has the bits
+// siddon_line_integral returns for the ray, and row those it returns on a volume of ones (1.0f * len == len), so 1 / row is the
+// weight R of the fp32 matrix P7 defines and no A 1 is ever stored.  Returns the span's kind; acc and row are 0 unless it is
+// kSiddonOk.
+template <class Load>
+NAF_SIDDON_HD SiddonKind siddon_line_integral_and_row(const SiddonGrid &g, const float o[3], const float d[3], float near, float far,
+                                                      Load load, float &acc, float &row) {
+    acc = 0.0f;
+    row = 0.0f;
+    SiddonSpan r;
+    const SiddonKind kind = siddon_span(g, o, d, near, far, r);
+    if (kind != kSiddonOk) return kind;
+    SiddonWalk w;
+    const uint32_t steps = siddon_begin(g, r, w);
+    float len[kSiddonGroup], f[kSiddonGroup];
+    uint64_t offset[kSiddonGroup];
+    NAF_SIDDON_UNROLL
+    for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+        float ds;
+        siddon_step(g, r, w, offset[j], ds);
+        len[j] = ds * r.dn;
+    }
+    NAF_SIDDON_UNROLL
+    for (uint32_t j = 0; j < kSiddonGroup; ++j) f[j] = load(offset[j]);
+    for (uint32_t k = kSiddonGroup; k < steps; k += kSiddonGroup) {
+        float len_next[kSiddonGroup], f_next[kSiddonGroup];
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+            float ds;
+            siddon_step(g, r, w, offset[j], ds);
+            len_next[j] = ds * r.dn;
+        }
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) f_next[j] = load(offset[j]);
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+            acc += f[j] * len[j];
+            row += len[j];
+            f[j] = f_next[j];
+            len[j] = len_next[j];
+        }
+    }
+    NAF_SIDDON_UNROLL
+    for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+        acc += f[j] * len[j];
+        row += len[j];
+    }
+    return kind;
+}
+
+// The paired scatter of the same step: siddon_scatter's span, end-point indices, trip count, crossings and tie order, with two
+// outputs.  Every step of positive length sends its length through den(offset, len) when `want_den`, and fl(y * len) through
+// num(offset, term) when y != 0.  A step of length 0 sends nothing to either, and neither does an empty or non-finite span.  Unlike
+// siddon_scatter it does not return on y == 0 while a den is wanted: such a ray still owes its chord lengths to the column sums.
+// A group is stepped first and sent after.
+template <class Num, class Den>
+NAF_SIDDON_HD void siddon_scatter_pair(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, float y,
+                                       bool want_den, Num num, Den den) {
+    const bool want_num = y != 0.0f;                       // a NaN y is sent, as in siddon_scatter
+    if (!want_num && !want_den) return;
+    SiddonSpan r;
+    if (siddon_span(g, o, d, near, far, r) != kSiddonOk) return;
+    SiddonWalk w;
+    const uint32_t steps = siddon_begin(g, r, w);
+    for (uint32_t k = 0; k < steps; k += kSiddonGroup) {
+        float len[kSiddonGroup];
+        uint64_t offset[kSiddonGroup];
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
+            float ds;
+            siddon_step(g, r, w, offset[j], ds);
+            len[j] = ds * r.dn;
+        }
+        NAF_SIDDON_UNROLL
+        for (uint32_t j = 0; j < kSiddonGroup; ++j)
+            if (len[j] > 0.0f) {
+                if (want_den) den(offset[j], len[j]);
+                if (want_num) num(offset[j], y * len[j]);
+            }
+    }
+}
+
 }  // namespace naf

@@ -11,8 +11,9 @@ that pixel, so projections and training rays agree by construction (no TIGRE axi
 lengths, the ray-voxel intersection projector TIGRE's `Ax` takes by default.  It has no sample step, so `accuracy` plays no part.
 `backproject_rays` and `backproject_scan` take the same `kind`: with "siddon" they add the exact transpose of that projector (P7,
 DESIGN.md section 21), one fp32 atomic per voxel a ray crosses, so A and A^T of either kind are a matched pair.  The Siddon transpose
-has the scatter form only.  The default everywhere is `kind="interpolated"`; `reconstruct.sirt`, `asd_pocs` and `cgls` take `kind`
-as well, the solvers on the fused subset kernels and FDK stay on the interpolated pair.
+has the scatter form only.  The default everywhere is `kind="interpolated"`; `reconstruct.sirt`, `asd_pocs`, `cgls`, `os_sart` and
+`fista_tv` take `kind` as well (the last two on the fused subset kernels of P8); FDK stays on the
+interpolated pair.
 
 There is no CPU fallback, like the rest of the hot path.
 """
@@ -112,6 +113,16 @@ class Scan:
         _abi.check(_abi.lib().naf_sart_backproject_scan(
             _abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self.detector_args(), _abi.ptr(num), _abi.ptr(den),
             _abi.stream_ptr()), "sart_backproject_scan")
+
+    def residual_siddon(self, volume, views, m, projections, y, r):
+        _abi.check(_abi.lib().naf_sart_residual_scan_siddon(                                   # no sample step
+            _abi.ptr(volume), *self._grid_and_poses(), m, *self.detector_args()[:-1], _index_ptr(views), self.N, _abi.ptr(projections),
+            _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr()), "sart_residual_scan_siddon")
+
+    def backproject_views_siddon(self, y, views, m, num, den):
+        _abi.check(_abi.lib().naf_sart_backproject_scan_siddon(                                # no sample step
+            _abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self.detector_args()[:-1], _abi.ptr(num),
+            _abi.ptr(den), _abi.stream_ptr()), "sart_backproject_scan_siddon")
 
     def gather(self, values, views, m, num, den, workspace, first=0, n_scan_views=None):
         """The gather transpose of `m` launch views: a view list into the whole scan, or without one the views from `first` on."""

@@ -5,11 +5,12 @@ back-projection (FDK) as one row filter (`filter.filter_rows`) followed by that 
 kernels and the TV proximal map (`tv.tv_prox`), and CGLS with per-ray weights over the same pair and the vector kernels of `cgls_kernels`.
 They are the baselines the reference took from TIGRE, which has no ROCm build.  DESIGN.md sections 13 to 19.
 
-`sirt`, `asd_pocs`, `cgls` and `ray_length_weights` take `kind`: "interpolated" (the default) is the pair above, "siddon" the
+`sirt`, `asd_pocs`, `cgls`, `os_sart`, `fista_tv` and `ray_length_weights` take `kind`: "interpolated" (the default) is the pair above, "siddon" the
 ray-voxel intersection projector and its exact transpose (include/naf_hip.h P6 / P7, DESIGN.md sections 20 and 21), the matched
 pair for scans made with `project_scan(kind="siddon")`.  A and A^T are always bound to the same kind.  The Siddon transpose sums
-with fp32 atomics and has no atomic-free form, so `kind="siddon"` with `deterministic=True` raises ValueError.  `os_sart`,
-`fista_tv` (the fused subset kernels) and `fdk` (its weights are derived for the interpolated A^T) have no such parameter.
+with fp32 atomics and has no atomic-free form, so `kind="siddon"` with `deterministic=True` raises ValueError.  `os_sart`
+and `fista_tv` run the pair on fused subset kernels of its own (P8), where R = 1 / (A 1) is the row sum the
+forward walk keeps beside A x.  `fdk` (its weights are derived for the interpolated A^T) has no such parameter.
 
 SIRT, as computed here (1 is the all-ones vector of the matching space, ⊙ the element-wise product):
 
@@ -305,7 +306,7 @@ def os_sart_operators(A, AT, b, subsets, n_iter, relax=1.0, relax_red=1.0, nonne
 
 
 def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-distance", relax=1.0, relax_red=1.0, nonneg=True,
-            x0=None, callback=None, weight_cache_bytes=2 << 30, seed=0, deterministic=False):
+            x0=None, callback=None, weight_cache_bytes=2 << 30, seed=0, deterministic=False, kind="interpolated"):
     """OS-SART reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, residual norms).  `n_subsets=None` is one view per subset (SART);
     the subsets and their order come from `subset_order(angles, n_subsets, order, seed)`.  The iteration of `os_sart_operators`,
@@ -313,16 +314,19 @@ def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-
     If n_subsets volumes fit `weight_cache_bytes`, C_s is built on the subset's first visit and kept; otherwise the column sums
     are rebuilt on every visit in the same march as the numerator.  `callback(k, x, residual_norm)` sees the live volume.
     `deterministic=True` takes the atomic-free transpose for the numerator and the column sums on all three routes: two runs
-    return the same bits and the same norms."""
+    return the same bits and the same norms.  `kind="siddon"` runs the same three launches per subset on the ray-voxel intersection
+    pair (naf_hip.h P8): R is the exact row sum of the fp32 matrix, taken in the residual's own walk; it cannot be deterministic."""
     import numpy as np
     import torch
 
     from . import sart
+    _check_kind("os_sart", kind, deterministic)
     relax, relax_red, n_iter = _check_os_sart(relax, relax_red, n_iter)
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)
     subsets = subset_order(angles, len(angles) if n_subsets is None else n_subsets, order, seed)
     most = max(len(s) for s in subsets)
     scan, x, transpose = _device_solve_setup("os_sart", projections, geo, angles, x0, deterministic, most)
+    transpose["kind"] = kind
     lists = [sart.ViewList(s, scan.N, projections.device) for s in subsets]
     y = torch.empty(most, scan.H, scan.W, device=x.device, dtype=torch.float32)
     r = torch.empty_like(y)
@@ -334,7 +338,7 @@ def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-
     for k in range(n_iter):
         total = torch.zeros((), device=x.device, dtype=torch.float64)
         for s, views in enumerate(lists):
-            ys, rs = sart.residual_scan(x, projections, geo, angles, views, y=y[:len(views)], r=r[:len(views)], scan=scan)
+            ys, rs = sart.residual_scan(x, projections, geo, angles, views, y=y[:len(views)], r=r[:len(views)], scan=scan, kind=kind)
             total += (ys.double() * rs.double()).sum()
             if C[s] is not None:
                 sart.backproject_scan(ys, geo, angles, views, num=num, **transpose)
@@ -457,29 +461,33 @@ DEFAULT_FISTA_TV_LAMBDA = 1e-4          # DESIGN.md section 18's sweep on the sy
 
 
 def fista_tv(projections, geo, angles, n_iter=30, lam=DEFAULT_FISTA_TV_LAMBDA, tv_iters=20, nonneg=True, x0=None, callback=None,
-             deterministic=False):
+             deterministic=False, kind="interpolated"):
     """FISTA-TV reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry) at `angles` ->
     (float32 volume of geo.nVoxel on the projections' device, residual norms at the extrapolated points).  The iteration of
     `fista_tv_operators` on the kernels: per iteration one `sart.residual_scan` and one `sart.backproject_scan` over all views
     (the first also returns A^T 1, whose maximum is L) and `tv.tv_prox` with `tv_iters` dual iterations, the dual carried from one
     iteration to the next as a warm start.  `lam` is the weight of TV in F (the module docstring; the default is DESIGN.md section
     18's).  `callback(k, x, residual_norm)` reads the norm back, which otherwise happens once at the end.
-    `deterministic=True` takes the atomic-free transpose: two runs return the same bits and the same norms."""
+    `deterministic=True` takes the atomic-free transpose: two runs return the same bits and the same norms.  `kind="siddon"` runs
+    the two scan launches on the ray-voxel intersection pair (naf_hip.h P8); with R = 1 / (A 1) the exact row sum of the fp32 matrix,
+    A^T R A 1 = A^T 1 holds for that matrix itself and L stays a rigorous bound.  It cannot be deterministic."""
     import torch
 
     from . import sart, tv
+    _check_kind("fista_tv", kind, deterministic)
     n_iter, lam = _check_fista_tv(n_iter, lam)
     tv_iters = int(tv_iters)
     if tv_iters < 0:
         raise ValueError(f"fista_tv: tv_iters must be >= 0, got {tv_iters}")
     scan, x, transpose = _device_solve_setup("fista_tv", projections, geo, angles, x0, deterministic)
+    transpose["kind"] = kind
     yw = torch.empty(scan.N, scan.H, scan.W, device=x.device, dtype=torch.float32)
     res = torch.empty_like(yw)
     num = torch.zeros_like(x)
     dual = torch.zeros((3, *scan.dims), device=x.device, dtype=torch.float32)
     y, t, L, norms = x, 1.0, None, []
     for k in range(n_iter):
-        sart.residual_scan(y, projections, geo, angles, None, y=yw, r=res, scan=scan)             # yw = R ⊙ res
+        sart.residual_scan(y, projections, geo, angles, None, y=yw, r=res, scan=scan, kind=kind)  # yw = R ⊙ res
         norms.append((yw.double() * res.double()).sum())
         if L is None:
             den = torch.zeros_like(x)

@@ -6,7 +6,9 @@ include/naf_hip.h P4).
     update            x += relax * num / den, clamped at 0; num = 0; den = 0 where asked
 
 A and A^T are `projector.project_scan` and `projector.backproject_scan` restricted to the list; `reconstruct.os_sart` is the solver
-on top.  There is no CPU fallback, like the rest of the hot path.
+on top.  `residual_scan` and `backproject_scan` take `kind`: "siddon" runs the same step on the ray-voxel intersection pair
+(`naf_sart_residual_scan_siddon`, `naf_sart_backproject_scan_siddon`; P8), where `len` is the ray's row sum
+A 1 taken in the same walk as A x; `update` serves both kinds.  There is no CPU fallback, like the rest of the hot path.
 """
 from __future__ import annotations
 
@@ -27,12 +29,14 @@ def _views(views, scan):
     return views, len(views)
 
 
-def residual_scan(volume, projections, geo, angles, views=None, y=None, r=None, want_r=True, scan=None):
+def residual_scan(volume, projections, geo, angles, views=None, y=None, r=None, want_r=True, scan=None, kind="interpolated"):
     """Weighted residual of the views `views` (indices into the scan; None: all, in order) of the scan `projections` [N, H, W] for
     the volume `volume` -> (y, r), float32 [len(views), H, W]: r = b - A x and y = r / len (0 on a ray that misses the volume).
     `y` and `r` may be given to be written into; `want_r=False` skips r and returns None for it.  `scan` is a `Scan` of the same
-    `geo` and `angles` to reuse across calls."""
+    `geo` and `angles` to reuse across calls.  `kind="siddon"` takes A of the ray-voxel intersection projector (P6) and for `len`
+    the ray's row sum (A 1)_r, the bits `project_scan(ones, kind="siddon")` returns (P8)."""
     who = "sart.residual_scan"
+    projector.check_kind(kind, who)
     _abi.check_volume(volume, who)
     projector.check_geometry(volume, geo)
     scan = projector.scan_for(geo, angles, volume.device, scan, "sart")
@@ -50,17 +54,20 @@ def residual_scan(volume, projections, geo, angles, views=None, y=None, r=None, 
     else:
         _abi.check_stack(r, shape, volume, who, "r")
     if m:
-        scan.residual(volume, views, m, projections, y, r)
+        (scan.residual_siddon if kind == "siddon" else scan.residual)(volume, views, m, projections, y, r)
     return y, r
 
 
-def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None, method="scatter", workspace=None):
+def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None, method="scatter", workspace=None,
+                     kind="interpolated"):
     """Transpose over the same view list: adds A_s^T y into `num` (None: a zeroed volume) and, if `den` is given, A_s^T 1 into
     `den`, both float32 volumes on the voxel grid of `geo` that are accumulated into -> num.  `method="gather"` takes the
     atomic-free gather form (naf_hip.h P5; the same bits on every call) instead of the scatter; `workspace` is then a span table
-    from `projector.gather_workspace` to reuse across calls (None: one is made; False: none, the spans are recomputed)."""
+    from `projector.gather_workspace` to reuse across calls (None: one is made; False: none, the spans are recomputed).
+    `kind="siddon"` is the transpose of the ray-voxel intersection projector (P7) with the paired column sums (P8); it sums with
+    atomics only, so with `method="gather"` it raises ValueError."""
     who = "sart.backproject_scan"
-    projector.check_method(method, who)
+    projector.check_kind_and_method(kind, method, who)
     if not isinstance(y, torch.Tensor) or not y.is_cuda:
         raise RuntimeError(f"{who}: y must be a CUDA/HIP tensor (no CPU path)")
     scan = projector.scan_for(geo, angles, y.device, scan, "sart")
@@ -85,7 +92,7 @@ def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None, 
                              "(projector.gather_workspace), None or False")
         scan.gather(y, views, m, num, den, workspace)
     elif m:
-        scan.backproject_views(y, views, m, num, den)
+        (scan.backproject_views_siddon if kind == "siddon" else scan.backproject_views)(y, views, m, num, den)
     return num
 
 

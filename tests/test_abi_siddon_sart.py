@@ -1,0 +1,78 @@
+"""The two entry points of the OS-SART subset step on the Siddon pair (include/naf_hip.h P8) are exported, declared and bound,
+refuse bad arguments before any launch with a message that names them, and the ABI version is the one existing callers pin.  No GPU
+needed: nothing is launched."""
+import ctypes
+import math
+import os
+import re
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {"naf_sart_residual_scan_siddon": 21, "naf_sart_backproject_scan_siddon": 20}
+
+
+def test_symbols_are_declared_bound_and_exported():
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi, build
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "naf_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(naf_[a-z0-9_]+)\s*\(", text))
+    lib = _abi.lib()
+    raw = ctypes.CDLL(build.LIB_PATH)
+    for name, n_args in NAMES.items():
+        assert name in declared and name in _abi.SIGNATURES and hasattr(raw, name)
+        assert len(_abi.SIGNATURES[name][1]) == n_args and getattr(lib, name).restype is ctypes.c_int
+        # P4's argument list without the sample step
+        interpolated = _abi.SIGNATURES[name[:-len("_siddon")]][1]
+        assert len(interpolated) == n_args + 1
+        assert [a for a in interpolated if a is not ctypes.c_float] == [a for a in _abi.SIGNATURES[name][1] if a is not ctypes.c_float]
+    assert "naf_sart_update_siddon" not in declared                     # the third launch is P4's own
+    assert lib.naf_abi_version() == 5
+
+
+def test_arguments_are_refused_before_any_launch():
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi
+    lib = _abi.lib()
+    vol, other, values, poses, proj = (ctypes.c_void_p(v) for v in (4096, 20480, 12288, 16384, 8192))
+    dv = (ctypes.c_float * 3)(1e-3, 7e-4, 1.3e-3)
+    dims = (ctypes.c_uint32 * 3)(17, 9, 33)
+
+    def refused(rc, what, who):
+        message = lib.naf_last_error()
+        return rc == -1 and what in message and who + b":" in message
+
+    def ref(p):
+        return ctypes.byref(p) if p is not None else None
+
+    def residual(volume=vol, d=dims, dvoxel=dv, p=poses, n_sub=2, w=24, h=24, DSD=1.5, parallel=0, index=None, n_scan=2, b=proj,
+                 y=values, r=None):
+        return lib.naf_sart_residual_scan_siddon(volume, ref(d), ref(dvoxel), p, n_sub, w, h, 1e-3, 1e-3, 0.0, 0.0, DSD, 0.9, 1.1,
+                                                 parallel, index, n_scan, b, y, r, None)
+
+    def transpose(y=values, index=None, n_sub=2, n_scan=2, d=dims, dvoxel=dv, p=poses, w=24, h=24, DSD=1.5, parallel=0, num=vol,
+                  den=None):
+        return lib.naf_sart_backproject_scan_siddon(y, index, n_sub, n_scan, ref(d), ref(dvoxel), p, w, h, 1e-3, 1e-3, 0.0, 0.0, DSD,
+                                                    0.9, 1.1, parallel, num, den, None)
+
+    R, B = b"sart_residual_scan_siddon", b"sart_backproject_scan_siddon"
+    # empty calls are successful no-ops whatever the pointers
+    assert residual(volume=None, d=None, dvoxel=None, p=None, n_sub=0, b=None, y=None) == 0
+    assert transpose(y=None, n_sub=0, d=None, dvoxel=None, p=None, num=None) == 0
+    assert transpose(n_sub=0, den=vol) == 0
+    for name in ("volume", "d", "dvoxel", "p", "b", "y"):
+        assert refused(residual(**{name: None}), b"null pointer", R), name
+    for name in ("y", "d", "dvoxel", "p", "num"):
+        assert refused(transpose(**{name: None}), b"null pointer", B), name
+    assert refused(transpose(den=vol), b"two volumes", B)
+    for call, who in ((residual, R), (transpose, B)):
+        assert refused(call(d=(ctypes.c_uint32 * 3)(17, 0, 33)), b"zero volume dimension", who)
+        for bad in (0.0, -1e-3, math.inf, math.nan):
+            for axis in range(3):
+                d = (ctypes.c_float * 3)(1e-3, 1e-3, 1e-3)
+                d[axis] = bad
+                assert refused(call(dvoxel=d), b"voxel size must be > 0", who)
+        assert refused(call(w=0), b"empty detector", who)
+        assert refused(call(h=0), b"empty detector", who)
+        for bad in (0.0, -1.0, math.nan):
+            assert refused(call(DSD=bad), b"DSD must be > 0", who)
+        assert call(DSD=0.0, parallel=1, n_sub=0) == 0
+        assert refused(call(n_sub=3), b"n_sub must be <= n_scan_views", who)      # without a view list
+        assert refused(call(n_sub=3, index=other, n_scan=0), b"zero views", who)
+        assert refused(call(n_sub=0xffffffff, index=other, n_scan=8, w=0xffff, h=0xffff), b"too many pixels", who)

@@ -3,9 +3,9 @@
 
 The analytic phantom at 64^3 and 50 views gives three training sets for one voxel volume: its projections by the interpolated
 projector (the operator the baselines reconstruct with), by the Siddon projector (another discretisation)
-and the phantom's analytic line integrals.  `reconstruct.sirt` (50 iterations) and `reconstruct.cgls` (15 iterations) run on
-each, once on the interpolated pair and once on the Siddon pair (kind="siddon": that projector and its exact transpose, DESIGN.md
-section 21); printed are psnr_3d and ssim_3d against the voxel volume.  A measurement, not a test.
+and the phantom's analytic line integrals.  `reconstruct.sirt` (50 iterations), `reconstruct.cgls` (15 iterations) and `reconstruct.os_sart`
+(20 iterations, one view per subset) run on each, once on the interpolated pair and once on the Siddon pair (kind="siddon": that
+projector and its exact transpose, DESIGN.md sections 21 and 22); printed are psnr_3d and ssim_3d against the voxel volume.  A measurement, not a test.
 
     python tools/inverse_crime.py [--n 64] [--views 50]
 """
@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--views", type=int, default=50)
     ap.add_argument("--sirt-iters", type=int, default=50)
     ap.add_argument("--cgls-iters", type=int, default=15)
+    ap.add_argument("--sart-iters", type=int, default=20)
     args = ap.parse_args()
     from neuralvolumetricreconstructionformedicalimages_amd import metrics, phantom, projector, reconstruct
     from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry, RayGenerator
@@ -44,7 +45,8 @@ def main():
     for kind in projector.KINDS:
         for name, projections in sets.items():
             for solver, run in (("sirt", lambda b: reconstruct.sirt(b, geo, angles, n_iter=args.sirt_iters, kind=kind)),
-                                ("cgls", lambda b: reconstruct.cgls(b, geo, angles, n_iter=args.cgls_iters, kind=kind))):
+                                ("cgls", lambda b: reconstruct.cgls(b, geo, angles, n_iter=args.cgls_iters, kind=kind)),
+                                ("os_sart", lambda b: reconstruct.os_sart(b, geo, angles, n_iter=args.sart_iters, kind=kind))):
                 x = run(projections)
                 x = x[0] if isinstance(x, tuple) else x
                 row = {"data": name, "pair": kind, "solver": solver, "psnr_3d": float(get_psnr_3d(x, volume)),

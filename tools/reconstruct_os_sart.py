@@ -6,6 +6,7 @@ tools/reconstruct_sirt.py does, whose loading and scoring code this tool runs.
     python tools/reconstruct_os_sart.py --scan data/chest_50.pickle --iters 20                      # one view per subset: SART
     python tools/reconstruct_os_sart.py --scan data/chest_50.pickle --iters 20 --subsets 10 --order random --relax-red 0.99
     python tools/reconstruct_os_sart.py --scan data/chest_50.pickle --iters 5 --init fdk --out sart_chest.npy
+    python tools/reconstruct_os_sart.py --scan data/chest_50.pickle --iters 20 --projector siddon   # the Siddon pair
 
 Prints one JSON line: psnr_3d, ssim_3d, the first and last weighted residual (each subset's taken before its update) and the time.
 """
@@ -31,12 +32,13 @@ def main(argv=None):
     def solve(args, proj, geo, angles):
         x, norms = os_sart(proj, geo, angles, n_iter=args.iters, n_subsets=args.subsets, order=args.order, relax=args.relax,
                            relax_red=args.relax_red, nonneg=not args.no_nonneg, x0=reconstruct_sirt.start_volume(args, proj, geo, angles),
-                           weight_cache_bytes=int(args.weight_cache_gib * 2 ** 30), seed=args.seed, deterministic=args.deterministic)
+                           weight_cache_bytes=int(args.weight_cache_gib * 2 ** 30), seed=args.seed, deterministic=args.deterministic,
+                           kind=args.projector)
         extra = {"subsets": args.subsets or len(angles), "order": args.order, "relax_red": args.relax_red,
                  "weights_cached": (args.subsets or len(angles)) * x.numel() * 4 <= int(args.weight_cache_gib * 2 ** 30)}
         return x, norms, extra
 
-    return reconstruct_sirt.main(argv, solve=solve, add_arguments=add_arguments, description=__doc__)
+    return reconstruct_sirt.main(argv, solve=solve, add_arguments=add_arguments, description=__doc__, projector_kinds=True)
 
 
 if __name__ == "__main__":

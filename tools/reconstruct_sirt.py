@@ -44,7 +44,8 @@ def main(argv=None, solve=_sirt, add_arguments=None, description=None, iterative
     """`solve(args, proj, geo, angles) -> (volume, residuals, extra result fields)` and `add_arguments(parser)` let another
     baseline (tools/reconstruct_asd_pocs.py, tools/reconstruct_fdk.py) run behind the same loading, timing and scoring; a baseline
     that is not `iterative` has no --iters, --relax, --no-nonneg and --init.  `projector_kinds` adds --projector for a solver that
-    takes `kind=` (SIRT itself, ASD-POCS, CGLS) and reports it; the others keep the interpolated pair and have no such option."""
+    takes `kind=` (SIRT itself, ASD-POCS, CGLS, OS-SART, FISTA-TV) and reports it; the others keep the interpolated pair and have no
+    such option."""
     projector_kinds = projector_kinds or solve is _sirt
     from neuralvolumetricreconstructionformedicalimages_amd import metrics
     from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
@@ -64,7 +65,7 @@ def main(argv=None, solve=_sirt, add_arguments=None, description=None, iterative
     if projector_kinds:
         ap.add_argument("--projector", choices=["interpolated", "siddon"], default="interpolated",
                         help="the pair A, A^T the solver runs on: the interpolated projector and its transpose, or the ray-voxel "
-                             "intersection (Siddon) projector and its exact transpose (DESIGN.md section 21; not with --deterministic)")
+                             "intersection (Siddon) projector and its exact transpose (DESIGN.md sections 21 and 22; not with --deterministic)")
     if add_arguments is not None:
         add_arguments(ap)
     args = ap.parse_args(argv)

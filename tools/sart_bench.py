@@ -6,6 +6,12 @@ composed from projector.project_scan / projector.backproject_scan on gathered vi
 
     python tools/sart_bench.py
     python tools/sart_bench.py --views 10 --windows 5
+    python tools/sart_bench.py --siddon          # the step on the Siddon pair
+
+`--siddon` times the same iteration on the ray-voxel intersection pair: the fused Siddon step (naf_sart_residual_scan_siddon,
+naf_sart_backproject_scan_siddon, naf_sart_update) with C_s cached and rebuilt, the iteration composed from
+project_scan / backproject_scan(kind="siddon") and torch passes, and the fused interpolated step, on data made with the Siddon
+projector.  The four forms alternate window by window in one run, so a drift of the machine falls on all of them alike.
 
 Reported: device-event time of one iteration in ms (median, min and max of `--windows` windows after `--warmup` iterations), and
 the largest difference between the volumes of the fused and the composed form after the timed iterations, relative to the
@@ -43,42 +49,59 @@ def _inverse(a):
     return torch.where(a > 0, 1.0 / a, torch.zeros_like(a))
 
 
-def fused_iteration(b, geo, angles, lists, scan, x, num, den, C, y, r):
+def fused_iteration(b, geo, angles, lists, scan, x, num, den, C, y, r, kind="interpolated"):
     """One pass over the subsets as reconstruct.os_sart runs it; C[s] is None where the column sums are rebuilt on every visit."""
     from neuralvolumetricreconstructionformedicalimages_amd import sart
     total = torch.zeros((), device=x.device, dtype=torch.float64)
     for s, views in enumerate(lists):
-        ys, rs = sart.residual_scan(x, b, geo, angles, views, y=y[:len(views)], r=r[:len(views)], scan=scan)
+        ys, rs = sart.residual_scan(x, b, geo, angles, views, y=y[:len(views)], r=r[:len(views)], scan=scan, kind=kind)
         total += (ys.double() * rs.double()).sum()
         if C[s] is not None:
-            sart.backproject_scan(ys, geo, angles, views, num=num, scan=scan)
+            sart.backproject_scan(ys, geo, angles, views, num=num, scan=scan, kind=kind)
             sart.update(x, num, C[s], 1.0, True, den_is_reciprocal=True)
         else:
-            sart.backproject_scan(ys, geo, angles, views, num=num, den=den, scan=scan)
+            sart.backproject_scan(ys, geo, angles, views, num=num, den=den, scan=scan, kind=kind)
             sart.update(x, num, den, 1.0, True, zero_den=True)
     return total
 
 
-def composed_iteration(b, geo, angles, subsets, x, R, C):
+def composed_iteration(b, geo, angles, subsets, x, R, C, kind="interpolated"):
     """The same pass from today's entry points: gathered views, a zeroed accumulator per step, torch element-wise passes.  Returns
     the new volume.  C[s] is None where the column sums are rebuilt on every visit (one more back-projection of ones)."""
     from neuralvolumetricreconstructionformedicalimages_amd import projector
     total = torch.zeros((), device=x.device, dtype=torch.float64)
     for s, views in enumerate(subsets):
         sub = angles[views]
-        rs = b[views] - projector.project_scan(x, geo, sub)
+        rs = b[views] - projector.project_scan(x, geo, sub, kind=kind)
         ys = R[views] * rs
         total += (ys.double() * rs.double()).sum()
-        Cs = C[s] if C[s] is not None else _inverse(projector.backproject_scan(torch.ones_like(ys), geo, sub))
-        x = torch.clamp(x + 1.0 * (Cs * projector.backproject_scan(ys, geo, sub)), 0, None)
+        Cs = C[s] if C[s] is not None else _inverse(projector.backproject_scan(torch.ones_like(ys), geo, sub, kind=kind))
+        x = torch.clamp(x + 1.0 * (Cs * projector.backproject_scan(ys, geo, sub, kind=kind)), 0, None)
     return x, total
 
 
-def run(views, warmup, windows):
+def _time_alternating(forms, warmup, windows):
+    """name -> [median, min, max] ms of one call, the forms taking turns window by window after `warmup` calls of each."""
+    for fn in forms.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    out = {name: [] for name in forms}
+    for _ in range(windows):
+        for name, fn in forms.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            out[name].append(a.elapsed_time(b))
+    return {name: [round(v, 3) for v in (statistics.median(t), min(t), max(t))] for name, t in out.items()}
+
+
+def _chest(views):
     from project_bench import SHAPES
-    from neuralvolumetricreconstructionformedicalimages_amd import phantom, projector, sart
+    from neuralvolumetricreconstructionformedicalimages_amd import phantom
     from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
-    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import subset_order
     nv, det, chest_views, pitch, vox = SHAPES["chest"]
     views = views or chest_views
     data = phantom.scan_geometry(256)
@@ -86,7 +109,56 @@ def run(views, warmup, windows):
     geo = ConeGeometry(data)
     table = phantom.ellipsoid_table(seed=0, extent=float(geo.sVoxel[0]) / 2)
     truth = phantom.volume(geo, table, device="cuda", slab=max(1, (1 << 22) // (nv * nv)))
-    angles = np.linspace(0, np.pi, views + 1)[:-1]
+    return geo, truth, np.linspace(0, np.pi, views + 1)[:-1], nv, det, views
+
+
+def run_siddon(views, warmup, windows):
+    """The iteration on the Siddon pair, fused (cached and rebuilt) and composed, and the fused interpolated one, in turns."""
+    from neuralvolumetricreconstructionformedicalimages_amd import projector, sart
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import subset_order
+    geo, truth, angles, nv, det, views = _chest(views)
+    b = projector.project_scan(truth, geo, angles, kind="siddon")
+    subsets = [[int(v) for v in s] for s in subset_order(angles, views)]
+    scan = sart.Scan(geo, angles, "cuda")
+    lists = [sart.ViewList(s, views, "cuda") for s in subsets]
+    res = {"volume": [nv] * 3, "detector": [det, det], "views": views, "subsets": len(subsets), "data": "siddon"}
+    ones = torch.ones(1, det, det, device="cuda")
+    C = {kind: [_inverse(projector.backproject_scan(ones, geo, angles[s], kind=kind)) for s in subsets] for kind in projector.KINDS}
+    R = _inverse(projector.project_scan(torch.ones_like(truth), geo, angles, kind="siddon"))
+    none = [None] * len(lists)
+    y = torch.empty(1, det, det, device="cuda")
+    r = torch.empty_like(y)
+    num, den = torch.zeros_like(truth), torch.zeros_like(truth)
+    x = {name: torch.zeros_like(truth) for name in ("siddon_fused_cached", "siddon_fused_rebuilt", "siddon_composed_cached",
+                                                    "interpolated_fused_cached")}
+
+    def composed():
+        x["siddon_composed_cached"], _ = composed_iteration(b, geo, angles, subsets, x["siddon_composed_cached"], R, C["siddon"], "siddon")
+
+    forms = {
+        "siddon_fused_cached": lambda: fused_iteration(b, geo, angles, lists, scan, x["siddon_fused_cached"], num, den, C["siddon"], y,
+                                                       r, "siddon"),
+        "siddon_fused_rebuilt": lambda: fused_iteration(b, geo, angles, lists, scan, x["siddon_fused_rebuilt"], num, den, none, y, r,
+                                                        "siddon"),
+        "siddon_composed_cached": composed,
+        "interpolated_fused_cached": lambda: fused_iteration(b, geo, angles, lists, scan, x["interpolated_fused_cached"], num, den,
+                                                             C["interpolated"], y, r),
+    }
+    for name, t in _time_alternating(forms, warmup, windows).items():
+        res[name + "_ms"] = t
+    top = x["siddon_composed_cached"].max()
+    res["fused_vs_composed_max_rel_diff"] = float((x["siddon_fused_cached"] - x["siddon_composed_cached"]).abs().max() / top)
+    res["rebuilt_vs_cached_max_rel_diff"] = float((x["siddon_fused_cached"] - x["siddon_fused_rebuilt"]).abs().max() / top)
+    res["speedup_fused_over_composed"] = round(res["siddon_composed_cached_ms"][0] / res["siddon_fused_cached_ms"][0], 2)
+    res["rebuilt_over_cached"] = round(res["siddon_fused_rebuilt_ms"][0] / res["siddon_fused_cached_ms"][0], 2)
+    res["interpolated_over_siddon"] = round(res["interpolated_fused_cached_ms"][0] / res["siddon_fused_cached_ms"][0], 2)
+    return res
+
+
+def run(views, warmup, windows):
+    from neuralvolumetricreconstructionformedicalimages_amd import projector, sart
+    from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import subset_order
+    geo, truth, angles, nv, det, views = _chest(views)
     b = projector.project_scan(truth, geo, angles)
     subsets = [[int(v) for v in s] for s in subset_order(angles, views)]
     scan = sart.Scan(geo, angles, "cuda")
@@ -126,8 +198,9 @@ def main():
     ap.add_argument("--views", type=int, default=None, help="views of the scan, one per subset (default: the chest scan's 50)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--siddon", action="store_true", help="time the step on the Siddon pair, next to the fused interpolated step")
     args = ap.parse_args()
-    print(json.dumps(run(args.views, args.warmup, args.windows)), flush=True)
+    print(json.dumps((run_siddon if args.siddon else run)(args.views, args.warmup, args.windows)), flush=True)
 
 
 if __name__ == "__main__":
