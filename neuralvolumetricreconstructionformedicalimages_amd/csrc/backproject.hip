@@ -44,14 +44,12 @@ extern "C" int naf_backproject_rays(const float *values, const float *rays, uint
                                     const float *dvoxel, float step, float *volume, void *stream) {
     if (n_rays == 0) return NAF_OK;
     ProjVolume v;
-    const int rc = make_volume("backproject_rays", volume, n1, n2, n3, dvoxel, step, &v);
+    uint32_t blocks;
+    int rc = make_volume("backproject_rays", volume, n1, n2, n3, dvoxel, step, &v);
+    if (rc == NAF_OK) rc = make_ray_launch("backproject_rays", rays, values, n_rays, &blocks);
     if (rc != NAF_OK) return rc;
-    if (!values || !rays) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays: null pointer");
-    if (((uintptr_t)rays) & 15u) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays: rays must be 16-byte aligned");
-    const uint64_t blocks = (n_rays + 255u) / 256u;
-    if (blocks > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays: too many rays for one call");
     { ProfScope prof_("backproject_rays_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(backproject_rays_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, v, volume, values, rays,
+      hipLaunchKernelGGL(backproject_rays_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, v, volume, values, rays,
                          n_rays); }
     return check_launch("backproject_rays_kernel");
 }

@@ -55,14 +55,12 @@ extern "C" int naf_project_rays(const float *volume, uint32_t n1, uint32_t n2, u
                                 uint64_t n_rays, float step, float *out, void *stream) {
     if (n_rays == 0) return NAF_OK;
     ProjVolume v;
-    const int rc = make_volume("project_rays", volume, n1, n2, n3, dvoxel, step, &v);
+    uint32_t blocks;
+    int rc = make_volume("project_rays", volume, n1, n2, n3, dvoxel, step, &v);
+    if (rc == NAF_OK) rc = make_ray_launch("project_rays", rays, out, n_rays, &blocks);
     if (rc != NAF_OK) return rc;
-    if (!rays || !out) return fail(NAF_ERR_INVALID_ARGUMENT, "project_rays: null pointer");
-    if (((uintptr_t)rays) & 15u) return fail(NAF_ERR_INVALID_ARGUMENT, "project_rays: rays must be 16-byte aligned");
-    const uint64_t blocks = (n_rays + 255u) / 256u;
-    if (blocks > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "project_rays: too many rays for one call");
     { ProfScope prof_("project_rays_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(project_rays_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, v, rays, out, n_rays); }
+      hipLaunchKernelGGL(project_rays_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, v, rays, out, n_rays); }
     return check_launch("project_rays_kernel");
 }
 

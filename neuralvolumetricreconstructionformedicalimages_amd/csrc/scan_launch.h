@@ -1,8 +1,9 @@
-// scan_launch.h -- what the six scan entry points (naf_project_scan, naf_project_scan_siddon, naf_backproject_scan,
-// naf_sart_residual_scan, naf_sart_backproject_scan, naf_backproject_scan_gather) share: the host checks of "a scan is ..." with the
-// launch grid, the view list, and the decode of a workgroup into a detector pixel.
+// scan_launch.h -- what the scan entry points (naf_project_scan, naf_backproject_scan, naf_sart_residual_scan,
+// naf_sart_backproject_scan, naf_backproject_scan_gather and the _siddon ones) share: the host checks of "a scan is ..." with the
+// launch grid, the view list, and the decode of a workgroup into a detector pixel; and, for the four
+// ray-list entry points, the host checks of "a list of rays is ...".
 //
-// Layout of the five tile kernels: one lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave, so that the samples of
+// Layout of the tile kernels: one lane per detector pixel, 16 x 16 pixels per workgroup, 8 x 8 per wave, so that the samples of
 // neighbouring rays at equal k land in the same or neighbouring cache lines; blockIdx.x = launch view * tiles_per_view + tile.  The
 // gather launches over voxels and takes only the checks and the RayGeo from here.
 #pragma once
@@ -70,6 +71,22 @@ inline int make_scan_launch(const char *who, const float *volume, std::initializ
     s->g = RayGeo{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
     s->tiles_x = tx;
     s->tiles_per_view = (uint32_t)tiles;
+    return NAF_OK;
+}
+
+// Host: the checks of a ray-list call (`rays` is [n_rays, 8], read as two float4 per ray; `other` is the call's one further device
+// pointer) and its grid: one lane per ray, `blocks` workgroups of 256.
+inline int make_ray_launch(const char *who, const float *rays, const void *other, uint64_t n_rays, uint32_t *blocks) {
+    const char *what = nullptr;
+    if (!rays || !other) what = "null pointer";
+    else if (((uintptr_t)rays) & 15u) what = "rays must be 16-byte aligned";
+    else if ((n_rays + 255u) / 256u > 0x7fffffffull) what = "too many rays for one call";
+    if (what) {
+        char msg[160];
+        std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    *blocks = (uint32_t)((n_rays + 255u) / 256u);
     return NAF_OK;
 }
 

@@ -7,19 +7,11 @@
 // Layout of the scan kernel: scan_launch.h's, rays made in registers, so the 64 lanes of a wave (8 x 8 pixels) at equal step add
 // into a small neighbourhood of the volume.  One no-return fp32 hardware atomic per voxel of positive chord length; a group of
 // kSiddonGroup steps is walked before its atomics are issued, and nothing waits for them.
-#include "scan_launch.h"
-#include "siddon_device.h"
+#include "siddon_launch.h"
 
 namespace naf {
 
 namespace {
-
-__device__ __forceinline__ void siddon_scatter_ray(const SiddonGrid &grid, float *__restrict__ volume, float4 a, float4 b, float y) {
-    const float o[3] = {a.x, a.y, a.z}, d[3] = {a.w, b.x, b.y};
-    siddon_scatter(grid, o, d, b.z, b.w, y, [volume](uint64_t offset, float term) {
-        atomicAdd(volume + offset, term);                     // no-return global_atomic_add_f32
-    });
-}
 
 __global__ void __launch_bounds__(256)
 siddon_backproject_rays_kernel(SiddonGrid grid, float *__restrict__ volume, const float *__restrict__ values,
@@ -27,7 +19,7 @@ siddon_backproject_rays_kernel(SiddonGrid grid, float *__restrict__ volume, cons
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rays) return;
     const float4 *r = reinterpret_cast<const float4 *>(rays + i * 8);
-    siddon_scatter_ray(grid, volume, r[0], r[1], values[i]);
+    siddon_transpose(grid, siddon_ray(r[0], r[1]), SiddonDepositValue{volume, values[i]});
 }
 
 // The launch's poses and projections come pre-offset to its first view.
@@ -38,7 +30,7 @@ siddon_backproject_scan_kernel(SiddonGrid grid, float *__restrict__ volume, cons
     if (!scan_pixel(tiles_x, tiles_per_view, g, p)) return;
     float4 r[2];
     make_pixel_ray(poses + (size_t)p.j * 12, p.row, p.col, g, r);
-    siddon_scatter_ray(grid, volume, r[0], r[1], projections[(uint64_t)p.j * g.W * g.H + p.pixel]);
+    siddon_transpose(grid, siddon_ray(r[0], r[1]), SiddonDepositValue{volume, projections[(uint64_t)p.j * g.W * g.H + p.pixel]});
 }
 
 }  // namespace
@@ -50,17 +42,13 @@ using namespace naf;
 extern "C" int naf_backproject_rays_siddon(const float *values, const float *rays, uint64_t n_rays, uint32_t n1, uint32_t n2,
                                            uint32_t n3, const float *dvoxel, float *volume, void *stream) {
     if (n_rays == 0) return NAF_OK;
-    ProjVolume checked;                                         // there is no sample step here: any valid one passes the checks
-    const int rc = make_volume("backproject_rays_siddon", volume, n1, n2, n3, dvoxel, 1.0f, &checked);
-    if (rc != NAF_OK) return rc;
-    if (!values || !rays) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays_siddon: null pointer");
-    if (((uintptr_t)rays) & 15u) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays_siddon: rays must be 16-byte aligned");
-    const uint64_t blocks = (n_rays + 255u) / 256u;
-    if (blocks > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "backproject_rays_siddon: too many rays for one call");
     SiddonGrid grid;
-    siddon_grid(n1, n2, n3, dvoxel, &grid);
+    uint32_t blocks;
+    int rc = make_siddon_grid("backproject_rays_siddon", volume, n1, n2, n3, dvoxel, &grid);
+    if (rc == NAF_OK) rc = make_ray_launch("backproject_rays_siddon", rays, values, n_rays, &blocks);
+    if (rc != NAF_OK) return rc;
     { ProfScope prof_("siddon_backproject_rays_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(siddon_backproject_rays_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, grid, volume,
+      hipLaunchKernelGGL(siddon_backproject_rays_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grid, volume,
                          values, rays, n_rays); }
     return check_launch("siddon_backproject_rays_kernel");
 }
@@ -70,11 +58,10 @@ extern "C" int naf_backproject_scan_siddon(const float *projections, const uint3
                                            float ov, float DSD, float near, float far, int parallel, float *volume, void *stream) {
     if (n_projections == 0) return NAF_OK;
     ScanLaunch s;
-    const int rc = make_scan_launch("backproject_scan_siddon", volume, {projections}, dims, dvoxel, poses, n_projections, det_w, det_h,
-                                    du, dv, ou, ov, DSD, near, far, parallel, 1.0f, &s);
-    if (rc != NAF_OK) return rc;
     SiddonGrid grid;
-    siddon_grid(dims[0], dims[1], dims[2], dvoxel, &grid);
+    const int rc = make_siddon_scan_launch("backproject_scan_siddon", volume, {projections}, dims, dvoxel, poses, n_projections, det_w,
+                                           det_h, du, dv, ou, ov, DSD, near, far, parallel, &s, &grid);
+    if (rc != NAF_OK) return rc;
     { ProfScope prof_("siddon_backproject_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(siddon_backproject_scan_kernel, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream,
                          grid, volume, projections, poses, s.g, s.tiles_x, s.tiles_per_view); }

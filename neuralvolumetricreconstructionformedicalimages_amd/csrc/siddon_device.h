@@ -164,94 +164,39 @@ NAF_SIDDON_HD void siddon_step(const SiddonGrid &g, const SiddonSpan &r, SiddonW
     for (int a = 0; a < 3; ++a) w.next[a] = pick[a] ? c : w.next[a];
 }
 
-// Line integral of one ray (o, d, near, far) through the piecewise-constant volume `load` reads (load(offset) -> float, one call per
-// step).  fp32 sum in traversal order of value * ((s_next - s_prev) * |d|).  The loads of a group of steps are issued before the
-// first of them is used: the indices depend on one another, the loads do not.
-template <class Load>
-NAF_SIDDON_HD float siddon_line_integral(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, Load load) {
+// One ray as the walks take it; d is un-normalised.
+struct SiddonRay {
+    float o[3], d[3], near, far;
+};
+
+// What a forward walk keeps of a ray: add(f, len) is called once per step, padding included, in traversal order.  SiddonIntegral is
+// P6's sum.  SiddonIntegralAndRow (P8) keeps the ray's row sum beside it: the bits the plain sum has on a
+// volume of ones (1.0f * len == len), so 1 / row is the weight R of the fp32 matrix P7 defines and no A 1 is ever stored.
+struct SiddonIntegral {
+    float acc = 0.0f;
+    NAF_SIDDON_HD void add(float f, float len) { acc += f * len; }
+};
+struct SiddonIntegralAndRow {
+    float acc = 0.0f, row = 0.0f;
+    NAF_SIDDON_HD void add(float f, float len) {
+        acc += f * len;
+        row += len;
+    }
+};
+
+// The forward walk of one ray through the piecewise-constant volume `load` reads (load(offset) -> float, one call per step): into
+// `sum`, in traversal order, every step's value and length (s_next - s_prev) * |d|.  The loads of a group of steps are issued before
+// the first of them is used: the indices depend on one another, the loads do not.  Returns the span's kind; `sum` is left as it was
+// unless that is kSiddonOk, and what an empty or a non-finite span yields is the caller's to say.
+template <class Load, class Sum>
+NAF_SIDDON_HD SiddonKind siddon_forward(const SiddonGrid &g, const SiddonRay &ray, Load load, Sum &sum) {
     SiddonSpan r;
-    const SiddonKind kind = siddon_span(g, o, d, near, far, r);
-    if (kind == kSiddonEmpty) return 0.0f;
-    if (kind == kSiddonNotFinite) return __builtin_nanf("");
+    const SiddonKind kind = siddon_span(g, ray.o, ray.d, ray.near, ray.far, r);
+    if (kind != kSiddonOk) return kind;
     SiddonWalk w;
     const uint32_t steps = siddon_begin(g, r, w);
     // group n + 1 is stepped and its loads are issued before group n's values are used, so the loads of two groups are in flight
     // while the next indices are computed
-    float acc = 0.0f, len[kSiddonGroup], f[kSiddonGroup];
-    uint64_t offset[kSiddonGroup];
-    NAF_SIDDON_UNROLL
-    for (uint32_t j = 0; j < kSiddonGroup; ++j) {
-        float ds;
-        siddon_step(g, r, w, offset[j], ds);
-        len[j] = ds * r.dn;
-    }
-    NAF_SIDDON_UNROLL
-    for (uint32_t j = 0; j < kSiddonGroup; ++j) f[j] = load(offset[j]);
-    for (uint32_t k = kSiddonGroup; k < steps; k += kSiddonGroup) {
-        float len_next[kSiddonGroup], f_next[kSiddonGroup];
-        NAF_SIDDON_UNROLL
-        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
-            float ds;
-            siddon_step(g, r, w, offset[j], ds);
-            len_next[j] = ds * r.dn;
-        }
-        NAF_SIDDON_UNROLL
-        for (uint32_t j = 0; j < kSiddonGroup; ++j) f_next[j] = load(offset[j]);
-        NAF_SIDDON_UNROLL
-        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
-            acc += f[j] * len[j];
-            f[j] = f_next[j];
-            len[j] = len_next[j];
-        }
-    }
-    NAF_SIDDON_UNROLL
-    for (uint32_t j = 0; j < kSiddonGroup; ++j) acc += f[j] * len[j];
-    return acc;
-}
-
-// The transpose of that map for one ray (include/naf_hip.h P7): the same span, end-point indices, trip count,
-// crossings and tie order, and for every step of positive length one call add(offset, y * ((s_next - s_prev) * |d|)), the factor
-// in brackets being the very float siddon_line_integral multiplies the voxel by.  Steps of length 0 (ties, the padding of the last
-// group, the exit voxel's fixed point) send nothing whatever y is, and neither does y == 0, an empty span or a non-finite one.
-// A group is stepped first and sent after: nothing here waits for what `add` does.
-template <class Add>
-NAF_SIDDON_HD void siddon_scatter(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, float y, Add add) {
-    if (y == 0.0f) return;
-    SiddonSpan r;
-    if (siddon_span(g, o, d, near, far, r) != kSiddonOk) return;
-    SiddonWalk w;
-    const uint32_t steps = siddon_begin(g, r, w);
-    for (uint32_t k = 0; k < steps; k += kSiddonGroup) {
-        float len[kSiddonGroup];
-        uint64_t offset[kSiddonGroup];
-        NAF_SIDDON_UNROLL
-        for (uint32_t j = 0; j < kSiddonGroup; ++j) {
-            float ds;
-            siddon_step(g, r, w, offset[j], ds);
-            len[j] = ds * r.dn;
-        }
-        NAF_SIDDON_UNROLL
-        for (uint32_t j = 0; j < kSiddonGroup; ++j)
-            if (len[j] > 0.0f) add(offset[j], y * len[j]);
-    }
-}
-
-// The forward walk of the OS-SART subset step on this pair (include/naf_hip.h P8): siddon_line_integral with
-// the ray's row sum kept beside the integral.  The same span, the same grouped stepping with the loads of group n + 1 issued before
-// group n is used, the same order of additions; next to acc += f * len it keeps row += len.  acc has the bits
-// siddon_line_integral returns for the ray, and row those it returns on a volume of ones (1.0f * len == len), so 1 / row is the
-// weight R of the fp32 matrix P7 defines and no A 1 is ever stored.  Returns the span's kind; acc and row are 0 unless it is
-// kSiddonOk.
-template <class Load>
-NAF_SIDDON_HD SiddonKind siddon_line_integral_and_row(const SiddonGrid &g, const float o[3], const float d[3], float near, float far,
-                                                      Load load, float &acc, float &row) {
-    acc = 0.0f;
-    row = 0.0f;
-    SiddonSpan r;
-    const SiddonKind kind = siddon_span(g, o, d, near, far, r);
-    if (kind != kSiddonOk) return kind;
-    SiddonWalk w;
-    const uint32_t steps = siddon_begin(g, r, w);
     float len[kSiddonGroup], f[kSiddonGroup];
     uint64_t offset[kSiddonGroup];
     NAF_SIDDON_UNROLL
@@ -274,32 +219,26 @@ NAF_SIDDON_HD SiddonKind siddon_line_integral_and_row(const SiddonGrid &g, const
         for (uint32_t j = 0; j < kSiddonGroup; ++j) f_next[j] = load(offset[j]);
         NAF_SIDDON_UNROLL
         for (uint32_t j = 0; j < kSiddonGroup; ++j) {
-            acc += f[j] * len[j];
-            row += len[j];
+            sum.add(f[j], len[j]);
             f[j] = f_next[j];
             len[j] = len_next[j];
         }
     }
     NAF_SIDDON_UNROLL
-    for (uint32_t j = 0; j < kSiddonGroup; ++j) {
-        acc += f[j] * len[j];
-        row += len[j];
-    }
-    return kind;
+    for (uint32_t j = 0; j < kSiddonGroup; ++j) sum.add(f[j], len[j]);
+    return kSiddonOk;                                      // the constant: a caller's tests of the kind then fold into the early return
 }
 
-// The paired scatter of the same step: siddon_scatter's span, end-point indices, trip count, crossings and tie order, with two
-// outputs.  Every step of positive length sends its length through den(offset, len) when `want_den`, and fl(y * len) through
-// num(offset, term) when y != 0.  A step of length 0 sends nothing to either, and neither does an empty or non-finite span.  Unlike
-// siddon_scatter it does not return on y == 0 while a den is wanted: such a ray still owes its chord lengths to the column sums.
-// A group is stepped first and sent after.
-template <class Num, class Den>
-NAF_SIDDON_HD void siddon_scatter_pair(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, float y,
-                                       bool want_den, Num num, Den den) {
-    const bool want_num = y != 0.0f;                       // a NaN y is sent, as in siddon_scatter
-    if (!want_num && !want_den) return;
+// The transpose of that map for one ray (include/naf_hip.h P7 and P8, DESIGN.md sections 21 and 22): the same span, end-point
+// indices, trip count, crossings and tie order, and for every step of positive length one call deposit(offset, len), len being the
+// very float the forward walk hands to `sum` beside the voxel.  Steps of length 0 (ties, the padding of the last group, the exit
+// voxel's fixed point) send nothing, and neither does an empty span, a non-finite one, or a deposit that says up front
+// (deposit.wanted()) that it has nothing to add.  A group is stepped first and sent after: nothing here waits for what `deposit` does.
+template <class Deposit>
+NAF_SIDDON_HD void siddon_transpose(const SiddonGrid &g, const SiddonRay &ray, const Deposit &deposit) {
+    if (!deposit.wanted()) return;
     SiddonSpan r;
-    if (siddon_span(g, o, d, near, far, r) != kSiddonOk) return;
+    if (siddon_span(g, ray.o, ray.d, ray.near, ray.far, r) != kSiddonOk) return;
     SiddonWalk w;
     const uint32_t steps = siddon_begin(g, r, w);
     for (uint32_t k = 0; k < steps; k += kSiddonGroup) {
@@ -313,10 +252,7 @@ NAF_SIDDON_HD void siddon_scatter_pair(const SiddonGrid &g, const float o[3], co
         }
         NAF_SIDDON_UNROLL
         for (uint32_t j = 0; j < kSiddonGroup; ++j)
-            if (len[j] > 0.0f) {
-                if (want_den) den(offset[j], len[j]);
-                if (want_num) num(offset[j], y * len[j]);
-            }
+            if (len[j] > 0.0f) deposit(offset[j], len[j]);
     }
 }
 

@@ -7,8 +7,7 @@
 //
 // Layout of both kernels: scan_launch.h's.  Launch view j is scan view view_index[j] (j itself without a list), whose pose, pixel
 // rays and measured values are read in place from the whole scan, so no subset is ever gathered.  No LDS, no scratch.
-#include "scan_launch.h"
-#include "siddon_device.h"
+#include "siddon_launch.h"
 
 namespace naf {
 
@@ -28,16 +27,15 @@ siddon_sart_residual_scan_kernel(SiddonGrid grid, const float *__restrict__ volu
         const float b = projections[(uint64_t)view * per_view + p.pixel];
         float4 ray[2];
         make_pixel_ray(poses + (size_t)view * 12, p.row, p.col, g, ray);
-        const float o[3] = {ray[0].x, ray[0].y, ray[0].z}, d[3] = {ray[0].w, ray[1].x, ray[1].y};
-        float acc, row;
-        const SiddonKind kind = siddon_line_integral_and_row(grid, o, d, ray[1].z, ray[1].w,
-                                                             [volume](uint64_t offset) { return volume[offset]; }, acc, row);
+        SiddonIntegralAndRow sum;
+        const SiddonKind kind =
+            siddon_forward(grid, siddon_ray(ray[0], ray[1]), [volume](uint64_t offset) { return volume[offset]; }, sum);
         if (kind == kSiddonEmpty) {
             res = b;
             weighted = 0.0f;
         } else if (kind == kSiddonOk) {
-            res = b - acc;                                    // b - (A x): P6's own sum
-            weighted = row > 0.0f ? res / row : 0.0f;         // R = 1 / (A 1), the row sum of the same walk
+            res = b - sum.acc;                                // b - (A x): P6's own sum
+            weighted = sum.row > 0.0f ? res / sum.row : 0.0f; // R = 1 / (A 1), the row sum of the same walk
         }
     }
     const uint64_t out = (uint64_t)p.j * per_view + p.pixel;
@@ -55,11 +53,7 @@ siddon_sart_backproject_scan_kernel(SiddonGrid grid, float *__restrict__ num, fl
     if (view >= list.n_scan_views) return;
     float4 ray[2];
     make_pixel_ray(poses + (size_t)view * 12, p.row, p.col, g, ray);
-    const float o[3] = {ray[0].x, ray[0].y, ray[0].z}, d[3] = {ray[0].w, ray[1].x, ray[1].y};
-    siddon_scatter_pair(
-        grid, o, d, ray[1].z, ray[1].w, y[(uint64_t)p.j * g.W * g.H + p.pixel], den != nullptr,
-        [num](uint64_t offset, float term) { atomicAdd(num + offset, term); },     // no-return global_atomic_add_f32
-        [den](uint64_t offset, float len) { atomicAdd(den + offset, len); });
+    siddon_transpose(grid, siddon_ray(ray[0], ray[1]), SiddonDepositPair{num, den, y[(uint64_t)p.j * g.W * g.H + p.pixel]});
 }
 
 }  // namespace
@@ -73,12 +67,11 @@ extern "C" int naf_sart_residual_scan_siddon(const float *volume, const uint32_t
                                              float DSD, float near, float far, int parallel, const uint32_t *view_index,
                                              uint32_t n_scan_views, const float *projections, float *y, float *r, void *stream) {
     if (n_sub == 0) return NAF_OK;
-    ScanLaunch s;                                               // there is no sample step here: any valid one passes the checks
-    const int rc = make_scan_launch("sart_residual_scan_siddon", volume, {projections, y}, dims, dvoxel, poses, n_sub, det_w, det_h, du,
-                                    dv, ou, ov, DSD, near, far, parallel, 1.0f, &s, kScanTiles, view_index, n_scan_views);
-    if (rc != NAF_OK) return rc;
+    ScanLaunch s;
     SiddonGrid grid;
-    siddon_grid(dims[0], dims[1], dims[2], dvoxel, &grid);
+    const int rc = make_siddon_scan_launch("sart_residual_scan_siddon", volume, {projections, y}, dims, dvoxel, poses, n_sub, det_w, det_h,
+                                           du, dv, ou, ov, DSD, near, far, parallel, &s, &grid, view_index, n_scan_views);
+    if (rc != NAF_OK) return rc;
     { ProfScope prof_("siddon_sart_residual_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(siddon_sart_residual_scan_kernel, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream, grid,
                          volume, poses, s.g, ViewList{view_index, n_scan_views}, projections, y, r, s.tiles_x, s.tiles_per_view); }
@@ -91,12 +84,11 @@ extern "C" int naf_sart_backproject_scan_siddon(const float *y, const uint32_t *
                                                 float far, int parallel, float *num, float *den, void *stream) {
     if (n_sub == 0) return NAF_OK;
     ScanLaunch s;
-    const int rc = make_scan_launch("sart_backproject_scan_siddon", num, {y}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou, ov,
-                                    DSD, near, far, parallel, 1.0f, &s, kScanTiles, view_index, n_scan_views);
+    SiddonGrid grid;
+    const int rc = make_siddon_scan_launch("sart_backproject_scan_siddon", num, {y}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou,
+                                           ov, DSD, near, far, parallel, &s, &grid, view_index, n_scan_views);
     if (rc != NAF_OK) return rc;
     if (den == num) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_backproject_scan_siddon: num and den must be two volumes");
-    SiddonGrid grid;
-    siddon_grid(dims[0], dims[1], dims[2], dvoxel, &grid);
     { ProfScope prof_("siddon_sart_backproject_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(siddon_sart_backproject_scan_kernel, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream, grid,
                          num, den, y, poses, s.g, ViewList{view_index, n_scan_views}, s.tiles_x, s.tiles_per_view); }

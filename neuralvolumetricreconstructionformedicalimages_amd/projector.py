@@ -104,25 +104,23 @@ class Scan:
             _abi.ptr(projections[first:first + count]), *self._grid_and_poses(first), count, *self.detector_args(), _abi.ptr(out),
             _abi.stream_ptr()), "backproject_scan")
 
-    def residual(self, volume, views, m, projections, y, r):
-        _abi.check(_abi.lib().naf_sart_residual_scan(
-            _abi.ptr(volume), *self._grid_and_poses(), m, *self.detector_args(), _index_ptr(views), self.N, _abi.ptr(projections),
-            _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr()), "sart_residual_scan")
+    def residual(self, volume, views, m, projections, y, r, kind="interpolated"):
+        """y, r of the `m` views `views` (None: the first m) by the fused forward walk of that `kind`."""
+        args = (_abi.ptr(volume), *self._grid_and_poses(), m, *self.detector_args())
+        rest = (_index_ptr(views), self.N, _abi.ptr(projections), _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr())
+        if kind == "siddon":                                    # no sample step
+            _abi.check(_abi.lib().naf_sart_residual_scan_siddon(*args[:-1], *rest), "sart_residual_scan_siddon")
+        else:
+            _abi.check(_abi.lib().naf_sart_residual_scan(*args, *rest), "sart_residual_scan")
 
-    def backproject_views(self, y, views, m, num, den):
-        _abi.check(_abi.lib().naf_sart_backproject_scan(
-            _abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self.detector_args(), _abi.ptr(num), _abi.ptr(den),
-            _abi.stream_ptr()), "sart_backproject_scan")
-
-    def residual_siddon(self, volume, views, m, projections, y, r):
-        _abi.check(_abi.lib().naf_sart_residual_scan_siddon(                                   # no sample step
-            _abi.ptr(volume), *self._grid_and_poses(), m, *self.detector_args()[:-1], _index_ptr(views), self.N, _abi.ptr(projections),
-            _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr()), "sart_residual_scan_siddon")
-
-    def backproject_views_siddon(self, y, views, m, num, den):
-        _abi.check(_abi.lib().naf_sart_backproject_scan_siddon(                                # no sample step
-            _abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self.detector_args()[:-1], _abi.ptr(num),
-            _abi.ptr(den), _abi.stream_ptr()), "sart_backproject_scan_siddon")
+    def backproject_views(self, y, views, m, num, den, kind="interpolated"):
+        """num += A_s^T y and, where `den` is given, den += A_s^T 1 over the same views, by the paired scatter of that `kind`."""
+        args = (_abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self.detector_args())
+        rest = (_abi.ptr(num), _abi.ptr(den), _abi.stream_ptr())
+        if kind == "siddon":                                    # no sample step
+            _abi.check(_abi.lib().naf_sart_backproject_scan_siddon(*args[:-1], *rest), "sart_backproject_scan_siddon")
+        else:
+            _abi.check(_abi.lib().naf_sart_backproject_scan(*args, *rest), "sart_backproject_scan")
 
     def gather(self, values, views, m, num, den, workspace, first=0, n_scan_views=None):
         """The gather transpose of `m` launch views: a view list into the whole scan, or without one the views from `first` on."""

@@ -198,10 +198,10 @@ def _scan_operators(geo, angles, views_per_call, deterministic, device, kind="in
     return A, AT
 
 
-def _device_solve_setup(who, projections, geo, angles, x0, deterministic, workspace_views=None):
+def _device_solve_setup(who, projections, geo, angles, x0, deterministic, workspace_views=None, kind="interpolated"):
     """What the solvers that run on the subset kernels start from -> (scan, x, transpose): the `Scan`, the start volume (zeros, or
-    a copy of `x0`) and the keyword arguments of `sart.backproject_scan`, with a span table for calls of up to `workspace_views`
-    views (default: all) if `deterministic`."""
+    a copy of `x0`) and the keyword arguments of `sart.backproject_scan` on the pair of `kind`, with a span table for calls of up to
+    `workspace_views` views (default: all) if `deterministic`."""
     import torch
 
     from . import _abi, projector
@@ -214,7 +214,7 @@ def _device_solve_setup(who, projections, geo, angles, x0, deterministic, worksp
         _abi.check_volume(x0, who, "x0")
         projector.check_geometry(x0, geo)
         x = x0.clone()
-    transpose = {"method": _method(deterministic), "scan": scan}
+    transpose = {"method": _method(deterministic), "scan": scan, "kind": kind}
     if deterministic:
         transpose["workspace"] = projector.gather_workspace(workspace_views or scan.N, scan.H, scan.W, projections.device)
     return scan, x, transpose
@@ -325,8 +325,7 @@ def os_sart(projections, geo, angles, n_iter=20, n_subsets=None, order="angular-
     angles = np.asarray(angles, dtype=np.float64).reshape(-1)
     subsets = subset_order(angles, len(angles) if n_subsets is None else n_subsets, order, seed)
     most = max(len(s) for s in subsets)
-    scan, x, transpose = _device_solve_setup("os_sart", projections, geo, angles, x0, deterministic, most)
-    transpose["kind"] = kind
+    scan, x, transpose = _device_solve_setup("os_sart", projections, geo, angles, x0, deterministic, most, kind)
     lists = [sart.ViewList(s, scan.N, projections.device) for s in subsets]
     y = torch.empty(most, scan.H, scan.W, device=x.device, dtype=torch.float32)
     r = torch.empty_like(y)
@@ -479,8 +478,7 @@ def fista_tv(projections, geo, angles, n_iter=30, lam=DEFAULT_FISTA_TV_LAMBDA, t
     tv_iters = int(tv_iters)
     if tv_iters < 0:
         raise ValueError(f"fista_tv: tv_iters must be >= 0, got {tv_iters}")
-    scan, x, transpose = _device_solve_setup("fista_tv", projections, geo, angles, x0, deterministic)
-    transpose["kind"] = kind
+    scan, x, transpose = _device_solve_setup("fista_tv", projections, geo, angles, x0, deterministic, kind=kind)
     yw = torch.empty(scan.N, scan.H, scan.W, device=x.device, dtype=torch.float32)
     res = torch.empty_like(yw)
     num = torch.zeros_like(x)

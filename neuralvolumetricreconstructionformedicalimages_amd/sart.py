@@ -54,7 +54,7 @@ def residual_scan(volume, projections, geo, angles, views=None, y=None, r=None, 
     else:
         _abi.check_stack(r, shape, volume, who, "r")
     if m:
-        (scan.residual_siddon if kind == "siddon" else scan.residual)(volume, views, m, projections, y, r)
+        scan.residual(volume, views, m, projections, y, r, kind)
     return y, r
 
 
@@ -92,7 +92,7 @@ def backproject_scan(y, geo, angles, views=None, num=None, den=None, scan=None, 
                              "(projector.gather_workspace), None or False")
         scan.gather(y, views, m, num, den, workspace)
     elif m:
-        (scan.backproject_views_siddon if kind == "siddon" else scan.backproject_views)(y, views, m, num, den)
+        scan.backproject_views(y, views, m, num, den, kind)
     return num
 
 

@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
-"""Host check of the Siddon traversal: compiles tools/siddon_host_check.cpp (the per-ray walk of csrc/siddon_device.h over a heap
-volume of exactly n1 n2 n3 floats; the kernels' own ray generation and tiling in csrc/siddon.hip are not part of it) for the CPU
-with AddressSanitizer and UBSan, walks the GPU tests' ray sets, NaN / Inf rays and hot-voxel volumes (tests/_siddon_oracle.py) and
-asserts every result within the float64 oracle's per-ray bound.  The program is never loaded into Python.  No GPU.
+"""Host check of the Siddon pair's two walks: compiles tools/siddon_host_check.cpp (siddon_forward and siddon_transpose of
+csrc/siddon_device.h over heap volumes of exactly n1 n2 n3 floats; the device deposits, the kernels' ray generation and their
+tiling are not part of it) for the CPU with AddressSanitizer and UBSan and runs it as a process of its own on the GPU tests' ray
+sets, the NaN / Inf rays and the hot-voxel volumes (tests/_siddon_oracle.py, tests/_siddon_transpose_oracle.py) with mixed-sign,
+zero, NaN and Inf values.  It asserts that
+  - the sanitizers report nothing,
+  - inside the program, bit for bit against its ungrouped restatement of the walk: the kind, acc and row of the forward walk, with
+    and without the row sum, and the steps each deposit of the transpose walk is called with (none for a deposit that declines),
+  - the forward results are within the float64 oracle's per-ray bound, NaN where the definition says NaN and 0 on an empty span,
+  - the numbers of sent terms are the oracle's, and the value deposit's volume, num and den stay inside the per-voxel bound
+    against float64.
+The program is never loaded into Python.  No GPU.
 
     python tools/siddon_host_check.py
 """
@@ -18,52 +26,101 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+FLAGS = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall"]
+
+
+def compiler():
+    return shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+
 
 def build(workdir):
-    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+    cxx = compiler()
     if cxx is None:
         raise RuntimeError("no host C++ compiler found")
     exe = os.path.join(workdir, "siddon_host_check")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-Wall", os.path.join(REPO, "tools", "siddon_host_check.cpp"), "-o", exe])
+    subprocess.check_call([cxx, *FLAGS, os.path.join(REPO, "tools", "siddon_host_check.cpp"), "-o", exe])
     return exe
 
 
-def walk(exe, workdir, volume, dvoxel, rays):
-    """The program's float32 result for `rays` [n, 8]; any sanitizer report is an error."""
-    vol_path, ray_path, out_path = (os.path.join(workdir, name) for name in ("volume.f32", "rays.f32", "out.f32"))
-    np.ascontiguousarray(volume, dtype=np.float32).tofile(vol_path)
-    np.ascontiguousarray(rays, dtype=np.float32).tofile(ray_path)
-    done = subprocess.run([exe, *[str(n) for n in volume.shape], *[repr(float(np.float32(v))) for v in dvoxel], str(len(rays)),
-                           vol_path, ray_path, out_path], capture_output=True, text=True)
+def walk(exe, workdir, volume, dvoxel, rays, y=None, start=None):
+    """Both walks over `rays` [n, 8]: the forward on `volume`, the value deposit of `y` (default zeros) into `start` (default zeros),
+    the pair deposit into zeroed num and den -> dict of acc [n], value, num, den (flat volumes) and the counts of terms sent to
+    each.  A sanitizer report or a mismatch inside the program is an error."""
+    names = ("volume", "start", "rays", "values", "acc", "value_out", "num_out", "den_out")
+    paths = [os.path.join(workdir, name + ".f32") for name in names]
+    y = np.zeros(len(rays)) if y is None else y
+    start = np.zeros(volume.shape) if start is None else start
+    for path, a in zip(paths, (volume, start, rays, y)):
+        np.ascontiguousarray(a, dtype=np.float32).tofile(path)
+    done = subprocess.run([exe, *[str(n) for n in volume.shape], *[repr(float(np.float32(v))) for v in dvoxel], str(len(rays)), *paths],
+                          capture_output=True, text=True)
     if done.returncode != 0 or done.stderr.strip():
-        raise RuntimeError(f"exit {done.returncode}; sanitizer output:\n{done.stderr}")
-    return np.fromfile(out_path, dtype=np.float32, count=len(rays))
+        raise RuntimeError(f"exit {done.returncode}: {done.stdout}\nsanitizer output:\n{done.stderr}")
+    words = done.stdout.split()
+    assert words[0::2] == ["value", "num", "den", "mismatches"] and int(words[7]) == 0, done.stdout
+    out = {name: np.fromfile(path, dtype=np.float32) for name, path in zip(("acc", "value", "num", "den"), paths[4:])}
+    out.update(n_value=int(words[1]), n_num=int(words[3]), n_den=int(words[5]))
+    return out
+
+
+def value_vectors(T, n):
+    """The three value vectors: mixed signs, every seventh 0, and NaN / 0 / Inf."""
+    plain = T.values(n)
+    planted = plain.copy()
+    planted[::7] = 0.0
+    special = plain.copy()
+    special[0::4], special[1::4], special[2::4] = np.nan, 0.0, np.inf
+    return (("mixed signs", plain), ("every seventh 0", planted), ("NaN / 0 / Inf", special))
+
+
+def check_forward(S, exe, workdir, volume, dvoxel, rays):
+    """Largest |acc - float64| / bound over the rays, NaN and 0 exactly where the definition has them."""
+    want, bound = S.project_rays(volume, dvoxel, rays)
+    got = walk(exe, workdir, volume, dvoxel, rays)["acc"]
+    assert np.array_equal(np.isnan(got), np.isnan(want)), (got, want)
+    return float(S.use(got, want, bound).max())
+
+
+def check_set(S, T, exe, workdir, name, dims, dvoxel, volume, rays):
+    """One ray set of the transpose oracle through both walks with the three value vectors -> the largest ratio to a bound."""
+    t = T.walk_triples(dims, dvoxel, rays)
+    v0, zero = T.start_volume(dims), np.zeros(dims)
+    want_acc, bound_acc = S.project_rays(volume, dvoxel, rays)
+    want_den, bound_den, m_den = T.want_and_bound(t, np.ones(len(rays)), zero)
+    worst = 0.0
+    for label, y in value_vectors(T, len(rays)):
+        want_value, bound_value, m = T.want_and_bound(t, y, v0)
+        want_num, bound_num, _ = T.want_and_bound(t, y, zero)
+        got = walk(exe, workdir, volume, dvoxel, rays, y, v0)
+        assert np.array_equal(np.isnan(got["acc"]), np.isnan(want_acc)), name
+        ratio = max(float(S.use(got["acc"], want_acc, bound_acc).max()), float(T.use(got["value"], want_value, bound_value).max()),
+                    float(T.use(got["num"], want_num, bound_num).max()), float(T.use(got["den"], want_den, bound_den).max()))
+        worst = max(worst, ratio)
+        print(f"{name}, y {label}: {len(rays)} rays, {got['n_value']} terms to the volume and {got['n_num']} to num, {got['n_den']} to "
+              f"den, every walk its restatement's; largest |. - float64| / bound {ratio:.3f}", flush=True)
+        assert got["n_value"] == got["n_num"] == int(m.sum()) and got["n_den"] == int(m_den.sum()), (name, got, int(m.sum()))
+        assert ratio <= 1.0, name
+    return worst
 
 
 def main():
     import _siddon_oracle as S
+    import _siddon_transpose_oracle as T
     with tempfile.TemporaryDirectory() as workdir:
         exe = build(workdir)
         worst = 0.0
-        for name, (dims, dvoxel, volume, rays) in S.ray_sets().items():
-            want, bound = S.project_rays(volume, dvoxel, rays)
-            ratio = S.use(walk(exe, workdir, volume, dvoxel, rays), want, bound).max()
-            worst = max(worst, ratio)
-            print(f"{name}: {len(rays)} rays, largest |. - float64| / bound {ratio:.3f}", flush=True)
-            assert ratio <= 1.0, name
+        for name, (dims, dvoxel, volume, rays) in T.ray_sets().items():     # _siddon_oracle.ray_sets() and the non-finite rays
+            worst = max(worst, check_set(S, T, exe, workdir, name, dims, dvoxel, volume, rays))
         dims, dvoxel, volume, rays = S.ray_sets()["c random"]
         for ijk in S.hot_voxels(dims):
-            hot = S.hot_volume(dims, ijk)
-            want, bound = S.project_rays(hot, dvoxel, rays)
-            ratio = S.use(walk(exe, workdir, hot, dvoxel, rays), want, bound).max()
+            ratio = check_forward(S, exe, workdir, S.hot_volume(dims, ijk), dvoxel, rays)
             worst = max(worst, ratio)
             assert ratio <= 1.0, ijk
         bad = S.non_finite_rays(rays)
-        want, bound = S.project_rays(volume, dvoxel, bad)
-        got = walk(exe, workdir, volume, dvoxel, bad)
+        want, _ = S.project_rays(volume, dvoxel, bad)
+        got = walk(exe, workdir, volume, dvoxel, bad)["acc"]
         assert np.array_equal(np.isnan(got), np.isnan(want)) and np.all(got[~np.isnan(want)] == 0), (got, want)
-        print(f"no sanitizer report; largest |. - float64| / bound over everything: {worst:.3f}")
+        print(f"no sanitizer report, no mismatch; largest |. - float64| / bound over everything: {worst:.3f}")
 
 
 if __name__ == "__main__":
