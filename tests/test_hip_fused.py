@@ -284,33 +284,18 @@ def test_bf16_mode_backward_matches_a_bf16_rounding_emulation(S):
     rays = _rays(n, seed=47)
     t_rand = torch.rand(n, S, generator=torch.Generator().manual_seed(5))
     target = torch.rand(n, generator=torch.Generator().manual_seed(6)) * 0.3
-    r = lambda t: t.bfloat16().float()                                                  # noqa: E731
-    leaky = torch.nn.functional.leaky_relu
+    # the roundings themselves live in tests/_mlp16_oracle.py (shared with the float64 reference of test_hip_mlp16_reference.py); here
+    # in fp32, on the upstream gradient of a mean squared error: weight 1 / n
+    import _mlp16_oracle as O
     with torch.no_grad():
         z = R.sample_depths(rays[:, 6:7], rays[:, 7:8], S, True, t_rand)
         pts = R.points_on_rays(rays, z, 0.3).reshape(-1, 3)
         dn = rays[:, 3:6].norm(dim=-1, keepdim=True)
         dist = torch.cat([z[:, 1:] - z[:, :-1], torch.full((n, 1), 1e-10)], -1) * dn
-        x = r(ref.encoder(pts, 0.3))
-        W = [r(l.weight) for l in ref.layers[:3]]
-        b = [l.bias for l in ref.layers]
-        w3 = ref.layers[3].weight                                                       # [1, 32] fp32
-        h1 = leaky(x @ W[0].T + b[0], 0.01)
-        h2 = leaky(r(h1) @ W[1].T + b[1], 0.01)
-        h3 = leaky(torch.cat([x, r(h2)], -1) @ W[2].T + b[2], 0.01)
-        sig = torch.sigmoid(h3 @ w3.T + b[3]).reshape(n, S)
-        acc_want = (sig * dist).sum(-1)
-        dacc = 2.0 * (acc_want - target) / n
-        g4 = ((dacc[:, None] * dist) * (sig * (1 - sig))).reshape(-1, 1)
-        mask = lambda h: torch.where(h > 0, torch.ones_like(h), torch.full_like(h, 0.01))     # noqa: E731
-        dw3 = (g4 * h3).sum(0, keepdim=True)
-        G3 = (w3 * g4) * mask(h3)
-        dW2 = r(G3).T @ torch.cat([x, r(h2)], -1)
-        G2 = (r(G3) @ W[2][:, 32:]) * mask(h2)
-        dW1 = r(G2).T @ r(h1)
-        G1 = (r(G2) @ W[1]) * mask(h1)
-        dW0 = r(G1).T @ x
-        dx = r(G3) @ W[2][:, :32] + r(G1) @ W[0]
+        emu = O.rehearse(ref.encoder(pts, 0.3).reshape(n, S, 32), dist, target, torch.full((n,), 1.0 / n), ref.layers, dtype=torch.float32)
+    acc_want, dx = emu["acc"], emu["dx"]
+    dW0, dW1, dW2, dw3 = emu["blocks"][0], emu["blocks"][2], emu["blocks"][4], emu["blocks"][6]
+    r = lambda t: t.bfloat16().float()                                                  # noqa: E731
     with fused.scatter_mode(1):          # the mode travels in the cfg captured by the forward call
         acc = fused.fused_render(rays.cuda(), net, S, True, t_rand=t_rand.cuda(), mlp_precision=_abi.BF16)
         ((acc - target.cuda()) ** 2).mean().backward()
