@@ -1,5 +1,5 @@
 // encode_kernel.h -- the hash-grid encoder kernel of the training / evaluation path (hashencoder.cu:77-198) and its launch rules.
-// Shared by render_fused.hip (points generated from rays, grids, point lists) and hash_encode.hip (the drop-in operator
+// Shared by render_fused.hip (through render_step.h: points generated from rays, grids, point lists) and hash_encode.hip (the drop-in operator
 // naf_hash_encode_forward: caller-supplied coordinates in [0, 1], hashencoder.h:13), so that a reference maintainer who binds
 // the operator gets the window gathers, the multi-point loop and the XCD groups of the fused path.
 #pragma once

@@ -15,10 +15,14 @@
 // all-ones where the level needs none, and the reference's `index % hashmap_size` (hashencoder.cu:74) stays behind a compare
 // that is never taken for in-range points.  Rows, weights (product order of hashencoder.cu:122-133), the fp32 fma chain and the
 // single rounding to bf16 are those of encode_kernel, so the results are bit-identical to the two-kernel path.
+// Holds the gather helpers and fused_forward_kernel itself; included from render_fused.hip only (through render_step.h).
 #pragma once
+
+#include <type_traits>
 
 #include "field_mlp16.h"
 #include "hash_kernels.h"
+#include "mlp_tile_io.h"
 
 namespace naf {
 
@@ -128,5 +132,71 @@ __device__ __forceinline__ void store_point_features(uint16_t *__restrict__ feat
 }
 
 constexpr uint32_t kFusedLevels = 16;
+
+// ---- 2c: gathers + MLP + line integral in one kernel, features in registers (fused_forward.h; forward-only calls) -----------
+// Src = SrcRays: one wave per ray (out[r] = sum_s sigma * dist, optional per-sample outputs).  Any other source: a plain point
+// list / generated grid, out[omap.at(p)] = sigma(p).  `feat` != nullptr additionally stores the features (diagnostic:
+// NAF_CFG_FUSED_STORE_FEATURES times what the feature traffic itself costs this kernel).
+template <typename TT, typename Src>
+__global__ void __launch_bounds__(256, 3)
+fused_forward_kernel(Src src, const typename TT::store_t *__restrict__ table, const int32_t *__restrict__ offsets,
+                     const float *__restrict__ mlp, float *__restrict__ out, float *__restrict__ sigma_out,
+                     float *__restrict__ depth_out, uint16_t *__restrict__ feat, uint32_t n_items, uint32_t B, uint32_t H, int act,
+                     OutMap omap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr uint32_t kShAligned = (Mlp16Shared::kBytes + 15u) & ~15u;
+    LevelRec *recs = reinterpret_cast<LevelRec *>(smem + kShAligned);
+    build_level_recs(recs, offsets, kFusedLevels, H);
+    Mlp16Shared::build<4>(smem, mlp);                          // ends with a workgroup barrier: the level records are visible too
+    const uint32_t lane = threadIdx.x & 63u, c = lane & 15u, g = lane >> 4;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6), n_waves = (gridDim.x * blockDim.x) >> 6;
+    const uint32_t table_rows = (uint32_t)offsets[kFusedLevels];
+    Act16 a;
+    if constexpr (std::is_same<Src, SrcRays>::value) {
+        const uint32_t S = src.S, tiles = (S + 15u) / 16u;
+        const bool use_zbuf = S <= kMaxSamplesLds;
+        float *zbuf = reinterpret_cast<float *>(smem + kShAligned + kFusedLevels * (uint32_t)sizeof(LevelRec)) + (threadIdx.x >> 6) * kMaxSamplesLds;
+        for (uint32_t r = wave; r < n_items; r += n_waves) {
+            const float4 *ray = reinterpret_cast<const float4 *>(src.rays + (size_t)r * 8);
+            const float4 ra = ray[0], rc = ray[1];
+            const float near = rc.z, far = rc.w;
+            const float dnorm = sqrtf(ra.w * ra.w + rc.x * rc.x + rc.y * rc.y);
+            if (use_zbuf) fill_depths(src, r, near, far, zbuf, lane);
+            float part = 0.0f, carry = 0.0f;
+            for (uint32_t k = 0; k < tiles; ++k) {
+                const uint32_t s = 16u * k + c;
+                const bool valid = s < S;
+                const uint32_t sc = valid ? s : S - 1u;
+                float x[3];
+                src.position(ra, rc, use_zbuf ? zbuf[sc] : src.depth(r, sc, near, far), x);
+                const Feat16Raw f = gather_point_features<TT>(recs, g, x, table, table_rows);
+                if (feat != nullptr && valid) store_point_features(feat, B, r * S + s, g, f);
+                const float z4 = mlp16_tile_forward(smem, lane, feat16_operand(f), a);
+                const float sigma = last_act16(act, z4);
+                const float term = !valid ? 0.0f
+                                 : sigma * (use_zbuf ? buffered_dist(zbuf, s, S, dnorm) : sample_dist(src, r, s, near, far, dnorm));
+                if (sigma_out != nullptr || depth_out != nullptr)          // per-sample outputs (wave-uniform test)
+                    carry = emit_samples<16>(term, sigma, carry, valid && g == 0u, c, sigma_out, depth_out, (size_t)r * S + s);
+                if (g == 0u) part += term;
+            }
+#pragma unroll
+            for (int off = 8; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);     // the 16 points of lane group 0
+            if (lane == 0) out[r] = part;
+        }
+    } else {
+        const uint32_t tiles = (n_items + 15u) / 16u;
+        for (uint32_t k = wave; k < tiles; k += n_waves) {
+            const uint32_t p0 = 16u * k + c;
+            const bool valid = p0 < n_items;
+            const uint32_t p = valid ? p0 : n_items - 1u;
+            float x[3];
+            src.get(p, x);
+            const Feat16Raw f = gather_point_features<TT>(recs, g, x, table, table_rows);
+            if (feat != nullptr && valid) store_point_features(feat, B, p, g, f);
+            const float z4 = mlp16_tile_forward(smem, lane, feat16_operand(f), a);
+            if (valid && g == 0u) out[omap.at(p)] = last_act16(act, z4);
+        }
+    }
+}
 
 }  // namespace naf

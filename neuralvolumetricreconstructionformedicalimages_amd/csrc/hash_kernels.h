@@ -1,6 +1,6 @@
 // hash_kernels.h -- templated gfx950 kernels of the multi-resolution hash-grid encoder.
 //
-// Shared by hash_encode.hip (stand-alone operator, reference ABI) and render_fused.hip (points generated on the
+// Shared by hash_encode.hip (stand-alone operator, reference ABI) and render_fused.hip (its headers mlp_tile_io.h .. render_step.h: points generated on the
 // fly from rays).  Follows reference src/encoder/hashencoder/src/hashencoder.cu:
 //   forward  kernel_grid           :77-198      backward  kernel_grid_backward :201-272
 //

@@ -1,6 +1,6 @@
 // render_ops.hip -- stand-alone ray-march operators for gfx950: stratified sampling, the attenuation line
 // integral and its backward, the encoder range check.  They back the drop-in `render()` surface
-// (reference src/render/render.py:82-212); the fused training path lives in render_fused.hip.
+// (reference src/render/render.py:82-212); the fused training path is compiled in render_fused.hip (entry points; kernels and drivers in the headers it lists).
 #include <cmath>
 #include <cstring>
 

@@ -1,5 +1,5 @@
 // scatter_host.h -- host side of the binned gradient scatter: the launch plan (tile shape, buckets, record blocks), the workspace
-// layout and the launch driver, shared by the training path (render_fused.hip) and the drop-in operator with a workspace
+// layout and the launch driver, shared by the training path (render_step.h, compiled in render_fused.hip) and the drop-in operator with a workspace
 // (hash_encode.hip: naf_hash_encode_backward_ws).
 #pragma once
 
@@ -74,7 +74,7 @@ static inline bool make_bin_plan(const naf_render_cfg *cfg, uint64_t n_points, B
 // pass holds fewer than four levels' worth of buckets.
 static inline uint32_t reducer_split(uint32_t NB, uint32_t nl) { return NB * nl >= 256u ? 1u : std::max(1u, std::min(16u, 1024u / (NB * nl))); }
 
-// The binned scatter's part of a workspace (the training step's: render_fused.hip carve(); the drop-in's: hash_encode.hip), carved
+// The binned scatter's part of a workspace (the training step's: render_step.h carve(); the drop-in's: hash_encode.hip), carved
 // from `base` for `plan`.
 struct BinRegions {
     unsigned char *regions;      // record blocks [level slot][tile][slots], bucket-sorted per tile
@@ -182,10 +182,10 @@ static int launch_binned_scatter(F &fam, const naf_render_cfg *cfg, const BinPla
 }
 
 // ---- record families ---------------------------------------------------------------------------------------------------------
-// (scatter_v2.h's, FxRecords, is declared in render_fused.hip: a class that is no template instantiates its kernels in every
+// (scatter_v2.h's, FxRecords, is declared in render_step.h, which render_fused.hip alone includes: a class that is no template instantiates its kernels in every
 // translation unit that declares it.)
 // scatter_binned.h: pair records of fp32 values, or of bf16 ones packed in pairs, from gradients whose (level l, point b) values sit
-// at grad + (l * sl + b * sb) * C.  The training path (render_fused.hip: fp32 parity mode, shapes with C != 2,
+// at grad + (l * sl + b * sb) * C.  The training path (render_step.h: fp32 parity mode, shapes with C != 2,
 // NAF_CFG_SCATTER_PAIR12) and the drop-in operator (hash_encode.hip: four levels per bin workgroup at every batch size, no Adam
 // tail -- so that it instantiates no reducer with one).
 template <typename FT, uint32_t C, typename Src, typename R, uint32_t kLvMany_, bool kAdamTail>

@@ -1,6 +1,6 @@
 """Float64 rehearsal of one bf16 training step of the canonical NAF network, with its cases, probes and tolerances (not a test module).
 
-The bf16 MLP kernels of csrc/render_fused.hip (mlp16_forward_split_kernel, mlp16_backward_kernel, mlp16_train_kernel<4> / <12>, the
+The bf16 MLP kernels of csrc/mlp16_kernels.h (mlp16_forward_split_kernel, mlp16_backward_kernel, mlp16_train_kernel<4> / <12>, the
 slab fold mlp16_fold_slab and slab_reduce_block of mlp_slabs.h) are "fp32 with bf16 MFMA operands": features, W0..W2, the hidden
 activations and the gradient tiles G3, G2, G1 are rounded to bf16 (round to nearest even) where they enter an MFMA; the accumulation,
 the output layer, the masks and the biases are not rounded.  rehearse() makes exactly those roundings and is exact elsewhere (float64),
@@ -8,7 +8,8 @@ so the kernels differ from it by fp32 summation order and by the rare operand th
 boundary -- and by nothing else.  tests/test_mlp16_oracle_cpu.py validates the rehearsal and the tolerances without a GPU,
 tests/test_hip_mlp16_reference.py holds the kernels to them, tests/test_hip_fused.py runs its fp32 form (the emulation it always had).
 
-WORK ITEMS.  backward16_parts / mlp_train_waves / tile_ranges restate the host logic of render_fused.hip: a ray is cut into `parts`
+WORK ITEMS.  backward16_parts / mlp_train_waves / n_slabs restate the launch plan of csrc/mlp_step_plan.h (tests/test_step_plan_cpu.py
+holds them to it), tile_ranges the kernels' first_tile: a ray is cut into `parts`
 ranges of 16-point tiles, item = ray * parts + part, four consecutive items (of one workgroup) fold into a slab, 768 workgroups of four
 waves at most.  They serve only to PLACE probes and faults; the reference sums over points and knows nothing of items.
 
@@ -58,7 +59,7 @@ def identity(t):
     return t
 
 
-# ---- host logic of render_fused.hip, restated ----------------------------------------------------------------------------------------
+# ---- launch plan of mlp_step_plan.h, restated -----------------------------------------------------------------------------------------
 def n_tiles(S):
     return (S + 15) // 16
 

@@ -1,5 +1,5 @@
 // isa_scatter.hip -- compile-only harness: instantiates the shipped shapes of the two scatter kernels so that their ISA and
-// resource usage can be inspected in seconds instead of recompiling render_fused.hip (2.5 min).
+// resource usage can be inspected in seconds instead of recompiling render_fused.hip (2.5 min; the only unit that compiles the step's kernels: see its header).
 //   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -I include -I <pkg>/csrc -c tools/isa_scatter.hip \
 //         -save-temps=obj -Rpass-analysis=kernel-resource-usage -o /tmp/isa/s.o
 #include "hash_kernels.h"

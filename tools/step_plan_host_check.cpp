@@ -1,0 +1,35 @@
+// step_plan_host_check.cpp -- prints the launch plan of the step's MLP kernels (csrc/mlp_step_plan.h: the very functions the host
+// drivers of csrc/render_step.h call) for the cases of a file, so that a CPU test can hold the plan to its restatement in
+// tests/_mlp16_oracle.py and to the invariants the kernel comments rely on (tools/step_plan_host_check.py builds it for the host with
+// AddressSanitizer / UBSan and runs it as a process of its own; tests/test_step_plan_cpu.py asserts).  No GPU, no HIP.
+//
+//   step_plan_host_check cases.txt        one "flags n_rays n_samples" per line (flags: naf_render_cfg::flags)
+// prints "caps <forward> <forward split> <backward> <backward16> <train max rays> <max samples lds>", then per case, in order,
+//   parts  train_waves  splits  split_grid  forward_grid16  forward_grid32  slabs16  slabs32  train_grid
+// for the canonical bf16 shape (C = 2) where that matters; train_grid is 0 where train_waves is.
+#include <cstdint>
+#include <cstdio>
+
+#include "../neuralvolumetricreconstructionformedicalimages_amd/csrc/mlp_step_plan.h"
+
+int main(int argc, char **argv) {
+    if (argc != 2) {
+        std::fprintf(stderr, "usage: step_plan_host_check cases.txt\n");
+        return 2;
+    }
+    FILE *fp = std::fopen(argv[1], "r");
+    if (!fp) return 2;
+    std::printf("caps %u %u %u %u %u %u\n", naf::kForwardBlocks, naf::kForwardSplitBlocks, naf::kBackwardBlocks, naf::kBackwardBlocks16,
+                naf::kMlpTrainMaxRays, naf::kMaxSamplesLds);
+    const bool bf16_c2 = true, per_sample_outputs = false;      // the canonical shape, line integrals only
+    unsigned flags, n_rays, S;
+    while (std::fscanf(fp, "%u %u %u", &flags, &n_rays, &S) == 3) {
+        const uint32_t parts = naf::backward16_parts(S, n_rays, flags);
+        const uint32_t waves = naf::mlp_train_waves(bf16_c2, S, n_rays, flags);
+        std::printf("%u %u %d %u %u %u %u %u %u\n", parts, waves, (int)naf::forward16_splits(n_rays, S, per_sample_outputs, flags),
+                    naf::forward16_split_grid(n_rays), naf::forward_grid(n_rays, true, 16u), naf::forward_grid(n_rays, true, 32u),
+                    naf::backward16_slabs(n_rays, parts), naf::backward_slabs(n_rays), waves ? naf::mlp_train_grid(n_rays, parts, waves) : 0u);
+    }
+    std::fclose(fp);
+    return 0;
+}
