@@ -765,6 +765,38 @@ int naf_cgls_residual_step(float *r, const float *q, const float *w, float *y, u
 int naf_cgls_direction_step(float *x, float *p, const float *s, uint64_t n, uint32_t k, uint32_t n_iter_max, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* V4  trilinear samples of a volume at world points, and the fused draw-and-sample that feeds the field fit (pretrain.fit_volume:
+ * a neural field started from a reconstructed volume).  DESIGN.md section 24; the arithmetic is csrc/volume_sample_device.h.
+ *   volume  f32 [n1, n2, n3] C-contiguous, axis 0 = x, every extent in 1 .. NAF_VOLUME_SAMPLE_MAX_EXTENT; voxel centres on the
+ *           get_voxels grid (tigre.py:388-400), the box |p_a| <= h_a = fp32(n_a * dvoxel[a] / 2) centred at the origin, as in P1
+ *   dvoxel  HOST f32 [3] voxel size in metres (> 0, finite);  dims  HOST u32 [3] = n1, n2, n3
+ * Value at p: trilinear between voxel centres, clamp-to-edge EVERYWHERE (a point outside the box returns the value of the nearest
+ * point of the centre hull; P1 returns zero there because it never samples outside).  The cell is P1's and P2's:
+ *   u_a = (p_a + h_a) * fp32(1 / dvoxel_a) - 1/2, one add, one multiply, one subtract; clamped on the float to [0, n_a - 1];
+ *   i_a = min(floor(u_a), n_a - 2), w_a = u_a - i_a (exact); an axis of one voxel is constant: its w_a is 0, it has no upper corner.
+ * The eight corners are blended by seven interpolations fma(w, b, fma(-w, a, a)), axis 2 first, then axis 1, then axis 0.  A weight
+ * of 0 returns a's bits and a weight of 1 b's: a point whose three u_a are whole numbers returns that voxel's bits.  At the float32 voxel centres of
+ * get_voxels that is so whenever every step of u_a is exact (a voxel size that is a power of two, for one); for any other voxel size
+ * the centre's u_a carries the rounding of its three operations and the value that of DESIGN.md section 24's bound.
+ * The clamp is applied to the float before it becomes an index, so no load leaves the volume whatever the floats hold:
+ *   a coordinate of +-infinity, or a finite one far outside, returns the edge value like any outside point;
+ *   a NaN coordinate returns NaN (its index is 0, its weight NaN); the other points of the call are unaffected.
+ * No atomics and no reduction: the same inputs return the same bits.  All volume offsets are 64-bit.  Pointers are 4-byte aligned.
+ * naf_volume_sample_points: points f32 [n, 3] -> out f32 [n].  n == 0 returns NAF_OK without examining the pointers.
+ * naf_volume_draw_sample: draws n points and samples the volume there in one pass; points_out f32 [n, 3], targets_out f32 [n].
+ *   Point i of step `step` is uniform in the box [lo, hi] (HOST f32 [3] each, finite, lo <= hi, hi - lo finite):
+ *     bits  = three rounds of the 32-bit finaliser m (x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16), all uint32:
+ *             h = m(lo32(seed) ^ i * 0x9e3779b1);  h = m(h ^ hi32(seed) ^ step * 0x85ebca77 ^ 0x27d4eb2f);  bits = m(h ^ (axis + 1) * 0xc2b2ae3d)
+ *     r     = (bits >> 8) * 2^-24, in [0, 1)
+ *     p_a   = min(lo_a + r * (hi_a - lo_a), hi_a)     one subtract, one multiply, one add, one minimum: lo_a <= p_a <= hi_a
+ *   The draw keeps no state and reads no other generator: equal arguments give equal bits, and targets_out holds exactly what
+ *   naf_volume_sample_points returns for points_out.  n == 0 returns NAF_OK without examining the pointers. */
+#define NAF_VOLUME_SAMPLE_MAX_EXTENT 16777216u
+int naf_volume_sample_points(const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, const float *points,
+                             uint64_t n, float *out, void *stream);
+int naf_volume_draw_sample(const float *volume, const uint32_t *dims, const float *dvoxel, const float *lo, const float *hi,
+                           uint64_t seed, uint32_t step, uint32_t n, float *points_out, float *targets_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,10 @@ SIGNATURES = {
     "naf_cgls_wdot": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
     "naf_cgls_residual_step": (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
     "naf_cgls_direction_step": (_i32, [_vp, _vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
+    "naf_volume_sample_points": (_i32, [_vp, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _u64, _vp, _vp]),
+    "naf_volume_draw_sample": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),
+                                      ctypes.POINTER(ctypes.c_float * 3), ctypes.POINTER(ctypes.c_float * 3), _u64, _u32, _u32, _vp, _vp,
+                                      _vp]),
 }
 
 

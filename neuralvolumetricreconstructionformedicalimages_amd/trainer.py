@@ -8,6 +8,10 @@ Two back ends, selected by the optional `backend.engine` key of the YAML (defaul
   * "module": `optimizer.zero_grad(); loss = compute_loss(...); loss.backward(); optimizer.step()` exactly like
               trainer.py:134-142, autograd running through the HIP operators.
 Checkpoints keep the reference layout {"epoch", "network", "network_fine", "optimizer"} (trainer.py:118-126).
+
+Optional warm start (`train.init_volume`: "fdk" or a .npy of shape nVoxel; `train.init_steps`, `train.init_points`): a run that does
+not resume from a checkpoint first fits the network to that volume (pretrain.fit_volume).  Without the key
+nothing changes.
 """
 from __future__ import annotations
 
@@ -23,6 +27,7 @@ from .encoder import get_encoder
 from .engine import NAFEngine
 from .loss import chunk_mean_weights
 from .network import get_network
+from .pretrain import check_init_geometry, fit_volume, init_volume_config, init_volume_tensor
 from .utils import get_ptycho_mask
 
 try:                                                       # tensorboard is optional in this image
@@ -86,6 +91,11 @@ class Trainer:
         self.global_step = 0
         self.conf = cfg
         self.device = torch.device(device)
+        # the warm start is refused on more than one process HERE, from the environment alone: every rank raises the same error
+        # before the process group exists, so none is left waiting in a collective
+        self.init_volume = init_volume_config(cfg["train"], int(os.environ.get("WORLD_SIZE", "1")))
+        self.init_fit_steps = 0                            # Adam steps the warm start ran in this process (0: none, or resumed)
+        self.init_fit_losses = None
         # data parallel when launched one process per GPU (torchrun contract: RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*);
         # rays of a step are sharded over the ranks, the model is replicated
         self.rank, self.world, self.group = 0, 1, None
@@ -111,6 +121,13 @@ class Trainer:
         os.makedirs(self.evaldir, exist_ok=True)
 
         data = cfg["exp"]["datadir"]
+        if self.init_volume is not None:                   # what the geometry alone can refuse is refused before any device work
+            if not isinstance(data, dict):
+                import pickle
+                with open(data, "rb") as handle:
+                    data = pickle.load(handle)
+            from .geometry import ConeGeometry
+            check_init_geometry(self.init_volume, ConeGeometry(data))
         train_dset = Dataset(data, cfg["train"]["n_rays"], "train", device, shard=(self.rank, self.world),
                              seed=backend.get("seed"))
         self.train_dset = train_dset
@@ -169,9 +186,28 @@ class Trainer:
             self.global_step = self.epoch_start * len(self.train_dloader)
             # the pixel draws are keyed by (seed, item count): a resumed run continues the sequence instead of replaying epoch 0's
             self.train_dset.set_draw_position(self.global_step)
+        elif self.init_volume is not None:
+            self._fit_init_volume()
 
         self.writer = SummaryWriter(self.expdir) if (SummaryWriter is not None and self.rank == 0) else _NullWriter()
         self.writer.add_text("parameters", self.args2string(cfg), global_step=0)
+
+    def _fit_init_volume(self):
+        """The warm start: fit the coarse network to `train.init_volume` with an optimiser of its own (the training optimiser's
+        moments stay zero), refresh the engine's 16-bit shadow, and start the fine network, if any, from the same layers (the two
+        share the encoder)."""
+        init, dset = self.init_volume, self.train_dset
+        vol = init_volume_tensor(init, dset.geo, dset.projs, dset.angles, self.device)
+        self.init_fit_losses = fit_volume(self.net, vol, dset.geo, init["steps"], n_points=init["points"],
+                                          lr=self.conf["train"]["lrate"], seed=int((self.conf.get("backend") or {}).get("seed") or 0))
+        self.init_fit_steps = init["steps"]
+        if self.net_fine is not None:
+            self.net_fine.layers.load_state_dict(self.net.layers.state_dict())
+        if self.engine is not None:
+            self.engine.sync_from_module()
+        if init["steps"] > 0:
+            print(f"[Trainer] fitted the network to init_volume {init['source']!r}: {init['steps']} steps of {init['points']} points, "
+                  f"loss {float(self.init_fit_losses[0]):.3g} -> {float(self.init_fit_losses[-1]):.3g}")
 
     @property
     def voxels(self):

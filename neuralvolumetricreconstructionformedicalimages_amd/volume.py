@@ -6,6 +6,11 @@ The definition is written down in include/naf_hip.h (V1) and DESIGN.md section 1
 x = j (a - 1) / (b - 1), the taps floor(x) - 1 .. floor(x) + 2 carry the cubic B-spline weights, taps outside the volume are
 mirrored about the edge samples, and nothing is prefiltered (an axis that keeps its extent is still smoothed).  There is no CPU
 path, like the rest of the hot path.
+
+`sample_points` and `draw_sample` read a volume back at world points (`naf_volume_sample_points`, `naf_volume_draw_sample`;
+include/naf_hip.h V4): trilinear between the voxel centres of `get_voxels`, clamp-to-edge, with P1's cell
+convention.  `draw_sample` draws its points from a counter-based hash of (seed, step, index, axis) and samples them in the same
+pass: it is what `pretrain.fit_volume` runs every step.  The float64 restatement is tests/_volume_sample_oracle.py.
 """
 from __future__ import annotations
 
@@ -86,3 +91,78 @@ def prepare_volume(image, n_voxel, convert, rescale_slope, rescale_intercept, no
         lo_t = torch.tensor(lo, dtype=torch.float32, device=dev)
         vol.sub_(lo_t).div_(torch.tensor(hi, dtype=torch.float32, device=dev) - lo_t)
     return vol
+
+
+def _voxel_size(dvoxel, who):
+    d = [float(v) for v in np.asarray(dvoxel, dtype=np.float64).reshape(-1)]
+    if len(d) != 3 or not all(np.isfinite(v) and v > 0 for v in d):
+        raise ValueError(f"{who}: dvoxel must be three finite voxel sizes > 0, got {dvoxel}")
+    return (ctypes.c_float * 3)(*d)
+
+
+def _check_sampled_volume(vol, who):
+    if not isinstance(vol, torch.Tensor) or not vol.is_cuda:
+        raise RuntimeError(f"{who}: volume must be a CUDA/HIP tensor (no CPU path)")
+    if vol.dtype != torch.float32:                       # a ValueError like filter_rows' (check_volume's is a TypeError)
+        raise ValueError(f"{who}: volume must be float32, got {vol.dtype}")
+    _abi.check_volume(vol, who)
+    if min(vol.shape) < 1:
+        raise ValueError(f"{who}: every extent must be at least 1, got {tuple(vol.shape)}")
+
+
+def sample_points(vol, dvoxel, points):
+    """`naf_volume_sample_points`: the CUDA float32 volume [n1, n2, n3] with voxel size `dvoxel` (three lengths, metres) sampled
+    trilinearly at the CUDA float32 world points [n, 3] -> float32 [n].  Clamp-to-edge outside the hull of the voxel centres; a NaN
+    coordinate gives NaN for that point alone."""
+    who = "sample_points"
+    _check_sampled_volume(vol, who)
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.device != vol.device:
+        raise RuntimeError(f"{who}: points must be a CUDA/HIP tensor on the volume's device (no CPU path)")
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+        raise ValueError(f"{who}: points must be a contiguous float32 [n, 3] tensor, got {points.dtype} {tuple(points.shape)}")
+    d = _voxel_size(dvoxel, who)
+    n = int(points.shape[0])
+    out = torch.empty(n, dtype=torch.float32, device=vol.device)
+    if n == 0:
+        return out
+    n1, n2, n3 = (int(v) for v in vol.shape)
+    with torch.cuda.device(vol.device):
+        _abi.check(_abi.lib().naf_volume_sample_points(_abi.ptr(vol), n1, n2, n3, d, _abi.ptr(points), n, _abi.ptr(out),
+                                                       _abi.stream_ptr()), who)
+    return out
+
+
+def draw_sample(vol, dvoxel, lo, hi, seed, step, n, points_out=None, targets_out=None):
+    """`naf_volume_draw_sample`: `n` points uniform in the box [lo, hi] (three floats each) from the counter-based hash of
+    (seed, step, index, axis), and the volume's trilinear value at each, in one launch -> (points [n, 3], targets [n]), float32 on
+    the volume's device.  No state and no torch generator: equal arguments give equal bits.  `points_out` / `targets_out` are
+    written in place when given."""
+    who = "draw_sample"
+    _check_sampled_volume(vol, who)
+    d = _voxel_size(dvoxel, who)
+    box = []
+    for name, v in (("lo", lo), ("hi", hi)):
+        v = [float(np.float32(x)) for x in np.asarray(v, dtype=np.float64).reshape(-1)]
+        if len(v) != 3 or not all(np.isfinite(x) for x in v):
+            raise ValueError(f"{who}: {name} must be three finite floats, got {v}")
+        box.append(v)
+    if any(a > b for a, b in zip(*box)):
+        raise ValueError(f"{who}: the box must have lo <= hi on every axis, got {box[0]} .. {box[1]}")
+    n, seed, step = int(n), int(seed), int(step)
+    if not 0 <= n < 2 ** 32 or not 0 <= step < 2 ** 32 or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{who}: n and step must fit 32 bits and seed 64 bits, got n {n}, step {step}, seed {seed}")
+    if points_out is None:
+        points_out = torch.empty((n, 3), dtype=torch.float32, device=vol.device)
+    else:
+        _abi.check_stack(points_out, (n, 3), vol, who, "points_out")
+    if targets_out is None:
+        targets_out = torch.empty(n, dtype=torch.float32, device=vol.device)
+    else:
+        _abi.check_stack(targets_out, (n,), vol, who, "targets_out")
+    if n == 0:
+        return points_out, targets_out
+    dims = (ctypes.c_uint32 * 3)(*(int(v) for v in vol.shape))
+    with torch.cuda.device(vol.device):
+        _abi.check(_abi.lib().naf_volume_draw_sample(_abi.ptr(vol), dims, d, (ctypes.c_float * 3)(*box[0]), (ctypes.c_float * 3)(*box[1]),
+                                                     seed, step, n, _abi.ptr(points_out), _abi.ptr(targets_out), _abi.stream_ptr()), who)
+    return points_out, targets_out

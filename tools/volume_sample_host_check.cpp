@@ -1,0 +1,147 @@
+// volume_sample_host_check.cpp -- runs the per-point arithmetic of csrc/volume_sample_device.h on the CPU, so that it can be compared
+// with a float64 evaluation and run under AddressSanitizer / UBSan (tools/volume_sample_host_check.py builds and drives it;
+// DESIGN.md section 24).  The volume lives on the heap and holds exactly n1 n2 n3 floats, so a load one element outside it is a
+// sanitizer report.  The kernels' launch geometry and their 12-byte point accesses are not compiled into this program; only the GPU
+// tests cover them.  No GPU, no HIP.
+//
+//   volume_sample_host_check sample n1 n2 n3 d1 d2 d3 n volume.f32 points.f32 out.f32
+//       samples the n points, writes out, prints "worst <largest |fp32 - float64| / (2^-24 max_a n_a max|f|)> nan <count>"
+//   volume_sample_host_check draw n1 n2 n3 d1 d2 d3 n seed step lo1 lo2 lo3 hi1 hi2 hi3 volume.f32 points.f32 targets.f32
+//       draws and samples n points, writes both, prints "outside <coordinates outside [lo, hi]>"
+//   volume_sample_host_check offsets
+//       cells of grids of more than 2^32 voxels against 64-bit integer arithmetic (no volume is allocated), prints "offsets <wrong>"
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../neuralvolumetricreconstructionformedicalimages_amd/csrc/volume_sample_device.h"
+
+namespace {
+
+bool read_all(const char *path, std::vector<float> &v) {
+    FILE *fp = std::fopen(path, "rb");
+    if (!fp) return false;
+    const size_t got = v.empty() ? 0 : std::fread(v.data(), sizeof(float), v.size(), fp);
+    std::fclose(fp);
+    return got == v.size();
+}
+
+bool write_all(const char *path, const std::vector<float> &v) {
+    FILE *fp = std::fopen(path, "wb");
+    if (!fp) return false;
+    const size_t put = v.empty() ? 0 : std::fwrite(v.data(), sizeof(float), v.size(), fp);
+    return std::fclose(fp) == 0 && put == v.size();
+}
+
+// The definition in float64 on the float32 inputs: u = (p + h) / d - 1/2 clamped, the eight products of weights.
+double sample_f64(const std::vector<float> &f, const uint32_t n[3], const float dvoxel[3], const float p[3]) {
+    int64_t lo[3], hi[3];
+    double w[3];
+    for (int a = 0; a < 3; ++a) {
+        const double h = (double)(float)((double)n[a] * (double)dvoxel[a] / 2.0);
+        double u = ((double)p[a] + h) / (double)dvoxel[a] - 0.5;
+        if (std::isnan(u)) return NAN;
+        u = std::fmin(std::fmax(u, 0.0), (double)n[a] - 1.0);
+        const double top = n[a] >= 2 ? (double)n[a] - 2.0 : 0.0;
+        const double i = std::fmin(std::floor(u), top);
+        lo[a] = (int64_t)i;
+        hi[a] = n[a] >= 2 ? lo[a] + 1 : lo[a];
+        w[a] = u - i;
+    }
+    double out = 0.0;
+    for (int x = 0; x < 2; ++x)
+        for (int y = 0; y < 2; ++y)
+            for (int z = 0; z < 2; ++z) {
+                const size_t at = ((size_t)(x ? hi[0] : lo[0]) * n[1] + (size_t)(y ? hi[1] : lo[1])) * n[2] + (size_t)(z ? hi[2] : lo[2]);
+                out += (x ? w[0] : 1.0 - w[0]) * (y ? w[1] : 1.0 - w[1]) * (z ? w[2] : 1.0 - w[2]) * (double)f.at(at);
+            }
+    return out;
+}
+
+int offsets() {
+    // 2048^3 = 2^33 voxels: the offset of a cell near the far corner needs 34 bits.  Only sample_cell runs: nothing is loaded.
+    int wrong = 0;
+    const uint32_t dims[2][3] = {{2048, 2048, 2048}, {70000, 300, 400}};
+    for (const auto &n : dims) {
+        const float d[3] = {0.001f, 0.001f, 0.001f};
+        naf::SampleGrid g;
+        naf::sample_grid(n[0], n[1], n[2], d, &g);
+        for (int k = 0; k < 64; ++k) {
+            uint32_t i[3];
+            float p[3], w[3];
+            for (int a = 0; a < 3; ++a) {
+                i[a] = (uint32_t)(((uint64_t)(n[a] - 2u) * (uint64_t)(k + (k % 3 == a ? 0 : 63 - k))) / 63u);
+                p[a] = (float)(((double)i[a] + 0.75 - (double)n[a] / 2.0) * (double)d[a]);       // a quarter into cell i_a
+            }
+            const uint64_t want = ((uint64_t)i[0] * n[1] + i[1]) * n[2] + i[2];
+            if (naf::sample_cell(g, p, w) != want) ++wrong;
+        }
+    }
+    std::printf("offsets %d\n", wrong);
+    return wrong ? 1 : 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    if (argc == 2 && !std::strcmp(argv[1], "offsets")) return offsets();
+    const bool samp = argc == 12 && !std::strcmp(argv[1], "sample");
+    const bool draw = argc == 20 && !std::strcmp(argv[1], "draw");
+    if (!samp && !draw) {
+        std::fprintf(stderr, "usage: %s sample n1 n2 n3 d1 d2 d3 n volume points out | draw n1 n2 n3 d1 d2 d3 n seed step lo(3) hi(3) "
+                             "volume points targets | offsets\n", argv[0]);
+        return 2;
+    }
+    const uint32_t n[3] = {(uint32_t)std::atoi(argv[2]), (uint32_t)std::atoi(argv[3]), (uint32_t)std::atoi(argv[4])};
+    const float d[3] = {(float)std::atof(argv[5]), (float)std::atof(argv[6]), (float)std::atof(argv[7])};
+    const size_t count = (size_t)std::strtoull(argv[8], nullptr, 10);
+    if (n[0] == 0 || n[1] == 0 || n[2] == 0 || !(d[0] > 0.0f) || !(d[1] > 0.0f) || !(d[2] > 0.0f)) return 2;
+    std::vector<float> f((size_t)n[0] * n[1] * n[2]);                   // exactly the volume: nothing to spare behind it
+    if (!read_all(argv[samp ? 9 : 17], f)) return 3;
+    naf::SampleGrid g;
+    naf::sample_grid(n[0], n[1], n[2], d, &g);
+    std::vector<float> pts(3 * count), out(count);
+
+    if (samp) {
+        if (!read_all(argv[10], pts)) return 3;
+        double fmax = 0.0, worst = 0.0;
+        for (float v : f) fmax = std::fmax(fmax, std::fabs((double)v));
+        const double unit = std::ldexp(1.0, -24) * (double)std::max(n[0], std::max(n[1], n[2])) * fmax;
+        size_t nans = 0;
+        for (size_t k = 0; k < count; ++k) {
+            out[k] = naf::sample_point(f.data(), g, &pts[3 * k]);
+            const double want = sample_f64(f, n, d, &pts[3 * k]);
+            if (std::isnan(want) != std::isnan(out[k])) return 4;        // NaN exactly where the definition has it
+            if (std::isnan(want)) {
+                ++nans;
+                continue;
+            }
+            if (unit > 0.0) worst = std::fmax(worst, std::fabs((double)out[k] - want) / unit);
+            else if ((double)out[k] != want) return 4;
+        }
+        if (!write_all(argv[11], out)) return 3;
+        std::printf("worst %.6g nan %zu\n", worst, nans);
+        return 0;
+    }
+
+    const uint64_t seed = std::strtoull(argv[9], nullptr, 10);
+    const uint32_t step = (uint32_t)std::strtoul(argv[10], nullptr, 10);
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = (float)std::atof(argv[11 + a]);
+        hi[a] = (float)std::atof(argv[14 + a]);
+    }
+    size_t outside = 0;
+    for (size_t k = 0; k < count; ++k) {
+        float *p = &pts[3 * k];
+        naf::sample_draw(seed, step, (uint32_t)k, lo, hi, p);
+        out[k] = naf::sample_point(f.data(), g, p);
+        for (int a = 0; a < 3; ++a) outside += !(p[a] >= lo[a] && p[a] <= hi[a]);
+    }
+    if (!write_all(argv[18], pts) || !write_all(argv[19], out)) return 3;
+    std::printf("outside %zu\n", outside);
+    return 0;
+}
