@@ -797,6 +797,43 @@ int naf_volume_sample_points(const float *volume, uint32_t n1, uint32_t n2, uint
 int naf_volume_draw_sample(const float *volume, const uint32_t *dims, const float *dvoxel, const float *lo, const float *hi,
                            uint64_t seed, uint32_t step, uint32_t n, float *points_out, float *targets_out, void *stream);
 
+/* A1  reprojection alignment of projections: the scores of a window of integer translations of every view against its reprojection,
+ * the sub-pixel peak of each score table, and the resampler that undoes a view's shift (align.py, reconstruct.align_projections).
+ * DESIGN.md section 25; the arithmetic is csrc/align_device.h.
+ *   views   f32 [N, H, W] C-contiguous, u along the last axis, v along the rows; H, W in 1 .. NAF_ALIGN_MAX_EXTENT
+ *   shifts  f32 [N, 2] = (du, dv) in pixels; the measured view b is the ideal view p translated by +shift:
+ *           b[n](r, c) ~ p[n](r - dv, c - du)
+ * naf_align_shift_scores: scores f64 [N, 2 Rv + 1, 2 Ru + 1], for integer dv = j - Rv and du = i - Ru
+ *     S[n, j, i] = sum_r sum_c w[n, r, c] * (b[n, r + dv, c + du] - p[n, r, c])^2,   r in [Rv, H - 1 - Rv], c in [Ru, W - 1 - Ru]:
+ *   the same pixels of p and the same count for every shift, so the scores of a view are comparable.  d = b - p is one fp32
+ *   subtraction; the term is ((double)d * (double)d) * (double)w (w == NULL: the square alone, all weights one).  The window is cut
+ *   into tiles of 16 x 64 pixels; a tile's terms are added in row-major order into one fp64 partial per shift, and the partials of a
+ *   shift in ascending tile order: no atomics, a fixed order that depends on H, W, Rv and Ru alone.  Equal inputs give equal bits,
+ *   and a view's scores do not depend on the other views of the call.  0 <= R <= NAF_ALIGN_MAX_SHIFT and 2 R < extent on each axis;
+ *   R = 0 searches nothing on that axis.  `workspace`: naf_align_scores_workspace_bytes(N, H, W, Rv, Ru) bytes (0 for arguments the
+ *   call would refuse), 8-byte aligned; more is allowed and changes nothing.  A NaN or Inf pixel makes the scores it enters NaN or Inf.
+ * naf_align_peak: scores -> shifts f32 [N, 2] and flags i32 [N].  The argmin over (j, i), ties to the lowest row-major index; per
+ *   axis a with R_a > 0, the minimum off that axis' border and den = (S- - S0) + (S+ - S0) > 0: delta = 1/2 (S- - S+) / den in fp64,
+ *   clamped to [-1/2, 1/2], otherwise 0;  shift_a = fp32(index_a - R_a + delta).  flags bit 0: the minimum lies on the border of the
+ *   window on an axis with R_a > 0;  bit 1: a score of the view is not finite: its shift is (0, 0) and bit 0 is clear.
+ * naf_align_shift_views: out[n, r, c] = views[n](r + dv_n, c + du_n) by cubic convolution (Keys, a = -1/2): 4 x 4 taps in fp32, rows
+ *   first then columns, clamp-to-edge.  Per axis the shift is clamped on the float to [-(n + 1), n + 1] (beyond it every tap is the
+ *   edge pixel), split into floor and fraction t, and the tap indices are clamped in integers: no load leaves the view whatever the
+ *   shift holds.  The weight polynomials are factored so that K(0) = 1 and K(1) = K(2) = 0 exactly, and t = 0 copies the tap: a
+ *   whole-number shift returns the source's bits (of the clamped pixel).  A NaN shift makes that view NaN and no other; +-inf is a
+ *   far shift, every pixel an edge value.  out must not be views.
+ * All three take the stream, allocate nothing and never synchronise; N == 0 returns NAF_OK without examining the pointers; element
+ * offsets are 64-bit; float pointers are 4-byte and fp64 pointers 8-byte aligned. */
+#define NAF_ALIGN_MAX_SHIFT 16u
+#define NAF_ALIGN_MAX_EXTENT 16777216u
+#define NAF_ALIGN_FLAG_BORDER 1
+#define NAF_ALIGN_FLAG_NON_FINITE 2
+size_t naf_align_scores_workspace_bytes(uint32_t N, uint32_t H, uint32_t W, uint32_t Rv, uint32_t Ru);
+int naf_align_shift_scores(const float *b, const float *p, const float *w, uint32_t N, uint32_t H, uint32_t W, uint32_t Rv, uint32_t Ru,
+                           void *workspace, size_t workspace_bytes, double *scores, void *stream);
+int naf_align_peak(const double *scores, uint32_t N, uint32_t Rv, uint32_t Ru, float *shifts, int32_t *flags, void *stream);
+int naf_align_shift_views(const float *views, const float *shifts, uint32_t N, uint32_t H, uint32_t W, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,10 @@ SIGNATURES = {
     "naf_volume_draw_sample": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),
                                       ctypes.POINTER(ctypes.c_float * 3), ctypes.POINTER(ctypes.c_float * 3), _u64, _u32, _u32, _vp, _vp,
                                       _vp]),
+    "naf_align_scores_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32, _u32, _u32]),
+    "naf_align_shift_scores": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, ctypes.c_size_t, _vp, _vp]),
+    "naf_align_peak": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "naf_align_shift_views": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
 }
 
 

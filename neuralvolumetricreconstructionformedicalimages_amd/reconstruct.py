@@ -635,6 +635,111 @@ def pwls_weights(projections):
     return xp.exp(-projections)
 
 
+def _check_align(n_outer, tol):
+    n_outer, tol = int(n_outer), float(tol)
+    if n_outer < 0:
+        raise ValueError(f"align: n_outer must be >= 0, got {n_outer}")
+    if not tol >= 0.0:
+        raise ValueError(f"align: tol must be >= 0, got {tol}")
+    return n_outer, tol
+
+
+def align_operators(A, solve, b, shift_views, estimate_shifts, n_outer=5, center=True, warm=True, tol=0.02, callback=None):
+    """Reprojection alignment (the joint iteration of tomopy's `align_joint`) as array code over callables, on arrays of `b`'s kind
+    ([N, H, W]; torch tensors on any device, numpy arrays).  A view's shift is (du, dv) in pixels, `shifts[N, 2] = (du, dv)`, and
+    the measured view is the ideal one translated by +shift (align.py).
+
+        A(x)                   volume -> projections [N, H, W]
+        solve(a, x0)           projections, start volume or None -> (volume, the solver's last residual norm)
+        shift_views(b, S)      the views of b with the shifts S undone
+        estimate_shifts(a, p)  -> (delta [N, 2], flags [N]): the translation of every view of a against p; a flagged view comes
+                               with the step it is to take (its integer shift, or none at all)
+
+        S = 0
+        for k in range(n_outer):
+            a = shift_views(b, S)                    always from the original b: blur never accumulates
+            x, residual = solve(a, x if warm and k > 0 else None)
+            delta, flags = estimate_shifts(a, A(x))
+            S += delta
+            if center: S -= mean(S) per axis         a common translation is a gauge of the volume, not of the views
+            stop when max |delta| < tol              one host read per outer iteration
+
+    `callback(k, x, entry)` runs after every outer iteration with that iteration's reconstruction.  Returns (aligned, S, history):
+    `aligned = shift_views(b, S)` for the final S and one dict per outer iteration with `rms` (sqrt of the mean over the views of
+    |delta|^2), `max` (the largest |component| of delta), `flagged` (views with a non-zero flag) and `residual`."""
+    n_outer, tol = _check_align(n_outer, tol)
+    xp, _ = _namespace(b)
+    N = int(b.shape[0])
+    S = b.new_zeros((N, 2)) if xp.__name__ == "torch" else xp.zeros((N, 2), dtype=b.dtype)
+    x, history = None, []
+    for k in range(n_outer):
+        a = shift_views(b, S)
+        x, residual = solve(a, x if warm and k > 0 else None)
+        delta, flags = estimate_shifts(a, A(x))
+        S = S + delta
+        if center:
+            S = S - S.mean(0)
+        biggest = float(abs(delta).max()) if N else 0.0
+        entry = {"rms": math.sqrt(float((delta * delta).sum(dtype=xp.float64)) / max(N, 1)), "max": biggest,
+                 "flagged": int((flags != 0).sum()), "residual": residual}
+        history.append(entry)
+        if callback is not None:
+            callback(k, x, entry)
+        if biggest < tol:
+            break
+    return shift_views(b, S), S, history
+
+
+ALIGN_SOLVERS = ("sirt", "cgls", "os_sart", "fista_tv", "asd_pocs")
+
+
+def align_projections(projections, geo, angles, n_outer=5, max_shift=4, solver="sirt", n_iter=20, center=True, warm=True, tol=0.02,
+                      weights=None, kind="interpolated", deterministic=False, callback=None, **solver_kwargs):
+    """Aligns `projections` [N, H, W] (float32, on the GPU) taken with `geo` at `angles` to their own reprojection: per-view detector
+    translations of up to `max_shift` pixels per outer iteration (an int, or (Ru, Rv); at most 16) are found and undone ->
+    (aligned [N, H, W], shifts float32 [N, 2] = (du, dv), history).  The iteration of `align_operators`: `solver` (one of
+    ALIGN_SOLVERS, run for `n_iter` iterations with `**solver_kwargs`, warm-started from the previous outer iteration's volume if
+    `warm`) reconstructs, `projector.project_scan` reprojects, `align.estimate_shifts` finds every view's translation and
+    `align.shift_views` resamples the ORIGINAL views with the accumulated shifts.  `weights` (float32 [N, H, W] >= 0, None for all
+    ones) weigh the squared differences of the shift search, so a mask leaves pixels out; `solver="cgls"` is given them too.
+    `kind` and `deterministic` go to the solver and the projector unchanged, and what those refuse stays refused.  The alignment
+    kernels add no atomics: with `deterministic=True` on the interpolated pair two runs return the same bits.  `callback(k, x,
+    entry)` sees every outer iteration's reconstruction."""
+    import torch
+
+    from . import align, projector
+    solvers = {"sirt": sirt, "cgls": cgls, "os_sart": os_sart, "fista_tv": fista_tv, "asd_pocs": asd_pocs}
+    if solver not in solvers:
+        raise ValueError(f"align_projections: solver must be one of {ALIGN_SOLVERS}, got {solver!r}")
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError("align_projections: projections must be a CUDA/HIP tensor (no CPU path)")
+    _check_align(n_outer, tol)
+    _check_kind("align_projections", kind, deterministic)
+    scan = projector.Scan(geo, angles, projections.device)
+    shape = (scan.N, scan.H, scan.W)
+    if projections.dtype != torch.float32 or tuple(projections.shape) != shape or not projections.is_contiguous():
+        raise ValueError(f"align_projections: projections must be contiguous float32 {shape}, got {projections.dtype} "
+                         f"{tuple(projections.shape)}")
+    align.window(max_shift, scan.H, scan.W, "align_projections")
+    if solver == "cgls" and weights is not None:
+        solver_kwargs = {"weights": weights, **solver_kwargs}
+    workspace = align.scores_workspace(scan.N, scan.H, scan.W, max_shift, projections.device)
+
+    def solve(a, x0):
+        x, hist = solvers[solver](a, geo, angles, n_iter=n_iter, x0=x0, kind=kind, deterministic=deterministic, **solver_kwargs)
+        last = hist[-1] if hist else math.nan
+        return x, float(last["residual"] if isinstance(last, dict) else last)
+
+    def A(x):
+        return projector.project_scan(x, geo, angles, kind=kind, scan=scan)
+
+    def estimate(a, p):
+        return align.estimate_shifts(a, p, max_shift, weights, workspace)
+
+    return align_operators(A, solve, projections, align.shift_views, estimate, n_outer=n_outer, center=center, warm=warm, tol=tol,
+                           callback=callback)
+
+
 def fdk_weights(geo, angles, filter="ram-lak"):
     """What `filter_rows` needs for an FDK reconstruction of a scan of `geo` at `angles`, as float32 numpy arrays, each formed in
     float64 and rounded once: (taps [W], pre [H, W] or None, post [H, W] or None, view_scale [N]).  See the module docstring."""
