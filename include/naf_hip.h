@@ -491,8 +491,16 @@ int naf_backproject_scan(const float *projections, const uint32_t *dims, const f
 #define NAF_FILTER_MAX_WIDTH 16384u
 int naf_filter_rows(const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre, const float *post,
                     const float *view_scale, float *out, void *stream);
+/* The same filter with one more factor, a weight per view and detector column (the short-scan weights of reconstruct.fdk, DESIGN.md
+ * section 26):
+ *   col         f32 [n_views, W] or NULL
+ *   out[i, r, n] = view_scale[i] * (post[r, n] * sum_{k = 0 .. W - 1} taps[|n - k|] * ((pre[r, k] * in[i, r, k]) * col[i, k]))
+ * x_k takes one more fp32 multiply, after pre's; everything else, the argument checks included, is naf_filter_rows, which is this
+ * call with col == NULL, bit for bit. */
+int naf_filter_rows_views(const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre,
+                          const float *post, const float *view_scale, const float *col, float *out, void *stream);
 
-/* P4  the subset step of OS-SART (reconstruct.os_sart): for a list s of views of a scan,
+/* P4 the subset step of OS-SART (reconstruct.os_sart): for a list s of views of a scan,
  *   x <- x + relax * C_s (.) A_s^T (R_s (.) (b_s - A_s x)),  R = 1 / (A 1),  C_s = 1 / (A_s^T 1),  then x <- max(x, 0)
  * as three launches, with A and A^T those of P1 and P2 restricted to the list.  All arithmetic is fp32, all offsets are 64-bit.
  *   view_index   DEVICE u32 [n_sub], or NULL for the identity (then n_sub <= n_scan_views).  Launch view j is scan view

@@ -151,6 +151,7 @@ SIGNATURES = {
     "naf_backproject_scan_siddon": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32,
                                            _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
     "naf_filter_rows": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "naf_filter_rows_views": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "naf_sart_residual_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
                                       _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "naf_sart_backproject_scan": (_i32, [_vp, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),

@@ -1,9 +1,10 @@
-// filter.hip -- detector-row filter for gfx950 (naf_filter_rows): the ramp filter of the FDK baseline, as a dense convolution of
-// every detector row with a symmetric tap array.  Defined in include/naf_hip.h (P3) and DESIGN.md section 15; the per-output
-// arithmetic is csrc/filter_device.h.
+// filter.hip -- detector-row filter for gfx950 (naf_filter_rows, naf_filter_rows_views): the ramp filter of the FDK baseline, as a
+// dense convolution of every detector row with a symmetric tap array.  Defined in include/naf_hip.h (P3) and DESIGN.md sections 15
+// and 26; the per-output arithmetic is csrc/filter_device.h.
 //
-// Layout: one detector row per workgroup.  The workgroup stages the pre-weighted row x[k] = pre[r, k] * in[i, r, k] and the taps in
-// LDS, then every lane owns kR = 8 consecutive outputs n0 .. n0 + 7 and walks k = 0 .. W - 1.  Output n0 + j needs taps[|n0 + j - k|]
+// Layout: one detector row per workgroup.  The workgroup stages the pre-weighted row x[k] = pre[r, k] * in[i, r, k] (times
+// col[i, k], the per-view column weight of naf_filter_rows_views, where one is given) and the taps in LDS, then every lane owns
+// kR = 8 consecutive outputs n0 .. n0 + 7 and walks k = 0 .. W - 1.  Output n0 + j needs taps[|n0 + j - k|]
 // at step k, which is what output n0 + j - 1 used at step k - 1: the lane keeps the eight taps in a register window and each step
 // slides one new tap, taps[|n0 - k - 1|], into it.  A step is one broadcast read of x[k] (every lane the same address), one read
 // of the new tap and eight FMAs.  The lanes' tap addresses are 8 words apart, which is eight lanes to a bank; the taps are therefore
@@ -47,7 +48,7 @@ __device__ __forceinline__ void filter_steps(const float *xs, const float *ts, u
 
 __global__ void __launch_bounds__(kMaxThreads)
 filter_rows_kernel(const float *in, uint32_t H, uint32_t W, const float *__restrict__ taps, const float *__restrict__ pre,
-                   const float *__restrict__ post, const float *__restrict__ view_scale, float *out) {
+                   const float *__restrict__ post, const float *__restrict__ view_scale, const float *__restrict__ col, float *out) {
     extern __shared__ __align__(16) float lds[];
     float *xs = lds;                               // [W]
     float *ts = lds + row_words(W);                // tap m at ts[tap_slot(m)], m = 0 .. W
@@ -55,11 +56,11 @@ filter_rows_kernel(const float *in, uint32_t H, uint32_t W, const float *__restr
     const uint32_t tid = threadIdx.x, threads = blockDim.x;
     const uint32_t row = blockIdx.x, r = row % H, view = row / H;
     const uint64_t base = (uint64_t)row * W, wbase = (uint64_t)r * W;      // 64-bit: 720 x 2048 x 2048 values is 12 GB
+    const uint64_t cbase = (uint64_t)view * W;
 
+    const bool has_pre = pre != nullptr, has_col = col != nullptr;
     for (uint32_t k = tid; k < W; k += threads) {
-        float v = in[base + k];
-        if (pre) v = filter_weigh(v, pre[wbase + k]);
-        xs[k] = v;
+        xs[k] = filter_stage(in[base + k], has_pre, has_pre ? pre[wbase + k] : 1.0f, has_col, has_col ? col[cbase + k] : 1.0f);
         ts[tap_slot(k)] = taps[k];
     }
     if (tid == 0) ts[tap_slot(W)] = 0.0f;
@@ -100,18 +101,27 @@ filter_rows_kernel(const float *in, uint32_t H, uint32_t W, const float *__restr
 
 using namespace naf;
 
-extern "C" int naf_filter_rows(const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre,
-                               const float *post, const float *view_scale, float *out, void *stream) {
+namespace {
+
+// Both entry points: `col` is NULL for naf_filter_rows; `name` heads the error messages.
+int filter_rows_launch(const char *name, const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre,
+                       const float *post, const float *view_scale, const float *col, float *out, void *stream) {
     char msg[160];
     if (W == 0 || W > NAF_FILTER_MAX_WIDTH) {
-        std::snprintf(msg, sizeof(msg), "filter_rows: row width %u is outside 1 .. %u (the row and its taps are staged in LDS)", W,
+        std::snprintf(msg, sizeof(msg), "%s: row width %u is outside 1 .. %u (the row and its taps are staged in LDS)", name, W,
                       (unsigned)NAF_FILTER_MAX_WIDTH);
         return fail(NAF_ERR_INVALID_ARGUMENT, msg);
     }
     const uint64_t rows = (uint64_t)n_views * H;
     if (rows == 0) return NAF_OK;
-    if (!in || !taps || !out) return fail(NAF_ERR_INVALID_ARGUMENT, "filter_rows: null pointer");
-    if (rows > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "filter_rows: more than 2^31 - 1 rows in one call");
+    if (!in || !taps || !out) {
+        std::snprintf(msg, sizeof(msg), "%s: null pointer", name);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
+    if (rows > 0x7fffffffull) {
+        std::snprintf(msg, sizeof(msg), "%s: more than 2^31 - 1 rows in one call", name);
+        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    }
     const uint32_t lanes = (W + kR - 1u) / kR;
     const uint32_t threads = std::min(kMaxThreads, (lanes + 63u) & ~63u);
     const uint32_t lds = filter_lds_bytes(W);
@@ -119,6 +129,18 @@ extern "C" int naf_filter_rows(const float *in, uint32_t n_views, uint32_t H, ui
     if (rc != NAF_OK) return rc;
     { ProfScope prof_("filter_rows_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(filter_rows_kernel, dim3((uint32_t)rows), dim3(threads), lds, (hipStream_t)stream, in, H, W, taps, pre, post,
-                         view_scale, out); }
+                         view_scale, col, out); }
     return check_launch("filter_rows_kernel");
+}
+
+}  // namespace
+
+extern "C" int naf_filter_rows(const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre,
+                               const float *post, const float *view_scale, float *out, void *stream) {
+    return filter_rows_launch("filter_rows", in, n_views, H, W, taps, pre, post, view_scale, nullptr, out, stream);
+}
+
+extern "C" int naf_filter_rows_views(const float *in, uint32_t n_views, uint32_t H, uint32_t W, const float *taps, const float *pre,
+                                     const float *post, const float *view_scale, const float *col, float *out, void *stream) {
+    return filter_rows_launch("filter_rows_views", in, n_views, H, W, taps, pre, post, view_scale, col, out, stream);
 }

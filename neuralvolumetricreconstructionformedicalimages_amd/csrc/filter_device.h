@@ -15,8 +15,16 @@
 
 namespace naf {
 
-// x[k] = pre[r, k] * in[i, r, k]: the value the sum reads (staged once per row by the kernel).
+// x[k] = pre[r, k] * in[i, r, k]: the value the sum reads (staged once per row by the kernel).  naf_filter_rows_views applies it a
+// second time, x[k] = col[i, k] * (pre[r, k] * in[i, r, k]): one more multiply, after pre's.
 NAF_FILTER_HD float filter_weigh(float v, float w) { return w * v; }
+
+// The staged value with every factor that is present, in the kernel's order: pre, then col.
+NAF_FILTER_HD float filter_stage(float v, bool has_pre, float pre, bool has_col, float col) {
+    if (has_pre) v = filter_weigh(v, pre);
+    if (has_col) v = filter_weigh(v, col);
+    return v;
+}
 
 // The tap that output n applies to input k: taps[|n - k|].
 NAF_FILTER_HD uint32_t filter_tap_index(uint32_t n, uint32_t k) { return n >= k ? n - k : k - n; }

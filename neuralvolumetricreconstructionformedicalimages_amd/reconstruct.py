@@ -101,7 +101,9 @@ one.  The 1 / U^2 of FDK is therefore already in A^T and no second back-projecto
     cone:      x_FDK = A^T y,   y_i = w_i * (DSO^2 / DSD^2) * (du dv / dV) * cos(gamma) * q_i
     parallel:  x_FDK = A^T y,   y_i = w_i * (du dv / dV) * q_i,   with tau = du and no cosine weights
 
-No short-scan (Parker) weights: a cone scan that covers less than a full turn is reconstructed with a bias.  A tilted
+By default there are no short-scan weights: a cone scan that covers less than a full turn is then reconstructed with a bias.
+`short_scan="parker"` multiplies p_i[r, k] by Parker's weight of view i and column k (`filter.parker_weights`, inside the filter's
+pass) and takes w_i = gap_i, for scans of pi .. 2 pi.  A tilted
 (laminographic) scan is refused: its constant and filter direction are not verified here.
 
 The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
@@ -761,24 +763,50 @@ def fdk_weights(geo, angles, filter="ram-lak"):
     return F.ramp_taps(W, du * DSO / DSD, filter), cos, cos, (w * (DSO / DSD) ** 2).astype(np.float32)
 
 
-def fdk_operators(AT, filter_rows, b, geo, angles, filter="ram-lak", nonneg=False):
+SHORT_SCAN = (None, "parker")
+
+
+def fdk_short_scan_weights(geo, angles, filter="ram-lak"):
+    """`fdk_weights` for a short scan, with Parker's weights: (taps [W], pre, post, view_scale [N], col [N, W]), float32 numpy
+    arrays, each formed in float64 and rounded once.  `col` is `filter.parker_weights`, whose refusals apply.  A ray pair's weights
+    sum to 1 where a full scan gives each 1/2 of 2 pi, so view i stands for its own angular step: w_i = gap_i
+    (`filter.view_gaps`), which is `view_weights` * covered range / pi, times `fdk_weights`' constants."""
+    from . import filter as F
+    import numpy as np
+    taps, pre, post, _ = fdk_weights(geo, angles, filter)
+    col = F.parker_weights(geo, angles)
+    du, dv = float(geo.dDetector[0]), float(geo.dDetector[1])
+    dV = float(np.prod(np.asarray(geo.dVoxel, dtype=np.float64)))
+    w = F.view_gaps(angles) * (du * dv / dV)
+    if geo.mode == "cone":
+        w = w * (float(geo.DSO) / float(geo.DSD)) ** 2
+    return taps, pre, post, w.astype(np.float32), col.astype(np.float32)
+
+
+def fdk_operators(AT, filter_rows, b, geo, angles, filter="ram-lak", nonneg=False, short_scan=None):
     """FDK over the transpose `AT` (projections -> volume, as in `sirt_operators`) and a row filter
     `filter_rows(b, taps, pre, post, view_scale)` that takes the float32 numpy arrays of `fdk_weights` and returns the filtered
-    projections as an array of `b`'s kind.  Returns AT(filter_rows(b, ...)), clamped at 0 if `nonneg`."""
+    projections as an array of `b`'s kind.  Returns AT(filter_rows(b, ...)), clamped at 0 if `nonneg`.  With
+    `short_scan="parker"` the arrays are those of `fdk_short_scan_weights` and the filter is called with a sixth, `col` [N, W]."""
+    if short_scan not in SHORT_SCAN:
+        raise ValueError(f"fdk: short_scan must be one of {SHORT_SCAN}, got {short_scan!r}")
     if len(b.shape) != 3 or int(b.shape[0]) != len(angles):
         raise ValueError(f"fdk: projections must be [N, H, W] with one view per angle, got {tuple(b.shape)} for {len(angles)} angles")
-    taps, pre, post, view_scale = fdk_weights(geo, angles, filter)
-    x = AT(filter_rows(b, taps, pre, post, view_scale))
+    if short_scan is None:
+        taps, pre, post, view_scale = fdk_weights(geo, angles, filter)
+        x = AT(filter_rows(b, taps, pre, post, view_scale))
+    else:
+        x = AT(filter_rows(b, *fdk_short_scan_weights(geo, angles, filter)))
     if nonneg:
         x = _namespace(b)[1](x, 0, None)
     return x
 
 
-def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call=None, deterministic=False):
+def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call=None, deterministic=False, short_scan=None):
     """FDK reconstruction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` (ConeGeometry, cone or untilted parallel
     beam) at `angles` -> float32 volume of geo.nVoxel on the projections' device.  One pass of `filter.filter_rows` and one of
     `projector.backproject_scan`; see the module docstring.  `deterministic=True` takes the atomic-free transpose: two runs return
-    the same bits."""
+    the same bits.  `short_scan="parker"` weighs the rays of a scan of pi .. 2 pi by Parker's weights, inside the filter's pass."""
     import torch
 
     from . import filter as F
@@ -786,8 +814,8 @@ def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call
     def on_device(a):
         return None if a is None else torch.tensor(a, device=projections.device)
 
-    def rows(b, taps, pre, post, view_scale):
-        return F.filter_rows(b, on_device(taps), on_device(pre), on_device(post), on_device(view_scale))
+    def rows(b, taps, pre, post, view_scale, col=None):
+        return F.filter_rows(b, on_device(taps), on_device(pre), on_device(post), on_device(view_scale), on_device(col))
 
     _, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device)
-    return fdk_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=nonneg)
+    return fdk_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=nonneg, short_scan=short_scan)

@@ -6,6 +6,10 @@ sum as one fp32 torch matmul with the dense Toeplitz matrix, and next to the bac
 
     python tools/filter_bench.py
     python tools/filter_bench.py --shape foot --views 64
+    python tools/filter_bench.py --shape chest --col
+
+`--col` adds Parker's weights of the scan's views (filter.parker_weights, float32 [N, W]) as the per-view column weight, so that the
+call is naf_filter_rows_views; the same shape without the option is the comparison.
 
 Reported per shape, one JSON line: device-event time of one call (median, minimum and maximum of `--windows` windows of `--iters`
 calls after warm-up, the method of tools/backproject_bench.py), the W^2 FMAs per row it performs and the rate that gives, the
@@ -25,10 +29,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 SHAPES = {"chest": (50, 512, 512, 256), "foot": (None, 2048, 2048, None)}      # views, H, W, voxels of the volume behind it
 
 
-def run(shape, views, warmup, iters, windows):
+def run(shape, views, warmup, iters, windows, with_col=False):
     from backproject_bench import _time
     from neuralvolumetricreconstructionformedicalimages_amd import phantom, projector
-    from neuralvolumetricreconstructionformedicalimages_amd.filter import filter_rows
+    from neuralvolumetricreconstructionformedicalimages_amd.filter import filter_rows, parker_weights
     from neuralvolumetricreconstructionformedicalimages_amd.geometry import ConeGeometry
     from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import fdk_weights
     N, H, W, nv = SHAPES[shape]
@@ -40,19 +44,21 @@ def run(shape, views, warmup, iters, windows):
     taps, pre, post, scale = (torch.tensor(a, device="cuda") for a in fdk_weights(geo, angles))
     x = torch.rand(N, H, W, device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
     out = torch.empty_like(x)
-    mine = _time(lambda: filter_rows(x, taps, pre, post, scale, out=out), warmup, iters, windows)
+    col = torch.tensor(parker_weights(geo, angles).astype(np.float32), device="cuda") if with_col else None
+    mine = _time(lambda: filter_rows(x, taps, pre, post, scale, col, out=out), warmup, iters, windows)
     n = torch.arange(W, device="cuda")
     T = taps[(n[:, None] - n[None, :]).abs()]                   # T[n, k] = taps[|n - k|]
     prev = torch.backends.cuda.matmul.allow_tf32
     torch.backends.cuda.matmul.allow_tf32 = False
 
     def dense():
-        return scale[:, None, None] * (post * torch.matmul(pre * x, T.t()))
+        xs = pre * x if col is None else (pre * x) * col[:, None, :]
+        return scale[:, None, None] * (post * torch.matmul(xs, T.t()))
     theirs = _time(dense, warmup, iters, windows)
     diff = float((dense() - out).abs().max() / out.abs().max())
     torch.backends.cuda.matmul.allow_tf32 = prev
     fmas = N * H * W * W
-    res = {"shape": shape, "views": N, "detector": [W, H], "filter_ms": round(mine[0], 4),
+    res = {"shape": shape, "views": N, "col": with_col, "detector": [W, H], "filter_ms": round(mine[0], 4),
            "filter_ms_min_max": [round(mine[1], 4), round(mine[2], 4)], "fma": fmas, "tera_fma_per_s": fmas / mine[0] * 1e-9,
            "torch_matmul_ms": round(theirs[0], 4), "torch_matmul_ms_min_max": [round(theirs[1], 4), round(theirs[2], 4)],
            "max_difference_from_matmul": diff}
@@ -67,12 +73,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", choices=["chest", "foot", "all"], default="all")
     ap.add_argument("--views", type=int, default=16, help="views of the foot shape")
+    ap.add_argument("--col", action="store_true", help="with a weight per view and column (naf_filter_rows_views)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--windows", type=int, default=3)
     args = ap.parse_args()
     for shape in (["chest", "foot"] if args.shape == "all" else [args.shape]):
-        print(json.dumps(run(shape, args.views, args.warmup, args.iters, args.windows)), flush=True)
+        print(json.dumps(run(shape, args.views, args.warmup, args.iters, args.windows, args.col)), flush=True)
         torch.cuda.empty_cache()
 
 

@@ -3,8 +3,10 @@
 csrc/filter_device.h, fed by a plain loop over every row; the kernel's own LDS staging, padded tap slots and sliding register window
 in csrc/filter.hip are not part of it) for the CPU with AddressSanitizer and UBSan, runs it over the shapes of the GPU tests, with and
 without the three factors, and prints its largest error as a share of the bound (W + 3) 2^-24 |view_scale post| sum |taps pre in|
-that tests/test_hip_filter.py asserts, next to the float64 convolution of tests/_filter_oracle.py.  The program is a stand-alone
-executable; nothing of it is loaded into Python.  No GPU.
+that tests/test_hip_filter.py asserts, next to the float64 convolution of tests/_filter_oracle.py.  Then the same with the weight per
+view and column of naf_filter_rows_views, `col`, against tests/_short_scan_oracle.py and the bound (W + 4) 2^-24 ... of
+tests/test_hip_short_scan.py; a `col` of ones must return the bits of the run without it.  The program is a stand-alone executable;
+nothing of it is loaded into Python.  No GPU.
 
     python tools/filter_host_check.py
 """
@@ -31,9 +33,9 @@ def build(workdir):
     return exe
 
 
-def run(exe, workdir, x, taps, pre, post, scale):
+def run(exe, workdir, x, taps, pre, post, scale, col=None):
     paths = []
-    for name, a in (("in", x), ("taps", taps), ("pre", pre), ("post", post), ("scale", scale)):
+    for name, a in (("in", x), ("taps", taps), ("pre", pre), ("post", post), ("scale", scale), ("col", col)):
         if a is None:
             paths.append("-")
             continue
@@ -67,6 +69,21 @@ def main():
                 got = run(exe, workdir, imp, taps, None, None, None)
                 assert got[0, 0].tobytes() == taps[np.abs(np.arange(shape[2]) - k0)].tobytes(), (shape, k0)
         print(f"largest error over all cases: {worst:.4f} of the bound; an impulse returns the taps bit for bit; no sanitizer report")
+        import _short_scan_oracle as S
+        worst = 0.0
+        for shape in S.SHAPES:
+            x, taps, pre, post, scale, col = S.filter_inputs(shape)
+            for name, w in (("col", (None, None, None, col)), ("all", (pre, post, scale, col))):
+                got = run(exe, workdir, x, taps, *w).astype(np.float64)
+                want, bound = S.filter_rows(x, taps, *w), S.filter_bound(x, taps, *w)
+                err = np.abs(got - want)
+                ratio = float((err / np.maximum(bound, np.finfo(np.float64).tiny)).max())
+                print(f"{shape} {name:8s}: max |out - float64| {err.max():.3e}  worst ratio to the bound {ratio:.4f}")
+                assert np.all(err <= bound), (shape, name)
+                worst = max(worst, ratio)
+            ones = run(exe, workdir, x, taps, pre, post, scale, np.ones_like(col))
+            assert ones.tobytes() == run(exe, workdir, x, taps, pre, post, scale).tobytes(), shape
+        print(f"with col, largest error over all cases: {worst:.4f} of the bound; a col of ones changes no bit; no sanitizer report")
 
 
 if __name__ == "__main__":
