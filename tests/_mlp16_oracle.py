@@ -161,10 +161,11 @@ def reference_rays(n, S, pattern):
     return sorted(probes + extra)
 
 
-def oracle_net(seed, log2T=12, scale=0.5):
-    """The canonical network's oracle twin with a random table (for the CPU tests; the GPU tests take _naf_helpers.naf_pair's)."""
+def oracle_net(seed, log2T=12, scale=0.5, L=16, C=2):
+    """The canonical network's oracle twin with a random table (for the CPU tests; the GPU tests take _naf_helpers.naf_pair's).
+    L x C = 32: the level shape of the encoder (tests/_mlp32_oracle.py runs 8 x 4 and 4 x 8)."""
     torch.manual_seed(seed)
-    enc = HashEncoderRef(3, 16, 2, 16, log2T)
+    enc = HashEncoderRef(3, L, C, 16, log2T)
     enc.embeddings.data.uniform_(-scale, scale)
     return DensityNetworkRef(enc, bound=BOUND, num_layers=4, hidden_dim=32, skips=(2,), out_dim=1, last_activation="sigmoid")
 
@@ -288,8 +289,10 @@ def rehearse(x, dist, target, weight, layers, rnd=bf16_round, dtype=torch.float6
     loss = (fault.get("loss_count", torch.ones(n)).to(dtype) * w * err * err).sum()
     gsig = (dacc[:, None] * dist).reshape(-1)
     xb = xr
-    if "feature_source" in fault:                                         # the backward of a point recomputed from another point's features
-        xb = xr.reshape(n, S, 32)[torch.arange(n)[:, None], fault["feature_source"]].reshape(n * S, 32)
+    if "feature_source" in fault:                                         # the backward of a point recomputed from another point's features:
+        src = fault["feature_source"]                                     # sample numbers [n, S] of the same ray, or (rays [n, S], samples [n, S])
+        src_ray, src_sample = src if isinstance(src, tuple) else (torch.arange(n)[:, None], src)
+        xb = xr.reshape(n, S, 32)[src_ray, src_sample].reshape(n * S, 32)
     m = fault.get("count")
     m = None if m is None else m.reshape(-1).to(dtype)
     if "extra" in fault:                                                  # points that should contribute nothing (padding)

@@ -57,6 +57,17 @@ def test_the_oracles_restatement_is_the_plan(plans):
         assert (p.parts, p.train_waves, p.slabs16) == (O.backward16_parts(n, S), O.mlp_train_waves(n, S), O.n_slabs(n, S)), (n, S, p)
 
 
+def test_the_32_point_restatement_is_the_plan(plans):
+    """slabs and forward grid of the 32-point kernels equal _mlp32_oracle's at every batch size of the grid and under either flag (the
+    32-point plan looks at neither), and so do the caps it restates."""
+    import _mlp32_oracle as M
+    caps, by_flags = plans
+    assert (caps.backward, caps.forward, caps.max_samples_lds) == (M.MAX_SLABS, M.MAX_FORWARD_GRID, O.MAX_SAMPLES_LDS)
+    for table in by_flags.values():
+        for (n, S), p in table.items():
+            assert (p.slabs32, p.forward_grid32) == (M.backward_slabs(n), M.forward_grid(n)), (n, S, p)
+
+
 def test_forward_splits_exactly_below_2048_rays_with_4_to_32_tiles(plans):
     _, by_flags = plans
     for (n, S), p in by_flags[0].items():
