@@ -427,8 +427,8 @@ int naf_adam_step(float *param, float *exp_avg, float *exp_avg_sq, float *grad, 
 
 /* E2  encoder input stage (hashgrid.py:122-125) without host round trips:
  *   out01[i] = (x[i] + size) / (2*size)   (IEEE fp32 add and divide, as torch evaluates it on the host)
- *   flag[0] |= 1 if any x[i] < -size or x[i] > size (or NaN); flag[1], flag[2] = min / max of x as
- *   order-preserving int32 (caller initialises flag to {0, INT32_MAX, INT32_MIN}).
+ *   flag[0] |= 1 if any x[i] < -size or x[i] > size (or NaN); flag[1], flag[2] = min / max of the x[i] that are not NaN as
+ *   order-preserving int32 (caller initialises flag to {0, INT32_MAX, INT32_MIN}; an input of NaN alone leaves those two).
  * out01 may be NULL (range check only).
  */
 int naf_normalize_inputs(const float *x, uint64_t n, float size, float *out01, int32_t *flag, void *stream);

@@ -211,11 +211,12 @@ normalize_inputs_kernel(const float *__restrict__ x, uint64_t n, float size, flo
                         int32_t *__restrict__ flag) {
     const float lo = -size, hi = size, denom = 2.0f * size;
     float mn = INFINITY, mx = -INFINITY;
+    bool bad = false;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const float v = x[i];
-        mn = fminf(mn, v);
+        mn = fminf(mn, v);                              // fminf / fmaxf drop a NaN: min and max are those of the other values,
         mx = fmaxf(mx, v);
-        if (v != v) { mn = v; mx = v; }
+        bad |= !(v >= lo && v <= hi);                   // and the range test is taken per value, so that a NaN raises the flag
         if (out01) out01[i] = (v + size) / denom;
     }
 #pragma unroll
@@ -223,10 +224,13 @@ normalize_inputs_kernel(const float *__restrict__ x, uint64_t n, float size, flo
         mn = fminf(mn, __shfl_xor(mn, off, 64));
         mx = fmaxf(mx, __shfl_xor(mx, off, 64));
     }
-    if ((threadIdx.x & 63u) == 0 && !(mn > mx)) {
-        if (!(mn >= lo) || !(mx <= hi)) atomicOr(flag, 1);
-        atomicMin(flag + 1, ordered_int(mn));
-        atomicMax(flag + 2, ordered_int(mx));
+    const bool wave_bad = __ballot(bad) != 0ull;
+    if ((threadIdx.x & 63u) == 0) {
+        if (wave_bad) atomicOr(flag, 1);
+        if (!(mn > mx)) {                               // a wave that saw no value (or NaN alone) leaves min / max as they are
+            atomicMin(flag + 1, ordered_int(mn));
+            atomicMax(flag + 2, ordered_int(mx));
+        }
     }
 }
 
