@@ -36,11 +36,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define NAF_AL_HD __host__ __device__ __forceinline__
-#else
-#define NAF_AL_HD inline
-#endif
+#include "host_device.h"
 
 namespace naf {
 
@@ -48,21 +44,21 @@ constexpr uint32_t kAlignMaxShift = 16;              // NAF_ALIGN_MAX_SHIFT
 constexpr int kAlignFlagBorder = 1, kAlignFlagNonFinite = 2;
 
 // ---- score ---------------------------------------------------------------------------------------------------------------------------
-NAF_AL_HD double align_term(float b, float p) {
+NAF_HD double align_term(float b, float p) {
     const float d = b - p;
     return (double)d * (double)d;
 }
 
-NAF_AL_HD double align_term(float b, float p, float w) { return align_term(b, p) * (double)w; }
+NAF_HD double align_term(float b, float p, float w) { return align_term(b, p) * (double)w; }
 
 // ---- peak ----------------------------------------------------------------------------------------------------------------------------
-NAF_AL_HD bool align_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }          // false for a NaN and for +-inf
+NAF_HD bool align_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }          // false for a NaN and for +-inf
 
 // The better of two candidates (value, row-major index): the smaller value, on a tie the lower index.  Values are finite here.
-NAF_AL_HD bool align_better(double va, uint32_t ia, double vb, uint32_t ib) { return va < vb || (va == vb && ia < ib); }
+NAF_HD bool align_better(double va, uint32_t ia, double vb, uint32_t ib) { return va < vb || (va == vb && ia < ib); }
 
 // Parabola through (-1, sm), (0, s0), (1, sp) with s0 the smallest: the vertex' offset, clamped to [-1/2, 1/2]; 0 if not convex.
-NAF_AL_HD double align_vertex(double sm, double s0, double sp) {
+NAF_HD double align_vertex(double sm, double s0, double sp) {
     const double den = (sm - s0) + (sp - s0);
     if (!(den > 0.0)) return 0.0;
     const double delta = 0.5 * (sm - sp) / den;
@@ -70,7 +66,7 @@ NAF_AL_HD double align_vertex(double sm, double s0, double sp) {
 }
 
 // Shift and flags of a table whose scores are all finite, given its argmin `at` (row-major).
-NAF_AL_HD void align_refine(const double *S, uint32_t Rv, uint32_t Ru, uint32_t at, float shift[2], int *flags) {
+NAF_HD void align_refine(const double *S, uint32_t Rv, uint32_t Ru, uint32_t at, float shift[2], int *flags) {
     const uint32_t nu = 2u * Ru + 1u, nv = 2u * Rv + 1u;
     const uint32_t j = at / nu, i = at % nu;
     const bool edge_u = Ru > 0u && (i == 0u || i == nu - 1u), edge_v = Rv > 0u && (j == 0u || j == nv - 1u);
@@ -83,7 +79,7 @@ NAF_AL_HD void align_refine(const double *S, uint32_t Rv, uint32_t Ru, uint32_t 
 }
 
 // The whole peak of one table, serially: what the kernel's parallel argmin must equal.
-NAF_AL_HD void align_peak(const double *S, uint32_t Rv, uint32_t Ru, float shift[2], int *flags) {
+NAF_HD void align_peak(const double *S, uint32_t Rv, uint32_t Ru, float shift[2], int *flags) {
     const uint32_t count = (2u * Rv + 1u) * (2u * Ru + 1u);
     uint32_t at = 0;
     bool finite = true;
@@ -109,7 +105,7 @@ struct AlignAxis {
 };
 
 // One axis of a view's shift; n is the extent (1 .. 2^24).
-NAF_AL_HD AlignAxis align_axis(float s, uint32_t n) {
+NAF_HD AlignAxis align_axis(float s, uint32_t n) {
     const float bound = (float)(n + 1u);
     const float c = fminf(fmaxf(s, -bound), bound);                       // a NaN leaves fmaxf as -bound
     const float f = floorf(c);
@@ -126,38 +122,30 @@ NAF_AL_HD AlignAxis align_axis(float s, uint32_t n) {
 }
 
 // Index of tap k of output coordinate x: clamp(x + i + k - 1, 0, n - 1), all in int64 (no wrap whatever the extents).
-NAF_AL_HD uint32_t align_tap(uint32_t x, const AlignAxis &a, int k, uint32_t n) {
+NAF_HD uint32_t align_tap(uint32_t x, const AlignAxis &a, int k, uint32_t n) {
     const int64_t at = (int64_t)x + (int64_t)a.i + (int64_t)k - 1;
     return at < 0 ? 0u : (at > (int64_t)n - 1 ? n - 1u : (uint32_t)at);
 }
 
-NAF_AL_HD float align_blend(const float v[4], const AlignAxis &a) {
+NAF_HD float align_blend(const float v[4], const AlignAxis &a) {
     if (a.t == 0.0f) return v[1];
     return fmaf(a.w[3], v[3], fmaf(a.w[2], v[2], fmaf(a.w[1], v[1], a.w[0] * v[0])));
 }
 
 // out(r, c) of one view `b` [H, W] under the axes of its shift: the sixteen taps are loaded before the first is used.
-NAF_AL_HD float align_sample(const float *b, uint32_t H, uint32_t W, uint32_t r, uint32_t c, const AlignAxis &av, const AlignAxis &au) {
+NAF_HD float align_sample(const float *b, uint32_t H, uint32_t W, uint32_t r, uint32_t c, const AlignAxis &av, const AlignAxis &au) {
     float v[4][4];
     uint32_t col[4];
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int k = 0; k < 4; ++k) col[k] = align_tap(c, au, k, W);
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int m = 0; m < 4; ++m) {
         const float *row = b + (uint64_t)align_tap(r, av, m, H) * W;
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+        NAF_UNROLL
         for (int k = 0; k < 4; ++k) v[m][k] = row[col[k]];
     }
     float rows[4];
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int m = 0; m < 4; ++m) rows[m] = align_blend(v[m], au);
     return align_blend(rows, av);
 }

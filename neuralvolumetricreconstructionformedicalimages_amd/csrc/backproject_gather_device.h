@@ -10,11 +10,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define NAF_GATHER_HD __host__ __device__ __forceinline__
-#else
-#define NAF_GATHER_HD inline
-#endif
+#include "host_device.h"
 
 namespace naf {
 
@@ -43,7 +39,7 @@ constexpr float kGatherEps = 1.0f / 524288.0f;
 // u_a = (p_a + h_a) / d_a - 1/2 lies in (i_a - 1, i_a + 1), that is p_a in (c_a - d_a, c_a + d_a) around the voxel centre c_a.
 // Clamp-to-edge gives an edge voxel the whole outer half cell, so the box reaches the volume's face there (an axis of one voxel: both
 // faces).  Widened by kGatherEps (h_a + d_a): the fp32 error of c_a, of the kernel's u_a and of the sample position.
-NAF_GATHER_HD void gather_support(const GatherGrid &g, const uint32_t i[3], float lo[3], float hi[3]) {
+NAF_HD void gather_support(const GatherGrid &g, const uint32_t i[3], float lo[3], float hi[3]) {
     for (int a = 0; a < 3; ++a) {
         const float m = kGatherEps * (g.half[a] + g.d[a]);
         const float below = ((float)i[a] - 0.5f) * g.d[a] - g.half[a], above = ((float)i[a] + 1.5f) * g.d[a] - g.half[a];
@@ -54,7 +50,7 @@ NAF_GATHER_HD void gather_support(const GatherGrid &g, const uint32_t i[3], floa
 
 // Smallest / largest pixel index whose centre, at (index + 1/2 - n / 2) * pitch + offset, can lie in [umin, umax] -> [first, last)
 // clipped to [0, n).  `margin` is in pixels.
-NAF_GATHER_HD void gather_pixel_range(float umin, float umax, float pitch, float offset, uint32_t n, uint32_t &first, uint32_t &last) {
+NAF_HD void gather_pixel_range(float umin, float umax, float pitch, float offset, uint32_t n, uint32_t &first, uint32_t &last) {
     const float shift = (float)n / 2.0f - 0.5f;
     const float a = (umin - offset) / pitch + shift, b = (umax - offset) / pitch + shift;
     const float margin = kGatherEps * ((float)n + (fabsf(offset) + fmaxf(fabsf(umin), fabsf(umax))) / fabsf(pitch));
@@ -71,7 +67,7 @@ NAF_GATHER_HD void gather_pixel_range(float umin, float umax, float pitch, float
 // project inside the convex hull of its eight projected corners, so the bounding rectangle of those serves.  Each corner's u, v is
 // widened by its fp32 error bound (section 17): kGatherEps S / q_z (DSD + |u|) for a cone, kGatherEps S for a parallel beam,
 // S = sum_a |p_a - t_a|.  A corner at or behind the source plane (q_z <= 0: no bound exists) gives the whole detector.
-NAF_GATHER_HD GatherRect gather_footprint(const float lo[3], const float hi[3], const float *P, const GatherDetector &det) {
+NAF_HD GatherRect gather_footprint(const float lo[3], const float hi[3], const float *P, const GatherDetector &det) {
     float umin = INFINITY, umax = -INFINITY, vmin = INFINITY, vmax = -INFINITY;
     bool whole = false;
     for (int c = 0; c < 8; ++c) {
@@ -109,8 +105,8 @@ NAF_GATHER_HD GatherRect gather_footprint(const float lo[3], const float hi[3], 
 // [k_lo, k_hi], false when there is none.  The slab test of ray_span on the box, with d[a] == 0 handled the same way; the interval
 // of t / seg - 1/2 is widened by one sample to either side, which covers the rounding of the two divisions and of span_point's
 // (k + 1/2) seg (relative 2^-23 of a value below n < 2^24; the box already carries the margin for positions).
-NAF_GATHER_HD bool gather_k_range(const float lo[3], const float hi[3], const float p0[3], const float d[3], float seg, uint32_t n,
-                                  uint32_t &k_lo, uint32_t &k_hi) {
+NAF_HD bool gather_k_range(const float lo[3], const float hi[3], const float p0[3], const float d[3], float seg, uint32_t n,
+                           uint32_t &k_lo, uint32_t &k_hi) {
     float t0 = 0.0f, t1 = INFINITY;
     for (int a = 0; a < 3; ++a) {
         if (d[a] == 0.0f) {
@@ -135,7 +131,7 @@ NAF_GATHER_HD bool gather_k_range(const float lo[3], const float hi[3], const fl
 // `voxel`: the scatter's (x[cx] * y[cy]) * z[cz] for the corner c whose offset cx next[0] + cy next[1] + cz next[2] is
 // voxel - cell, 0 if there is none.  An upper corner on a constant axis (next[a] == 0) does not exist.  The offsets of the existing
 // corners are distinct and no voxel other than a corner has one of them (section 17), so at most one term is taken.
-NAF_GATHER_HD float gather_corner_weight(uint64_t voxel, uint64_t cell, const uint64_t next[3], const float w[3]) {
+NAF_HD float gather_corner_weight(uint64_t voxel, uint64_t cell, const uint64_t next[3], const float w[3]) {
     const uint64_t diff = voxel - cell;                                        // wraps for a voxel below the cell: matches nothing
     const float x[2] = {1.0f - w[0], w[0]}, y[2] = {1.0f - w[1], w[1]}, z[2] = {1.0f - w[2], w[2]};
     float out = 0.0f;

@@ -17,16 +17,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define NAF_SIDDON_HD __host__ __device__ __forceinline__
-#else
-#define NAF_SIDDON_HD inline
-#endif
-#if defined(__clang__)
-#define NAF_SIDDON_UNROLL _Pragma("unroll")
-#else
-#define NAF_SIDDON_UNROLL
-#endif
+#include "host_device.h"
 
 namespace naf {
 
@@ -63,11 +54,11 @@ struct SiddonSpan {
 
 enum SiddonKind { kSiddonEmpty = 0, kSiddonOk = 1, kSiddonNotFinite = 2 };
 
-NAF_SIDDON_HD bool siddon_finite(float x) { return (x - x) == 0.0f; }   // false for NaN and +-infinity
+NAF_HD bool siddon_finite(float x) { return (x - x) == 0.0f; }   // false for NaN and +-infinity
 
-NAF_SIDDON_HD SiddonKind siddon_span(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, SiddonSpan &s) {
+NAF_HD SiddonKind siddon_span(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, SiddonSpan &s) {
     float t0 = near, t1 = far;
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (int k = 0; k < 3; ++k) {
         if (d[k] == 0.0f) {
             if (o[k] < -g.half[k] || o[k] > g.half[k]) t1 = -INFINITY;    // parallel to the slab and outside it
@@ -82,7 +73,7 @@ NAF_SIDDON_HD SiddonKind siddon_span(const SiddonGrid &g, const float o[3], cons
     s.dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     s.s_end = t1 - t0;
     bool finite = siddon_finite(s.s_end);
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (int k = 0; k < 3; ++k) {
         s.d[k] = d[k];
         s.p0[k] = fmaf(t0, d[k], o[k]);
@@ -93,14 +84,14 @@ NAF_SIDDON_HD SiddonKind siddon_span(const SiddonGrid &g, const float o[3], cons
 
 // Voxel index of coordinate p on axis a, clamped to [0, n_a - 1].  The clamp is made on the float (fmaxf / fminf drop a NaN), so the
 // conversion to an integer is defined for every input.
-NAF_SIDDON_HD int32_t siddon_index(const SiddonGrid &g, int a, float p) {
+NAF_HD int32_t siddon_index(const SiddonGrid &g, int a, float p) {
     float u = floorf((p + g.half[a]) * g.inv_d[a]);
     u = fminf(fmaxf(u, 0.0f), (float)(g.n[a] - 1u));
     return (int32_t)u;
 }
 
 // Parameter s (from p0) at which the ray crosses plane m of axis a: from m itself, never by increments.
-NAF_SIDDON_HD float siddon_crossing(const SiddonGrid &g, const SiddonSpan &r, int a, int32_t m) {
+NAF_HD float siddon_crossing(const SiddonGrid &g, const SiddonSpan &r, int a, int32_t m) {
     return (fmaf((float)m, g.dvox[a], -g.half[a]) - r.p0[a]) / r.d[a];
 }
 
@@ -115,11 +106,11 @@ struct SiddonWalk {
 };
 
 // Returns the number of steps: rem_x + rem_y + rem_z + 1.
-NAF_SIDDON_HD uint32_t siddon_begin(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w) {
+NAF_HD uint32_t siddon_begin(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w) {
     uint32_t steps = 1;
     w.offset = 0;
     w.s_prev = 0.0f;
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) {
         const int32_t i0 = siddon_index(g, a, r.p0[a]);
         const int32_t i1 = siddon_index(g, a, fmaf(r.s_end, r.d[a], r.p0[a]));
@@ -136,7 +127,7 @@ NAF_SIDDON_HD uint32_t siddon_begin(const SiddonGrid &g, const SiddonSpan &r, Si
 
 // One step: the offset of the current voxel and the length (in s) of the segment inside it, then the move across the nearest plane.
 // With no crossing left the segment runs to s_end, and every later step is a zero-length segment of the same voxel.
-NAF_SIDDON_HD void siddon_step(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w, uint64_t &offset, float &ds) {
+NAF_HD void siddon_step(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w, uint64_t &offset, float &ds) {
     const float dx = r.d[0], dy = r.d[1], dz = r.d[2];
     const bool ax = w.rem[0] > 0u, ay = w.rem[1] > 0u, az = w.rem[2] > 0u;
     // the smallest of the next crossings; an exhausted axis counts as +infinity: it is never chosen (integer tests gate every choice)
@@ -150,17 +141,17 @@ NAF_SIDDON_HD void siddon_step(const SiddonGrid &g, const SiddonSpan &r, SiddonW
     ds = s - w.s_prev;
     w.s_prev = s;
     // the move, without a branch: the picked axis steps, and its next crossing comes from its new plane by one division
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) {
         w.idx[a] += pick[a] ? w.dir[a] : 0;
         w.rem[a] -= pick[a] ? 1u : 0u;
         w.offset = (uint64_t)((int64_t)w.offset + (pick[a] ? w.jump[a] : (int64_t)0));
     }
     float num[3];
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) num[a] = fmaf((float)(w.idx[a] + (w.dir[a] > 0 ? 1 : 0)), g.dvox[a], -g.half[a]) - r.p0[a];
     const float c = (px ? num[0] : (py ? num[1] : num[2])) / (px ? dx : (py ? dy : dz));   // siddon_crossing of the picked axis
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) w.next[a] = pick[a] ? c : w.next[a];
 }
 
@@ -174,11 +165,11 @@ struct SiddonRay {
 // volume of ones (1.0f * len == len), so 1 / row is the weight R of the fp32 matrix P7 defines and no A 1 is ever stored.
 struct SiddonIntegral {
     float acc = 0.0f;
-    NAF_SIDDON_HD void add(float f, float len) { acc += f * len; }
+    NAF_HD void add(float f, float len) { acc += f * len; }
 };
 struct SiddonIntegralAndRow {
     float acc = 0.0f, row = 0.0f;
-    NAF_SIDDON_HD void add(float f, float len) {
+    NAF_HD void add(float f, float len) {
         acc += f * len;
         row += len;
     }
@@ -189,7 +180,7 @@ struct SiddonIntegralAndRow {
 // the first of them is used: the indices depend on one another, the loads do not.  Returns the span's kind; `sum` is left as it was
 // unless that is kSiddonOk, and what an empty or a non-finite span yields is the caller's to say.
 template <class Load, class Sum>
-NAF_SIDDON_HD SiddonKind siddon_forward(const SiddonGrid &g, const SiddonRay &ray, Load load, Sum &sum) {
+NAF_HD SiddonKind siddon_forward(const SiddonGrid &g, const SiddonRay &ray, Load load, Sum &sum) {
     SiddonSpan r;
     const SiddonKind kind = siddon_span(g, ray.o, ray.d, ray.near, ray.far, r);
     if (kind != kSiddonOk) return kind;
@@ -199,32 +190,32 @@ NAF_SIDDON_HD SiddonKind siddon_forward(const SiddonGrid &g, const SiddonRay &ra
     // while the next indices are computed
     float len[kSiddonGroup], f[kSiddonGroup];
     uint64_t offset[kSiddonGroup];
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (uint32_t j = 0; j < kSiddonGroup; ++j) {
         float ds;
         siddon_step(g, r, w, offset[j], ds);
         len[j] = ds * r.dn;
     }
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (uint32_t j = 0; j < kSiddonGroup; ++j) f[j] = load(offset[j]);
     for (uint32_t k = kSiddonGroup; k < steps; k += kSiddonGroup) {
         float len_next[kSiddonGroup], f_next[kSiddonGroup];
-        NAF_SIDDON_UNROLL
+        NAF_UNROLL
         for (uint32_t j = 0; j < kSiddonGroup; ++j) {
             float ds;
             siddon_step(g, r, w, offset[j], ds);
             len_next[j] = ds * r.dn;
         }
-        NAF_SIDDON_UNROLL
+        NAF_UNROLL
         for (uint32_t j = 0; j < kSiddonGroup; ++j) f_next[j] = load(offset[j]);
-        NAF_SIDDON_UNROLL
+        NAF_UNROLL
         for (uint32_t j = 0; j < kSiddonGroup; ++j) {
             sum.add(f[j], len[j]);
             f[j] = f_next[j];
             len[j] = len_next[j];
         }
     }
-    NAF_SIDDON_UNROLL
+    NAF_UNROLL
     for (uint32_t j = 0; j < kSiddonGroup; ++j) sum.add(f[j], len[j]);
     return kSiddonOk;                                      // the constant: a caller's tests of the kind then fold into the early return
 }
@@ -235,7 +226,7 @@ NAF_SIDDON_HD SiddonKind siddon_forward(const SiddonGrid &g, const SiddonRay &ra
 // voxel's fixed point) send nothing, and neither does an empty span, a non-finite one, or a deposit that says up front
 // (deposit.wanted()) that it has nothing to add.  A group is stepped first and sent after: nothing here waits for what `deposit` does.
 template <class Deposit>
-NAF_SIDDON_HD void siddon_transpose(const SiddonGrid &g, const SiddonRay &ray, const Deposit &deposit) {
+NAF_HD void siddon_transpose(const SiddonGrid &g, const SiddonRay &ray, const Deposit &deposit) {
     if (!deposit.wanted()) return;
     SiddonSpan r;
     if (siddon_span(g, ray.o, ray.d, ray.near, ray.far, r) != kSiddonOk) return;
@@ -244,13 +235,13 @@ NAF_SIDDON_HD void siddon_transpose(const SiddonGrid &g, const SiddonRay &ray, c
     for (uint32_t k = 0; k < steps; k += kSiddonGroup) {
         float len[kSiddonGroup];
         uint64_t offset[kSiddonGroup];
-        NAF_SIDDON_UNROLL
+        NAF_UNROLL
         for (uint32_t j = 0; j < kSiddonGroup; ++j) {
             float ds;
             siddon_step(g, r, w, offset[j], ds);
             len[j] = ds * r.dn;
         }
-        NAF_SIDDON_UNROLL
+        NAF_UNROLL
         for (uint32_t j = 0; j < kSiddonGroup; ++j)
             if (len[j] > 0.0f) deposit(offset[j], len[j]);
     }

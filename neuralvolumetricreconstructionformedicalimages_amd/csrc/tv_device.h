@@ -6,11 +6,7 @@
 
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define NAF_TV_HD __host__ __device__ __forceinline__
-#else
-#define NAF_TV_HD inline
-#endif
+#include "host_device.h"
 
 namespace naf {
 
@@ -24,7 +20,7 @@ struct TvStencil {
 };
 
 // m = sqrt(eps + d0^2 + d1^2 + d2^2), the squares added in axis order.
-NAF_TV_HD float tv_magnitude(float d0, float d1, float d2, float eps) {
+NAF_HD float tv_magnitude(float d0, float d1, float d2, float eps) {
     float s = d0 * d0;
     s = s + d1 * d1;
     s = s + d2 * d2;
@@ -33,24 +29,18 @@ NAF_TV_HD float tv_magnitude(float d0, float d1, float d2, float eps) {
 
 // g[v] = (D_0 + D_1 + D_2) f[v] / m[v]  -  sum_a [v_a < n_a - 1] D_a f[v + e_a] / m[v + e_a], the three terms subtracted in axis
 // order; *m_out = m[v].  Selects, not products, drop the absent neighbours: whatever lies in their slots has no effect.
-NAF_TV_HD float tv_point(const TvStencil &s, float eps, float *m_out) {
+NAF_HD float tv_point(const TvStencil &s, float eps, float *m_out) {
     float d[3];
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) d[a] = s.has_lo[a] ? s.c - s.lo[a] : 0.0f;
     const float m = tv_magnitude(d[0], d[1], d[2], eps);
     *m_out = m;
     float g = ((d[0] + d[1]) + d[2]) / m;
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) {
         if (!s.has_hi[a]) continue;
         float e[3];                                  // the backward differences of the neighbour u = v + e_a
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+        NAF_UNROLL
         for (int b = 0; b < 3; ++b) {
             if (b == a) e[b] = s.hi[a] - s.c;        // u_a = v_a + 1 > 0
             else e[b] = s.has_lo[b] ? s.hi[a] - s.diag[a][b] : 0.0f;
@@ -62,10 +52,10 @@ NAF_TV_HD float tv_point(const TvStencil &s, float eps, float *m_out) {
 
 // One normalised descent step: scale = step / ||g||_2 with the norm rounded to fp32 from the fp64 sum of squares; a sum that is
 // not > 0 (zero, or NaN) gives scale 0 and the volume stays as it is.
-NAF_TV_HD float tv_step_scale(double sum_g2, float step) {
+NAF_HD float tv_step_scale(double sum_g2, float step) {
     return sum_g2 > 0.0 ? step / (float)sqrt(sum_g2) : 0.0f;
 }
 
-NAF_TV_HD float tv_step_apply(float c, float g, float scale) { return c - scale * g; }
+NAF_HD float tv_step_apply(float c, float g, float scale) { return c - scale * g; }
 
 }  // namespace naf

@@ -8,30 +8,24 @@
 
 #include <cmath>
 
-#if defined(__HIPCC__)
-#define NAF_TVPROX_HD __host__ __device__ __forceinline__
-#else
-#define NAF_TVPROX_HD inline
-#endif
+#include "host_device.h"
 
 namespace naf {
 
 // The dual step 1 / (12 lambda): 12 >= ||D D^T|| in three dimensions.  Formed once on the host and passed to the kernel.
-NAF_TVPROX_HD float tvprox_dual_step(float lambda) { return 1.0f / (12.0f * lambda); }
+NAF_HD float tvprox_dual_step(float lambda) { return 1.0f / (12.0f * lambda); }
 
 // (D^T p)[v] = sum_a ([v_a > 0] p_a[v] - [v_a < n_a - 1] p_a[v + e_a]), the three terms added in axis order.
 // lo[a] = p_a[v], hi[a] = p_a[v + e_a]; has_lo[a] = v_a > 0, has_hi[a] = v_a < n_a - 1.
-NAF_TVPROX_HD float tvprox_adjoint(const float lo[3], const float hi[3], const bool has_lo[3], const bool has_hi[3]) {
+NAF_HD float tvprox_adjoint(const float lo[3], const float hi[3], const bool has_lo[3], const bool has_hi[3]) {
     float t[3];
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) t[a] = (has_lo[a] ? lo[a] : 0.0f) - (has_hi[a] ? hi[a] : 0.0f);
     return (t[0] + t[1]) + t[2];
 }
 
 // u = P_C(b - lambda * dt), dt = (D^T p)[v].  P_C clamps at 0 with a compare, so a NaN stays NaN.
-NAF_TVPROX_HD float tvprox_primal(float b, float dt, float lambda, bool nonneg) {
+NAF_HD float tvprox_primal(float b, float dt, float lambda, bool nonneg) {
     const float u = b - lambda * dt;
     return (nonneg && u < 0.0f) ? 0.0f : u;
 }
@@ -40,21 +34,17 @@ NAF_TVPROX_HD float tvprox_primal(float b, float dt, float lambda, bool nonneg) 
 //   q_a = [v_a > 0] (r_a + step * (u - u_lo[a]))          (a masked component is 0 and does not enter the norm)
 //   p_a = q_a / max(1, sqrt(q_0^2 + q_1^2 + q_2^2))       (squares added in axis order)
 //   r_next_a = p_a + momentum * (p_a - [v_a > 0] p_old_a)
-NAF_TVPROX_HD void tvprox_dual(float u, const float u_lo[3], const float r[3], const float p_old[3], const bool has_lo[3], float step,
-                               float momentum, float p[3], float r_next[3]) {
+NAF_HD void tvprox_dual(float u, const float u_lo[3], const float r[3], const float p_old[3], const bool has_lo[3], float step,
+                        float momentum, float p[3], float r_next[3]) {
     float q[3];
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) q[a] = has_lo[a] ? r[a] + step * (u - u_lo[a]) : 0.0f;
     float s = q[0] * q[0];
     s = s + q[1] * q[1];
     s = s + q[2] * q[2];
     const float n = sqrtf(s);
     const float d = n > 1.0f ? n : 1.0f;
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) {
         p[a] = q[a] / d;
         r_next[a] = p[a] + momentum * (p[a] - (has_lo[a] ? p_old[a] : 0.0f));

@@ -25,11 +25,7 @@
 #include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define NAF_VS_HD __host__ __device__ __forceinline__
-#else
-#define NAF_VS_HD inline
-#endif
+#include "host_device.h"
 
 namespace naf {
 
@@ -59,11 +55,9 @@ inline void sample_grid(uint32_t n1, uint32_t n2, uint32_t n3, const float *dvox
 }
 
 // The cell of p: the 64-bit element offset of its lower corner and the three weights of the upper corners.
-NAF_VS_HD uint64_t sample_cell(const SampleGrid &g, const float p[3], float w[3]) {
+NAF_HD uint64_t sample_cell(const SampleGrid &g, const float p[3], float w[3]) {
     uint64_t base = 0;
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+    NAF_UNROLL
     for (int a = 0; a < 3; ++a) {
         float u = p[a] + g.half[a];
         u = u * g.inv_d[a];
@@ -77,10 +71,10 @@ NAF_VS_HD uint64_t sample_cell(const SampleGrid &g, const float p[3], float w[3]
     return base;
 }
 
-NAF_VS_HD float sample_lerp(float a, float b, float w) { return fmaf(w, b, fmaf(-w, a, a)); }
+NAF_HD float sample_lerp(float a, float b, float w) { return fmaf(w, b, fmaf(-w, a, a)); }
 
 // The eight corners of the cell at `base`, all loaded before the first is used (c[4 x + 2 y + z]).
-NAF_VS_HD void sample_corners(const float *f, const SampleGrid &g, uint64_t base, float c[8]) {
+NAF_HD void sample_corners(const float *f, const SampleGrid &g, uint64_t base, float c[8]) {
     const float *q = f + base;
     const uint64_t sx = g.next[0], sy = g.next[1], sz = g.next[2];
     c[0] = q[0];
@@ -93,7 +87,7 @@ NAF_VS_HD void sample_corners(const float *f, const SampleGrid &g, uint64_t base
     c[7] = q[sx + sy + sz];
 }
 
-NAF_VS_HD float sample_blend(const float c[8], const float w[3]) {
+NAF_HD float sample_blend(const float c[8], const float w[3]) {
     const float c00 = sample_lerp(c[0], c[1], w[2]), c01 = sample_lerp(c[2], c[3], w[2]);
     const float c10 = sample_lerp(c[4], c[5], w[2]), c11 = sample_lerp(c[6], c[7], w[2]);
     const float c0 = sample_lerp(c00, c01, w[1]), c1 = sample_lerp(c10, c11, w[1]);
@@ -101,7 +95,7 @@ NAF_VS_HD float sample_blend(const float c[8], const float w[3]) {
 }
 
 // Value of the volume at p: trilinear, clamp-to-edge; NaN when a coordinate of p is NaN.
-NAF_VS_HD float sample_point(const float *f, const SampleGrid &g, const float p[3]) {
+NAF_HD float sample_point(const float *f, const SampleGrid &g, const float p[3]) {
     float w[3], c[8];
     const uint64_t base = sample_cell(g, p, w);
     sample_corners(f, g, base, c);
@@ -110,7 +104,7 @@ NAF_VS_HD float sample_point(const float *f, const SampleGrid &g, const float p[
 
 // ---- the draw: point i of step `step` under `seed`, uniform in the box [lo, hi] -----------------------------------------------------
 // The integer finaliser of csrc/naf_device.h's mix32 ("lowbias32"), restated here because that header needs HIP.
-NAF_VS_HD uint32_t sample_mix32(uint32_t h) {
+NAF_HD uint32_t sample_mix32(uint32_t h) {
     h ^= h >> 16; h *= 0x7feb352du;
     h ^= h >> 15; h *= 0x846ca68bu;
     h ^= h >> 16;
@@ -119,20 +113,18 @@ NAF_VS_HD uint32_t sample_mix32(uint32_t h) {
 
 // 32 random bits of (seed, step, i, axis): three rounds of the finaliser, each keyed by the next word.  No state: equal arguments
 // give equal bits.  All arithmetic is uint32 with wrap-around.
-NAF_VS_HD uint32_t sample_hash(uint64_t seed, uint32_t step, uint32_t i, uint32_t axis) {
+NAF_HD uint32_t sample_hash(uint64_t seed, uint32_t step, uint32_t i, uint32_t axis) {
     uint32_t h = sample_mix32((uint32_t)seed ^ (i * 0x9e3779b1u));
     h = sample_mix32(h ^ (uint32_t)(seed >> 32) ^ (step * 0x85ebca77u) ^ 0x27d4eb2fu);
     return sample_mix32(h ^ ((axis + 1u) * 0xc2b2ae3du));
 }
 
 // 32 bits -> [0, 1): the top 24 bits times 2^-24 (both exact in fp32).
-NAF_VS_HD float sample_unit(uint32_t bits) { return (float)(bits >> 8) * (1.0f / 16777216.0f); }
+NAF_HD float sample_unit(uint32_t bits) { return (float)(bits >> 8) * (1.0f / 16777216.0f); }
 
 // p_a = min(lo_a + r_a * (hi_a - lo_a), hi_a): one subtract, one multiply, one add, one minimum; lo <= p <= hi for lo <= hi.
-NAF_VS_HD void sample_draw(uint64_t seed, uint32_t step, uint32_t i, const float lo[3], const float hi[3], float p[3]) {
-#ifdef __HIPCC__
-#pragma unroll
-#endif
+NAF_HD void sample_draw(uint64_t seed, uint32_t step, uint32_t i, const float lo[3], const float hi[3], float p[3]) {
+    NAF_UNROLL
     for (uint32_t a = 0; a < 3u; ++a) {
         const float r = sample_unit(sample_hash(seed, step, i, a));
         const float e = hi[a] - lo[a];

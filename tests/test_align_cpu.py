@@ -2,25 +2,13 @@
 `reconstruct.align_operators` as array code on numpy arrays, the float64 outer loop on the end-to-end scans that the GPU test is
 measured against, and tools/align_host_check.cpp, which runs csrc/align_device.h under AddressSanitizer and UBSan as a process of its
 own.  No GPU."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
 import _align_oracle as O
+from _host_check import load, needs_compiler
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _driver():
-    spec = importlib.util.spec_from_file_location("align_host_check", os.path.join(REPO, "tools", "align_host_check.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-D = _driver()
+D = load("align")
 
 
 def _smooth(H, W, du=0.0, dv=0.0):
@@ -147,9 +135,6 @@ def test_the_float64_loop_recovers_the_planted_shifts(name):
     assert run["history"][-1]["flagged"] == 0
 
 
-needs_compiler = pytest.mark.skipif(D.compiler() is None, reason="no host C++ compiler found")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
     workdir = str(tmp_path_factory.mktemp("align_host_check"))
@@ -159,7 +144,7 @@ def program(tmp_path_factory):
 @needs_compiler
 @pytest.mark.parametrize("case", D.SCORE_CASES)
 def test_host_scores_and_peak_equal_the_oracle(program, case):
-    """Exit status 0 and nothing on stderr (`_run` raises otherwise); scores inside (terms + 1) 2^-53, peaks and flags the oracle's."""
+    """Exit status 0 and nothing on stderr (`host_check.run` raises otherwise); scores inside (terms + 1) 2^-53, peaks and flags the oracle's."""
     assert D.check_scores(O, *program, *case) <= 1.0
 
 

@@ -3,29 +3,17 @@ AddressSanitizer and UBSan and run as a process of its own, holds siddon_forward
 restatement of the walk, and tools/siddon_host_check.py holds their sums to the float64 oracles.  Here it runs on the hand-made ray
 sets of both oracles (ties, grazes, constant axes, zero components, NaN / Inf: each at most 32 rays, the smallest of either oracle
 among them) with the three value vectors; `python tools/siddon_host_check.py` runs the scan and random sets as well."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
+import _host_check
 import _siddon_oracle as S
 import _siddon_transpose_oracle as T
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _driver():
-    spec = importlib.util.spec_from_file_location("siddon_host_check", os.path.join(REPO, "tools", "siddon_host_check.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-D = _driver()
+D = _host_check.load("siddon")
 SMALL = [name for name, case in T.ray_sets().items() if len(case[3]) <= 32]
 
-pytestmark = pytest.mark.skipif(D.compiler() is None, reason="no host C++ compiler found")
+pytestmark = _host_check.needs_compiler
 
 
 @pytest.fixture(scope="module")

@@ -8,11 +8,11 @@ Grid: n_rays 0, every value 1 .. 3 100, 4 096, 65 536 and floor(2^31 / 192); n_s
 The forward under NAF_CFG_MLP_TWO_KERNELS: that flag keeps the kernel PAIR, whose forward is mlp16_forward_split_kernel (naf_hip.h;
 tests/test_hip_mlp16_reference.py forces the pair with it to hold that kernel to float64), so the split condition is the unflagged
 one.  Only NAF_CFG_BACKWARD_ONE_WAVE_PER_SIMD ("no mlp16_forward_split_kernel, no mlp16_train_kernel") turns the split off."""
-import importlib.util
 import os
 
 import pytest
 
+import _host_check
 import _mlp16_oracle as O
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,15 +21,8 @@ N_RAYS = list(range(0, 3101)) + [4096, 65536, (1 << 31) // 192]
 N_SAMPLES = (1, 2, 7, 15, 16, 17, 50, 63, 64, 65, 192, 200, 511, 512, 513, 1024, 1025)
 
 
-def _driver():
-    spec = importlib.util.spec_from_file_location("step_plan_host_check", os.path.join(REPO, "tools", "step_plan_host_check.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-D = _driver()
-pytestmark = pytest.mark.skipif(D.compiler() is None, reason="no host C++ compiler found")
+D = _host_check.load("step_plan")
+pytestmark = _host_check.needs_compiler
 
 
 @pytest.fixture(scope="module")

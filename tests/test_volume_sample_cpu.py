@@ -2,7 +2,6 @@
 properties, the per-point arithmetic of csrc/volume_sample_device.h on the CPU under AddressSanitizer and UBSan
 (tools/volume_sample_host_check.cpp, a process of its own), and the argument checks of `pretrain` and of `Trainer`'s
 `train.init_volume` keys, all of which raise before anything touches a device."""
-import importlib.util
 import os
 
 import numpy as np
@@ -10,19 +9,10 @@ import pytest
 import torch
 
 import _volume_sample_oracle as O
+from _host_check import load, needs_compiler
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _driver():
-    spec = importlib.util.spec_from_file_location("volume_sample_host_check", os.path.join(REPO, "tools", "volume_sample_host_check.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-D = _driver()
-needs_compiler = pytest.mark.skipif(D.compiler() is None, reason="no host C++ compiler found")
+D = load("volume_sample")
 
 
 # ---- the oracle's own properties ---------------------------------------------------------------------------------------------------
@@ -103,7 +93,7 @@ def test_host_check_offsets_are_64_bit(program):
 @pytest.mark.parametrize("dims", D.SHAPES)
 @pytest.mark.parametrize("exact", [True, False])
 def test_host_check_holds_the_arithmetic_to_float64(program, dims, exact):
-    """Exit status 0 and nothing on stderr (`_run` raises otherwise); NaN where a coordinate is NaN; everything else inside the
+    """Exit status 0 and nothing on stderr (`host_check.run` raises otherwise); NaN where a coordinate is NaN; everything else inside the
     bound; centres bit-equal at a power-of-two voxel size; the draw bit-equal to the oracle's and its targets to the sampler's."""
     exe, workdir = program
     assert (1, 4, 4) in D.SHAPES and (4, 1, 1) in D.SHAPES and (1, 1, 1) in D.SHAPES

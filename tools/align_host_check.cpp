@@ -8,37 +8,41 @@
 //   align_host_check peak N Rv Ru scores.f64 shifts.f32 flags.i32           align_peak on every table
 //   align_host_check shift N H W views.f32 shifts.f32 out.f32               align_axis / align_sample at every output pixel
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../neuralvolumetricreconstructionformedicalimages_amd/csrc/align_device.h"
+#include "host_check.h"
+
+using namespace host_check;
 
 namespace {
 
 template <typename T>
+std::vector<std::vector<T>> make(size_t n, size_t each) {
+    return std::vector<std::vector<T>>(n, std::vector<T>(each));                 // exactly `each` elements per view
+}
+
+// A file holds the views one after another; each goes into, or comes from, its own heap block.
+template <typename T>
 bool read_views(const char *path, std::vector<std::vector<T>> &views) {
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return false;
-    bool ok = true;
-    for (auto &v : views) ok = ok && (v.empty() || std::fread(v.data(), sizeof(T), v.size(), fp) == v.size());
-    std::fclose(fp);
-    return ok;
+    std::vector<T> file;
+    for (const auto &v : views) file.insert(file.end(), v.begin(), v.end());
+    if (!read_all(path, file)) return false;
+    size_t at = 0;
+    for (auto &v : views) {
+        v.assign(file.begin() + at, file.begin() + at + v.size());
+        at += v.size();
+    }
+    return true;
 }
 
 template <typename T>
 bool write_views(const char *path, const std::vector<std::vector<T>> &views) {
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return false;
-    bool ok = true;
-    for (const auto &v : views) ok = ok && (v.empty() || std::fwrite(v.data(), sizeof(T), v.size(), fp) == v.size());
-    return std::fclose(fp) == 0 && ok;
-}
-
-template <typename T>
-std::vector<std::vector<T>> make(size_t n, size_t each) {
-    return std::vector<std::vector<T>>(n, std::vector<T>(each));                 // exactly `each` elements per view
+    std::vector<T> file;
+    for (const auto &v : views) file.insert(file.end(), v.begin(), v.end());
+    return write_all(path, file);
 }
 
 }  // namespace
@@ -46,11 +50,11 @@ std::vector<std::vector<T>> make(size_t n, size_t each) {
 int main(int argc, char **argv) {
     if (argc == 11 && !std::strcmp(argv[1], "scores")) {
         const uint32_t N = std::atoi(argv[2]), H = std::atoi(argv[3]), W = std::atoi(argv[4]), Rv = std::atoi(argv[5]), Ru = std::atoi(argv[6]);
-        if (H == 0 || W == 0 || Rv > naf::kAlignMaxShift || Ru > naf::kAlignMaxShift || 2 * Rv >= H || 2 * Ru >= W) return 2;
+        if (H == 0 || W == 0 || Rv > naf::kAlignMaxShift || Ru > naf::kAlignMaxShift || 2 * Rv >= H || 2 * Ru >= W) return kBadArguments;
         const bool has_w = std::strcmp(argv[9], "-") != 0;
         auto b = make<float>(N, (size_t)H * W), p = make<float>(N, (size_t)H * W), w = make<float>(has_w ? N : 0, (size_t)H * W);
         auto out = make<double>(N, (size_t)(2 * Rv + 1) * (2 * Ru + 1));
-        if (!read_views(argv[7], b) || !read_views(argv[8], p) || (has_w && !read_views(argv[9], w))) return 3;
+        if (!read_views(argv[7], b) || !read_views(argv[8], p) || (has_w && !read_views(argv[9], w))) return kIoFailure;
         for (uint32_t n = 0; n < N; ++n)
             for (uint32_t j = 0; j <= 2 * Rv; ++j)
                 for (uint32_t i = 0; i <= 2 * Ru; ++i) {
@@ -62,35 +66,33 @@ int main(int argc, char **argv) {
                         }
                     out[n][(size_t)j * (2 * Ru + 1) + i] = sum;
                 }
-        return write_views(argv[10], out) ? 0 : 3;
+        return write_views(argv[10], out) ? 0 : kIoFailure;
     }
     if (argc == 8 && !std::strcmp(argv[1], "peak")) {
         const uint32_t N = std::atoi(argv[2]), Rv = std::atoi(argv[3]), Ru = std::atoi(argv[4]);
-        if (Rv > naf::kAlignMaxShift || Ru > naf::kAlignMaxShift) return 2;
+        if (Rv > naf::kAlignMaxShift || Ru > naf::kAlignMaxShift) return kBadArguments;
         auto S = make<double>(N, (size_t)(2 * Rv + 1) * (2 * Ru + 1));
         auto shifts = make<float>(N, 2);
         auto flags = make<int32_t>(N, 1);
-        if (!read_views(argv[5], S)) return 3;
+        if (!read_views(argv[5], S)) return kIoFailure;
         for (uint32_t n = 0; n < N; ++n) {
             int f = 0;
             naf::align_peak(S[n].data(), Rv, Ru, shifts[n].data(), &f);
             flags[n][0] = f;
         }
-        return write_views(argv[6], shifts) && write_views(argv[7], flags) ? 0 : 3;
+        return write_views(argv[6], shifts) && write_views(argv[7], flags) ? 0 : kIoFailure;
     }
     if (argc == 8 && !std::strcmp(argv[1], "shift")) {
         const uint32_t N = std::atoi(argv[2]), H = std::atoi(argv[3]), W = std::atoi(argv[4]);
-        if (H == 0 || W == 0) return 2;
+        if (H == 0 || W == 0) return kBadArguments;
         auto views = make<float>(N, (size_t)H * W), out = make<float>(N, (size_t)H * W), shifts = make<float>(N, 2);
-        if (!read_views(argv[5], views) || !read_views(argv[6], shifts)) return 3;
+        if (!read_views(argv[5], views) || !read_views(argv[6], shifts)) return kIoFailure;
         for (uint32_t n = 0; n < N; ++n) {
             const naf::AlignAxis au = naf::align_axis(shifts[n][0], W), av = naf::align_axis(shifts[n][1], H);
             for (uint32_t r = 0; r < H; ++r)
                 for (uint32_t c = 0; c < W; ++c) out[n][(size_t)r * W + c] = naf::align_sample(views[n].data(), H, W, r, c, av, au);
         }
-        return write_views(argv[7], out) ? 0 : 3;
+        return write_views(argv[7], out) ? 0 : kIoFailure;
     }
-    std::fprintf(stderr, "usage: %s scores N H W Rv Ru b p w|- out | peak N Rv Ru scores shifts flags | shift N H W views shifts out\n",
-                 argv[0]);
-    return 2;
+    return usage(argv[0], "scores N H W Rv Ru b p w|- out | peak N Rv Ru scores shifts flags | shift N H W views shifts out");
 }

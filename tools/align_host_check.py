@@ -12,19 +12,16 @@ The program is never loaded into Python.  No GPU.
 
     python tools/align_host_check.py
 """
+import functools
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.append(os.path.dirname(os.path.abspath(__file__)))          # tools/, for a caller that loads this file by its path
+import host_check  # noqa: E402
 
-FLAGS = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall"]
 # (H, W, Rv, Ru): the GPU tests' shapes, one pixel, one row, one column, no search on an axis, the largest window
 SCORE_CASES = ((20, 24, 2, 3), (1, 1, 0, 0), (1, 9, 0, 4), (7, 1, 3, 0), (5, 6, 0, 2), (5, 6, 2, 0), (33, 35, 16, 16), (40, 70, 16, 1))
 SHIFT_SHAPES = ((1, 1), (1, 5), (6, 1), (2, 2), (9, 11))
@@ -33,52 +30,25 @@ SHIFTS = ((0.0, 0.0), (1.0, -2.0), (0.5, 0.25), (-0.3, 2.7), (-2.0 ** -30, 2.0 *
           (NAN, 0.0), (0.0, NAN), (3e38, -3e38), (-12.0, 13.0))
 
 
-def compiler():
-    return shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-
-
-def build(workdir):
-    cxx = compiler()
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "align_host_check")
-    subprocess.check_call([cxx, *FLAGS, os.path.join(REPO, "tools", "align_host_check.cpp"), "-o", exe])
-    return exe
-
-
-def _run(cmd):
-    done = subprocess.run(cmd, capture_output=True, text=True)
-    if done.returncode != 0 or done.stderr.strip():
-        raise RuntimeError(f"exit {done.returncode}: {done.stdout}\nsanitizer output:\n{done.stderr}")
-
-
-def _put(workdir, name, a, dtype):
-    path = os.path.join(workdir, name)
-    np.ascontiguousarray(a, dtype=dtype).tofile(path)
-    return path
+compiler = host_check.compiler                                       # such a caller asks the driver, not host_check
+build = functools.partial(host_check.build, "align")
 
 
 def scores(exe, workdir, b, p, Rv, Ru, w=None):
-    N, H, W = b.shape
-    out = os.path.join(workdir, "scores.f64")
-    _run([exe, "scores", str(N), str(H), str(W), str(Rv), str(Ru), _put(workdir, "b.f32", b, np.float32),
-          _put(workdir, "p.f32", p, np.float32), "-" if w is None else _put(workdir, "w.f32", w, np.float32), out])
-    return np.fromfile(out, dtype=np.float64).reshape(N, 2 * Rv + 1, 2 * Ru + 1)
+    shape = (len(b), 2 * Rv + 1, 2 * Ru + 1)
+    (out,), _ = host_check.run(exe, ["scores", *b.shape, Rv, Ru], [b, p, w], [(np.float64, int(np.prod(shape)))])
+    return out.reshape(shape)
 
 
 def peak(exe, workdir, S):
     N, nv, nu = S.shape
-    paths = [os.path.join(workdir, name) for name in ("peak_shifts.f32", "peak_flags.i32")]
-    _run([exe, "peak", str(N), str(nv // 2), str(nu // 2), _put(workdir, "peak_scores.f64", S, np.float64), *paths])
-    return np.fromfile(paths[0], dtype=np.float32).reshape(N, 2), np.fromfile(paths[1], dtype=np.int32)
+    (shifts, flags), _ = host_check.run(exe, ["peak", N, nv // 2, nu // 2], [(S, np.float64)], [(np.float32, 2 * N), (np.int32, N)])
+    return shifts.reshape(N, 2), flags
 
 
 def shift(exe, workdir, views, shifts):
-    N, H, W = views.shape
-    out = os.path.join(workdir, "shifted.f32")
-    _run([exe, "shift", str(N), str(H), str(W), _put(workdir, "views.f32", views, np.float32),
-          _put(workdir, "shifts.f32", shifts, np.float32), out])
-    return np.fromfile(out, dtype=np.float32).reshape(N, H, W)
+    (out,), _ = host_check.run(exe, ["shift", *views.shape], [views, shifts], [(np.float32, views.size)])
+    return out.reshape(views.shape)
 
 
 def check_scores(O, exe, workdir, H, W, Rv, Ru, seed=0):

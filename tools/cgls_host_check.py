@@ -7,58 +7,34 @@ a breakdown or a stop leaves r, x and p bit for bit.  The program is never loade
 
     python tools/cgls_host_check.py
 """
-import os
-import shutil
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+import host_check
 
 
-def build(workdir):
-    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "cgls_host_check")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-Wall", os.path.join(REPO, "tools", "cgls_host_check.cpp"), "-o", exe])
-    return exe
-
-
-def run(exe, workdir, args, inputs, outputs):
-    """`inputs`: float32 arrays written to files and passed after `args`; `outputs`: (dtype, count) of the files the program writes."""
-    paths = []
-    for i, a in enumerate(inputs):
-        paths.append(os.path.join(workdir, f"in{i}.f32"))
-        np.ascontiguousarray(a, dtype=np.float32).tofile(paths[-1])
-    outs = [os.path.join(workdir, f"out{i}.bin") for i in range(len(outputs))]
-    done = subprocess.run([exe, *[str(a) for a in args], *paths, *outs], check=True, capture_output=True, text=True)
-    if done.stderr.strip():
-        raise RuntimeError(f"sanitizer output:\n{done.stderr}")
-    return [np.fromfile(path, dtype=dtype, count=count) for path, (dtype, count) in zip(outs, outputs)]
+def run(exe, args, inputs, outputs):
+    """The arrays of host_check.run: the program prints nothing."""
+    return host_check.run(exe, args, inputs, outputs)[0]
 
 
 def main():
     import _cgls_oracle as C
     f32, f64 = np.float32, np.float64
     with tempfile.TemporaryDirectory() as workdir:
-        exe = build(workdir)
+        exe = host_check.build("cgls", workdir)
         worst = {"wdot": 0.0, "residual r": 0.0, "residual y": 0.0, "direction x": 0.0, "direction p": 0.0}
         for n in C.SIZES:
             r, q, w, x, p, s = C.step_inputs(n)
             for has_w in (1, 0):
                 weights = w if has_w else None
-                total, = run(exe, workdir, ["wdot", n, has_w], [r, w], [(f64, 1)])
+                total, = run(exe, ["wdot", n, has_w], [r, w], [(f64, 1)])
                 want = C.wsum(r, weights)
                 assert abs(total[0] - want) <= C.wsum_bound(n, want), (n, has_w)
                 worst["wdot"] = max(worst["wdot"], abs(total[0] - want) / max(C.wsum_bound(n, want), 1e-300))
                 for gamma, delta, _ in C.LIVE_SCALARS:
-                    r2, y, out = run(exe, workdir, ["residual", n, has_w, repr(gamma), repr(delta), 0], [r, q, w],
+                    r2, y, out = run(exe, ["residual", n, has_w, repr(gamma), repr(delta), 0], [r, q, w],
                                      [(f32, n), (f32, n), (f64, 2)])
                     want_r, want_y = C.residual_step(r, q, weights, gamma, delta)
                     bound_r, bound_y = C.residual_bounds(q, weights, gamma, delta, r2, y)
@@ -70,11 +46,11 @@ def main():
                 spoiled = q.copy()
                 spoiled[0] = np.inf
                 for gamma, delta, stopped in dead:
-                    r2, y, out = run(exe, workdir, ["residual", n, has_w, repr(gamma), repr(delta), stopped], [r, spoiled, w],
+                    r2, y, out = run(exe, ["residual", n, has_w, repr(gamma), repr(delta), stopped], [r, spoiled, w],
                                      [(f32, n), (f32, n), (f64, 2)])
                     assert out[1] == 0.0 and np.array_equal(r2, r) and np.array_equal(y, w * r if has_w else r), (n, gamma, delta)
             for gamma, delta, gamma_next in C.LIVE_SCALARS:
-                x2, p2 = run(exe, workdir, ["direction", n, repr(gamma), repr(delta), repr(gamma_next), 0], [x, p, s], [(f32, n)] * 2)
+                x2, p2 = run(exe, ["direction", n, repr(gamma), repr(delta), repr(gamma_next), 0], [x, p, s], [(f32, n)] * 2)
                 want_x, want_p = C.direction_step(x, p, s, gamma, delta, gamma_next)
                 bound_x, bound_p = C.fma_bound(gamma / delta, p, x2), C.fma_bound(gamma_next / gamma, p, p2)
                 assert np.all(np.abs(x2 - want_x) <= bound_x) and np.all(np.abs(p2 - want_p) <= bound_p), (n, gamma)
@@ -83,7 +59,7 @@ def main():
             spoiled = s.copy()
             spoiled[n // 2] = np.nan
             for gamma, delta, stopped in [(g, d, 0) for g, d, _ in C.DEAD_SCALARS] + [(*C.LIVE_SCALARS[0][:2], 3)]:
-                x2, p2 = run(exe, workdir, ["direction", n, repr(gamma), repr(delta), 1.5, stopped], [x, p, spoiled], [(f32, n)] * 2)
+                x2, p2 = run(exe, ["direction", n, repr(gamma), repr(delta), 1.5, stopped], [x, p, spoiled], [(f32, n)] * 2)
                 assert np.array_equal(x2, x) and np.array_equal(p2, p), (n, gamma, delta)
             print(f"n {n}: every bound holds", flush=True)
         print("no sanitizer report; largest |. - float64| / bound: " + ", ".join(f"{k} {v:.3e}" for k, v in worst.items()))

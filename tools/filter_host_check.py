@@ -10,53 +10,27 @@ nothing of it is loaded into Python.  No GPU.
 
     python tools/filter_host_check.py
 """
-import os
-import shutil
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+import host_check
 
 
-def build(workdir):
-    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "filter_host_check")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-Wall", os.path.join(REPO, "tools", "filter_host_check.cpp"), "-o", exe])
-    return exe
-
-
-def run(exe, workdir, x, taps, pre, post, scale, col=None):
-    paths = []
-    for name, a in (("in", x), ("taps", taps), ("pre", pre), ("post", post), ("scale", scale), ("col", col)):
-        if a is None:
-            paths.append("-")
-            continue
-        paths.append(os.path.join(workdir, name + ".f32"))
-        np.ascontiguousarray(a, dtype=np.float32).tofile(paths[-1])
-    dst = os.path.join(workdir, "out.f32")
-    out = subprocess.run([exe, *[str(v) for v in x.shape], *paths, dst], check=True, capture_output=True, text=True)
-    if out.stderr.strip():
-        raise RuntimeError(f"sanitizer output:\n{out.stderr}")
-    return np.fromfile(dst, dtype=np.float32).reshape(x.shape)
+def run(exe, x, taps, pre, post, scale, col=None):
+    (out,), _ = host_check.run(exe, x.shape, [x, taps, pre, post, scale, col], [(np.float32, x.size)])
+    return out.reshape(x.shape)
 
 
 def main():
     import _filter_oracle as F
     worst = 0.0
     with tempfile.TemporaryDirectory() as workdir:
-        exe = build(workdir)
+        exe = host_check.build("filter", workdir)
         for shape in F.SHAPES:
             x, taps, pre, post, scale = F.filter_inputs(shape)
             for name, w in (("plain", (None, None, None)), ("weighted", (pre, post, scale))):
-                got = run(exe, workdir, x, taps, *w).astype(np.float64)
+                got = run(exe, x, taps, *w).astype(np.float64)
                 want, bound = F.filter_rows(x, taps, *w), F.filter_bound(x, taps, *w)
                 err = np.abs(got - want)
                 ratio = float((err / np.maximum(bound, np.finfo(np.float64).tiny)).max())
@@ -66,7 +40,7 @@ def main():
             for k0 in sorted({0, shape[2] // 2, shape[2] - 1}):
                 imp = np.zeros(shape, dtype=np.float32)
                 imp[..., k0] = 1.0
-                got = run(exe, workdir, imp, taps, None, None, None)
+                got = run(exe, imp, taps, None, None, None)
                 assert got[0, 0].tobytes() == taps[np.abs(np.arange(shape[2]) - k0)].tobytes(), (shape, k0)
         print(f"largest error over all cases: {worst:.4f} of the bound; an impulse returns the taps bit for bit; no sanitizer report")
         import _short_scan_oracle as S
@@ -74,15 +48,15 @@ def main():
         for shape in S.SHAPES:
             x, taps, pre, post, scale, col = S.filter_inputs(shape)
             for name, w in (("col", (None, None, None, col)), ("all", (pre, post, scale, col))):
-                got = run(exe, workdir, x, taps, *w).astype(np.float64)
+                got = run(exe, x, taps, *w).astype(np.float64)
                 want, bound = S.filter_rows(x, taps, *w), S.filter_bound(x, taps, *w)
                 err = np.abs(got - want)
                 ratio = float((err / np.maximum(bound, np.finfo(np.float64).tiny)).max())
                 print(f"{shape} {name:8s}: max |out - float64| {err.max():.3e}  worst ratio to the bound {ratio:.4f}")
                 assert np.all(err <= bound), (shape, name)
                 worst = max(worst, ratio)
-            ones = run(exe, workdir, x, taps, pre, post, scale, np.ones_like(col))
-            assert ones.tobytes() == run(exe, workdir, x, taps, pre, post, scale).tobytes(), shape
+            ones = run(exe, x, taps, pre, post, scale, np.ones_like(col))
+            assert ones.tobytes() == run(exe, x, taps, pre, post, scale).tobytes(), shape
         print(f"with col, largest error over all cases: {worst:.4f} of the bound; a col of ones changes no bit; no sanitizer report")
 
 

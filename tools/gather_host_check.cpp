@@ -15,45 +15,41 @@
 #include <vector>
 
 #include "../neuralvolumetricreconstructionformedicalimages_amd/csrc/backproject_gather_device.h"
+#include "host_check.h"
+
+using namespace host_check;
 
 namespace {
 
+// A whole file, however long (the number of triples is not on the command line); main checks the sizes it knows.
 template <class T>
-bool read_all(const char *path, std::vector<T> &v) {
+bool read_file(const char *path, std::vector<T> &v) {
     FILE *fp = std::fopen(path, "rb");
     if (!fp) return false;
     std::fseek(fp, 0, SEEK_END);
     const long bytes = std::ftell(fp);
-    std::fseek(fp, 0, SEEK_SET);
-    if (bytes < 0 || bytes % (long)sizeof(T)) {
-        std::fclose(fp);
-        return false;
-    }
-    v.resize((size_t)bytes / sizeof(T));
-    const size_t got = std::fread(v.data(), sizeof(T), v.size(), fp);
     std::fclose(fp);
-    return got == v.size();
+    if (bytes < 0 || bytes % (long)sizeof(T)) return false;
+    v.resize((size_t)bytes / sizeof(T));
+    return read_all(path, v);
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
-    if (argc != 14) {
-        std::fprintf(stderr, "usage: %s n1 n2 n3 W H n_views parallel grid det poses spans triples out\n", argv[0]);
-        return 2;
-    }
+    if (argc != 14) return usage(argv[0], "n1 n2 n3 W H n_views parallel grid det poses spans triples out");
     naf::GatherGrid grid;
     for (int a = 0; a < 3; ++a) grid.n[a] = (uint32_t)std::atoi(argv[1 + a]);
     const uint32_t W = (uint32_t)std::atoi(argv[4]), H = (uint32_t)std::atoi(argv[5]), N = (uint32_t)std::atoi(argv[6]);
     const int parallel = std::atoi(argv[7]);
     std::vector<float> g, d, poses, spans;
     std::vector<int64_t> triples;
-    if (!read_all(argv[8], g) || !read_all(argv[9], d) || !read_all(argv[10], poses) || !read_all(argv[11], spans) ||
-        !read_all(argv[12], triples))
-        return 3;
+    if (!read_file(argv[8], g) || !read_file(argv[9], d) || !read_file(argv[10], poses) || !read_file(argv[11], spans) ||
+        !read_file(argv[12], triples))
+        return kIoFailure;
     const size_t per_view = (size_t)W * H, n_voxels = (size_t)grid.n[0] * grid.n[1] * grid.n[2];
     if (g.size() != 6 || d.size() != 5 || poses.size() != (size_t)N * 12 || spans.size() != per_view * N * 9 || triples.size() % 3)
-        return 3;
+        return kIoFailure;
     for (int a = 0; a < 3; ++a) {
         grid.half[a] = g.at(a);
         grid.d[a] = g.at(3 + a);
@@ -91,7 +87,7 @@ int main(int argc, char **argv) {
     std::vector<int64_t> out(triples.size() / 3 + 2);
     for (size_t t = 0; t < triples.size() / 3; ++t) {
         const int64_t ray = triples.at(3 * t), k = triples.at(3 * t + 1), voxel = triples.at(3 * t + 2);
-        if (ray < 0 || (size_t)ray >= per_view * N || voxel < 0 || (size_t)voxel >= n_voxels) return 3;
+        if (ray < 0 || (size_t)ray >= per_view * N || voxel < 0 || (size_t)voxel >= n_voxels) return kIoFailure;
         const size_t at = (size_t)ray * n_voxels + (size_t)voxel;
         out.at(t) = k >= k_lo.at(at) && k <= k_hi.at(at);
     }
@@ -121,8 +117,5 @@ int main(int argc, char **argv) {
                                 if (naf::gather_corner_weight(vv, cv, next, w) != want) return 5;
                             }
     }
-    FILE *fp = std::fopen(argv[13], "wb");
-    if (!fp) return 3;
-    const size_t put = std::fwrite(out.data(), sizeof(int64_t), out.size(), fp);
-    return std::fclose(fp) == 0 && put == out.size() ? 0 : 3;
+    return write_all(argv[13], out) ? 0 : kIoFailure;
 }

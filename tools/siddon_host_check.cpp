@@ -29,23 +29,11 @@
 #include <vector>
 
 #include "../neuralvolumetricreconstructionformedicalimages_amd/csrc/siddon_device.h"
+#include "host_check.h"
+
+using namespace host_check;
 
 namespace {
-
-bool read_all(const char *path, float *v, size_t n) {
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return false;
-    const size_t got = std::fread(v, sizeof(float), n, fp);
-    std::fclose(fp);
-    return got == n;
-}
-
-bool write_all(const char *path, const float *v, size_t n) {
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return false;
-    const size_t put = std::fwrite(v, sizeof(float), n, fp);
-    return std::fclose(fp) == 0 && put == n;
-}
 
 struct Term {
     uint64_t offset;
@@ -107,23 +95,19 @@ struct PairDeposit {
 }  // namespace
 
 int main(int argc, char **argv) {
-    if (argc != 16) {
-        std::fprintf(stderr, "usage: siddon_host_check n1 n2 n3 dv1 dv2 dv3 n_rays volume.f32 start.f32 rays.f32 values.f32 acc.f32 "
-                             "value_out.f32 num_out.f32 den_out.f32\n");
-        return 2;
-    }
+    if (argc != 16)
+        return usage(argv[0], "n1 n2 n3 dv1 dv2 dv3 n_rays volume.f32 start.f32 rays.f32 values.f32 acc.f32 value_out.f32 num_out.f32 "
+                              "den_out.f32");
     const uint32_t n1 = (uint32_t)std::atoi(argv[1]), n2 = (uint32_t)std::atoi(argv[2]), n3 = (uint32_t)std::atoi(argv[3]);
     const float dvoxel[3] = {std::strtof(argv[4], nullptr), std::strtof(argv[5], nullptr), std::strtof(argv[6], nullptr)};
     const size_t n_rays = (size_t)std::atoll(argv[7]), n_vox = (size_t)n1 * n2 * n3;
-    if (n_vox == 0 || n_rays == 0) return 2;
+    if (n_vox == 0 || n_rays == 0) return kBadArguments;
     std::unique_ptr<float[]> volume(new float[n_vox]), ones(new float[n_vox]), value_out(new float[n_vox]);
     std::unique_ptr<float[]> num(new float[n_vox]()), den(new float[n_vox]()), num_alone(new float[n_vox]());
     std::unique_ptr<float[]> rays(new float[n_rays * 8]), values(new float[n_rays]), acc_out(new float[n_rays]);
     if (!read_all(argv[8], volume.get(), n_vox) || !read_all(argv[9], value_out.get(), n_vox) ||
-        !read_all(argv[10], rays.get(), n_rays * 8) || !read_all(argv[11], values.get(), n_rays)) {
-        std::fprintf(stderr, "siddon_host_check: short read\n");
-        return 2;
-    }
+        !read_all(argv[10], rays.get(), n_rays * 8) || !read_all(argv[11], values.get(), n_rays))
+        return kIoFailure;
     for (size_t i = 0; i < n_vox; ++i) ones[i] = 1.0f;
     naf::SiddonGrid grid;
     naf::siddon_grid(n1, n2, n3, dvoxel, &grid);
@@ -172,7 +156,7 @@ int main(int argc, char **argv) {
     if (std::memcmp(num.get(), num_alone.get(), n_vox * sizeof(float)) != 0) ++mismatches;
     if (!write_all(argv[12], acc_out.get(), n_rays) || !write_all(argv[13], value_out.get(), n_vox) ||
         !write_all(argv[14], num.get(), n_vox) || !write_all(argv[15], den.get(), n_vox))
-        return 2;
+        return kIoFailure;
     std::printf("value %zu num %zu den %zu mismatches %zu\n", value_total, num_total, den_total, mismatches);
     return mismatches ? 1 : 0;
 }

@@ -14,51 +14,31 @@ The program is never loaded into Python.  No GPU.
 
     python tools/siddon_host_check.py
 """
+import functools
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.append(os.path.dirname(os.path.abspath(__file__)))          # tools/, for a caller that loads this file by its path
+import host_check  # noqa: E402
 
-FLAGS = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall"]
-
-
-def compiler():
-    return shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-
-
-def build(workdir):
-    cxx = compiler()
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "siddon_host_check")
-    subprocess.check_call([cxx, *FLAGS, os.path.join(REPO, "tools", "siddon_host_check.cpp"), "-o", exe])
-    return exe
+compiler = host_check.compiler                                       # such a caller asks the driver, not host_check
+build = functools.partial(host_check.build, "siddon")
 
 
 def walk(exe, workdir, volume, dvoxel, rays, y=None, start=None):
     """Both walks over `rays` [n, 8]: the forward on `volume`, the value deposit of `y` (default zeros) into `start` (default zeros),
     the pair deposit into zeroed num and den -> dict of acc [n], value, num, den (flat volumes) and the counts of terms sent to
     each.  A sanitizer report or a mismatch inside the program is an error."""
-    names = ("volume", "start", "rays", "values", "acc", "value_out", "num_out", "den_out")
-    paths = [os.path.join(workdir, name + ".f32") for name in names]
     y = np.zeros(len(rays)) if y is None else y
     start = np.zeros(volume.shape) if start is None else start
-    for path, a in zip(paths, (volume, start, rays, y)):
-        np.ascontiguousarray(a, dtype=np.float32).tofile(path)
-    done = subprocess.run([exe, *[str(n) for n in volume.shape], *[repr(float(np.float32(v))) for v in dvoxel], str(len(rays)), *paths],
-                          capture_output=True, text=True)
-    if done.returncode != 0 or done.stderr.strip():
-        raise RuntimeError(f"exit {done.returncode}: {done.stdout}\nsanitizer output:\n{done.stderr}")
-    words = done.stdout.split()
-    assert words[0::2] == ["value", "num", "den", "mismatches"] and int(words[7]) == 0, done.stdout
-    out = {name: np.fromfile(path, dtype=np.float32) for name, path in zip(("acc", "value", "num", "den"), paths[4:])}
+    arrays, stdout = host_check.run(exe, [*volume.shape, *[repr(float(np.float32(v))) for v in dvoxel], len(rays)],
+                                    [volume, start, rays, y], [(np.float32, len(rays))] + [(np.float32, volume.size)] * 3)
+    words = stdout.split()
+    assert words[0::2] == ["value", "num", "den", "mismatches"] and int(words[7]) == 0, stdout
+    out = dict(zip(("acc", "value", "num", "den"), arrays))
     out.update(n_value=int(words[1]), n_num=int(words[3]), n_den=int(words[5]))
     return out
 

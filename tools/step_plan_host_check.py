@@ -7,30 +7,19 @@ loaded into Python.  No GPU.
     python tools/step_plan_host_check.py [flags n_rays n_samples]
 """
 import collections
+import functools
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall"]
+sys.path.append(os.path.dirname(os.path.abspath(__file__)))          # tools/, for a caller that loads this file by its path
+import host_check  # noqa: E402
 
 Caps = collections.namedtuple("Caps", "forward forward_split backward backward16 train_max_rays max_samples_lds")
 Plan = collections.namedtuple("Plan", "parts train_waves splits split_grid forward_grid16 forward_grid32 slabs16 slabs32 train_grid")
 
-
-def compiler():
-    return shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-
-
-def build(workdir, defines=()):
-    cxx = compiler()
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "step_plan_host_check")
-    subprocess.check_call([cxx, *FLAGS, *defines, os.path.join(REPO, "tools", "step_plan_host_check.cpp"), "-o", exe])
-    return exe
+compiler = host_check.compiler                                       # such a caller asks the driver, not host_check
+build = functools.partial(host_check.build, "step_plan")
 
 
 def plan(exe, workdir, cases):
@@ -38,10 +27,7 @@ def plan(exe, workdir, cases):
     path = os.path.join(workdir, "cases.txt")
     with open(path, "w") as f:
         f.write("".join(f"{a} {b} {c}\n" for a, b, c in cases))
-    done = subprocess.run([exe, path], capture_output=True, text=True)
-    if done.returncode != 0 or done.stderr.strip():
-        raise RuntimeError(f"exit {done.returncode}\nsanitizer output:\n{done.stderr}")
-    lines = done.stdout.splitlines()
+    lines = host_check.run(exe, [path])[1].splitlines()
     head = lines[0].split()
     assert head[0] == "caps" and len(lines) == len(cases) + 1, (head, len(lines), len(cases))
     return Caps(*map(int, head[1:])), [Plan(*map(int, line.split())) for line in lines[1:]]

@@ -6,49 +6,28 @@ tests' bounds are 4 x these figures (tests/test_hip_tv.py)
 
     python tools/tv_host_check.py
 """
-import os
-import shutil
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+import host_check
 
 
-def build(workdir):
-    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "tv_host_check")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-Wall", os.path.join(REPO, "tools", "tv_host_check.cpp"), "-o", exe])
-    return exe
-
-
-def run(exe, workdir, args, volume):
-    src, dst = os.path.join(workdir, "in.f32"), os.path.join(workdir, "out.f32")
-    np.ascontiguousarray(volume, dtype=np.float32).tofile(src)
-    out = subprocess.run([exe, *[str(a) for a in args], src, dst], check=True, capture_output=True, text=True)
-    if out.stderr.strip():
-        raise RuntimeError(f"sanitizer output:\n{out.stderr}")
-    sums = [float(v) for v in out.stdout.split()]
-    return np.fromfile(dst, dtype=np.float32).reshape(volume.shape), sums
+def run(exe, args, volume):
+    (out,), stdout = host_check.run(exe, args, [volume], [(np.float32, volume.size)])
+    return out.reshape(volume.shape), [float(v) for v in stdout.split()]
 
 
 def main():
     import _tv_oracle as T
     with tempfile.TemporaryDirectory() as workdir:
-        exe = build(workdir)
+        exe = host_check.build("tv", workdir)
         worst_g = worst_tv = worst_g2 = 0.0
         for shape in T.SHAPES + T.GPU_SHAPES:
             for kind in T.KINDS:
                 for eps in T.EPS:
                     x = T.volume(kind, shape)
-                    g, (tv, g2) = run(exe, workdir, ["gradient", *shape, repr(eps)], x)
+                    g, (tv, g2) = run(exe, ["gradient", *shape, repr(eps)], x)
                     want = T.gradient(x, eps)
                     err = float(np.abs(g - want).max())
                     zero = T.constant_neighbourhood(x)
@@ -63,7 +42,7 @@ def main():
               f"largest |sum g^2 - oracle| / N {worst_g2:.3e}")
         clean, noisy = T.noisy_phantom()
         for eps in T.EPS:
-            got, (tv, g2) = run(exe, workdir, ["descent", *noisy.shape, repr(eps), repr(T.DESCENT_STEP), T.DESCENT_STEPS], noisy)
+            got, (tv, g2) = run(exe, ["descent", *noisy.shape, repr(eps), repr(T.DESCENT_STEP), T.DESCENT_STEPS], noisy)
             want, tv_want, norm_want = T.descent(noisy, T.DESCENT_STEP, T.DESCENT_STEPS, eps)
             print(f"descent, {T.DESCENT_STEPS} steps of {T.DESCENT_STEP} from the noisy 32^3 phantom, eps {eps:g}: "
                   f"max|f - oracle| {np.abs(got - want).max():.3e}  TV before the last step {tv:.6f} vs {tv_want:.6f} "

@@ -6,12 +6,14 @@
 //   tvprox_host_check step   n1 n2 n3 lambda momentum nonneg b.f32 r.f32 p_old.f32 p.f32 r_next.f32    one dual iteration
 //   tvprox_host_check primal n1 n2 n3 lambda nonneg b.f32 p.f32 x.f32                                  x = P_C(b - lambda D^T p)
 #include <cstdint>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../neuralvolumetricreconstructionformedicalimages_amd/csrc/tvprox_device.h"
+#include "host_check.h"
+
+using namespace host_check;
 
 namespace {
 
@@ -65,34 +67,16 @@ void step(const Dims &d, const std::vector<float> &b, const std::vector<float> &
             }
 }
 
-bool read_all(const char *path, std::vector<float> &v) {
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return false;
-    const size_t got = std::fread(v.data(), sizeof(float), v.size(), fp);
-    std::fclose(fp);
-    return got == v.size();
-}
-
-bool write_all(const char *path, const std::vector<float> &v) {
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return false;
-    const size_t put = std::fwrite(v.data(), sizeof(float), v.size(), fp);
-    return std::fclose(fp) == 0 && put == v.size();
-}
-
 }  // namespace
 
 int main(int argc, char **argv) {
     const bool is_step = argc == 13 && !std::strcmp(argv[1], "step");
     const bool is_primal = argc == 10 && !std::strcmp(argv[1], "primal");
-    if (!is_step && !is_primal) {
-        std::fprintf(stderr, "usage: %s step n1 n2 n3 lambda momentum nonneg b r p_old p r_next | primal n1 n2 n3 lambda nonneg b p x\n",
-                     argv[0]);
-        return 2;
-    }
+    if (!is_step && !is_primal)
+        return usage(argv[0], "step n1 n2 n3 lambda momentum nonneg b r p_old p r_next | primal n1 n2 n3 lambda nonneg b p x");
     Dims d;
     for (int a = 0; a < 3; ++a) d.n[a] = (uint32_t)std::atoi(argv[2 + a]);
-    if (d.n[0] == 0 || d.n[1] == 0 || d.n[2] == 0) return 2;
+    if (d.n[0] == 0 || d.n[1] == 0 || d.n[2] == 0) return kBadArguments;
     d.stride[0] = (uint64_t)d.n[1] * d.n[2];
     d.stride[1] = d.n[2];
     d.stride[2] = 1;
@@ -103,15 +87,15 @@ int main(int argc, char **argv) {
         const float momentum = (float)std::atof(argv[6]);
         const bool nonneg = std::atoi(argv[7]) != 0;
         std::vector<float> r(3 * d.volume), r_next(3 * d.volume);
-        if (!read_all(argv[8], b) || !read_all(argv[9], r) || !read_all(argv[10], p)) return 3;
+        if (!read_all(argv[8], b) || !read_all(argv[9], r) || !read_all(argv[10], p)) return kIoFailure;
         step(d, b, r, p, lambda, momentum, nonneg, r_next);
-        if (!write_all(argv[11], p) || !write_all(argv[12], r_next)) return 3;
+        if (!write_all(argv[11], p) || !write_all(argv[12], r_next)) return kIoFailure;
     } else {
         const bool nonneg = std::atoi(argv[6]) != 0;
         std::vector<float> x(d.volume);
-        if (!read_all(argv[7], b) || !read_all(argv[8], p)) return 3;
+        if (!read_all(argv[7], b) || !read_all(argv[8], p)) return kIoFailure;
         primal(d, b, p, lambda, nonneg, x);
-        if (!write_all(argv[9], x)) return 3;
+        if (!write_all(argv[9], x)) return kIoFailure;
     }
     return 0;
 }

@@ -7,46 +7,23 @@ come from (4 x those figures; tests/test_hip_tvprox.py).  
 
     python tools/tvprox_host_check.py
 """
-import os
-import shutil
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+import host_check
 
 
-def build(workdir):
-    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "tvprox_host_check")
-    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-Wall", os.path.join(REPO, "tools", "tvprox_host_check.cpp"), "-o", exe])
-    return exe
-
-
-def run(exe, workdir, args, inputs, outputs):
+def run(exe, args, inputs, outputs):
     """`inputs`: arrays written to files and passed after `args`; `outputs`: shapes of the float32 files the program writes."""
-    paths = []
-    for i, a in enumerate(inputs):
-        paths.append(os.path.join(workdir, f"in{i}.f32"))
-        np.ascontiguousarray(a, dtype=np.float32).tofile(paths[-1])
-    outs = [os.path.join(workdir, f"out{i}.f32") for i in range(len(outputs))]
-    done = subprocess.run([exe, *[str(a) for a in args], *paths, *outs], check=True, capture_output=True, text=True)
-    if done.stderr.strip():
-        raise RuntimeError(f"sanitizer output:\n{done.stderr}")
-    return [np.fromfile(path, dtype=np.float32).reshape(shape) for path, shape in zip(outs, outputs)]
+    arrays, _ = host_check.run(exe, args, inputs, [(np.float32, int(np.prod(shape))) for shape in outputs])
+    return [a.reshape(shape) for a, shape in zip(arrays, outputs)]
 
 
 def main():
     import _tvprox_oracle as T
     with tempfile.TemporaryDirectory() as workdir:
-        exe = build(workdir)
+        exe = host_check.build("tvprox", workdir)
         worst = {"host step": 0.0, "oracle f32 step": 0.0, "host primal": 0.0, "oracle f32 primal": 0.0}
         for shape in T.STEP_SHAPES:
             for lam in T.STEP_LAMBDAS:
@@ -54,7 +31,7 @@ def main():
                     b, r, p_old = T.step_inputs(shape)
                     want_p, want_r = T.step(b, r, p_old, lam, T.STEP_MOMENTUM, nonneg)
                     own_p, own_r = T.step_f32(b, r, p_old, lam, T.STEP_MOMENTUM, nonneg)
-                    p, r_next = run(exe, workdir, ["step", *shape, repr(lam), repr(T.STEP_MOMENTUM), int(nonneg)], [b, r, p_old],
+                    p, r_next = run(exe, ["step", *shape, repr(lam), repr(T.STEP_MOMENTUM), int(nonneg)], [b, r, p_old],
                                     [(3,) + shape] * 2)
                     host = max(float(np.abs(p - want_p).max()), float(np.abs(r_next - want_r).max()))
                     own = max(float(np.abs(own_p - want_p).max()), float(np.abs(own_r - want_r).max()))
@@ -62,7 +39,7 @@ def main():
                                 for t in (p, r_next))
                     assert inert == 0.0, (shape, lam, nonneg)
                     want_x = T.primal(b, r, lam, nonneg)
-                    x, = run(exe, workdir, ["primal", *shape, repr(lam), int(nonneg)], [b, r], [shape])
+                    x, = run(exe, ["primal", *shape, repr(lam), int(nonneg)], [b, r], [shape])
                     host_x = float(np.abs(x - want_x).max())
                     own_x = float(np.abs(T.primal_f32(b, r, lam, nonneg) - want_x).max())
                     same = np.array_equal(p, own_p) and np.array_equal(r_next, own_r) and np.array_equal(x, T.primal_f32(b, r, lam, nonneg))

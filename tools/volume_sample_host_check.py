@@ -13,68 +13,46 @@ The program is never loaded into Python.  No GPU.
 
     python tools/volume_sample_host_check.py
 """
+import functools
 import os
-import shutil
-import subprocess
 import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, "tests"))
+sys.path.append(os.path.dirname(os.path.abspath(__file__)))          # tools/, for a caller that loads this file by its path
+import host_check  # noqa: E402
 
-FLAGS = ["-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall"]
 SHAPES = ((5, 6, 7), (1, 4, 4), (4, 1, 1), (2, 2, 2), (1, 1, 1))
 
-
-def compiler():
-    return shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-
-
-def build(workdir):
-    cxx = compiler()
-    if cxx is None:
-        raise RuntimeError("no host C++ compiler found")
-    exe = os.path.join(workdir, "volume_sample_host_check")
-    subprocess.check_call([cxx, *FLAGS, os.path.join(REPO, "tools", "volume_sample_host_check.cpp"), "-o", exe])
-    return exe
-
-
-def _run(cmd):
-    done = subprocess.run(cmd, capture_output=True, text=True)
-    if done.returncode != 0 or done.stderr.strip():
-        raise RuntimeError(f"exit {done.returncode}: {done.stdout}\nsanitizer output:\n{done.stderr}")
-    return done.stdout.split()
+compiler = host_check.compiler                                       # such a caller asks the driver, not host_check
+build = functools.partial(host_check.build, "volume_sample")
 
 
 def _grid_args(volume, dvoxel):
-    return [*[str(n) for n in volume.shape], *[repr(float(np.float32(v))) for v in dvoxel]]
+    return [*volume.shape, *[repr(float(np.float32(v))) for v in dvoxel]]
 
 
 def sample(exe, workdir, volume, dvoxel, points):
     """sample_point at `points` [n, 3] -> (float32 [n], the program's largest error in units of 2^-24 max n max|f|, its NaN count)."""
-    paths = [os.path.join(workdir, name + ".f32") for name in ("volume", "points", "out")]
-    for path, a in zip(paths, (volume, points)):
-        np.ascontiguousarray(a, dtype=np.float32).tofile(path)
-    words = _run([exe, "sample", *_grid_args(volume, dvoxel), str(len(points)), *paths])
+    (out,), stdout = host_check.run(exe, ["sample", *_grid_args(volume, dvoxel), len(points)], [volume, points],
+                                    [(np.float32, len(points))])
+    words = stdout.split()
     assert words[0::2] == ["worst", "nan"], words
-    return np.fromfile(paths[2], dtype=np.float32), float(words[1]), int(words[3])
+    return out, float(words[1]), int(words[3])
 
 
 def draw(exe, workdir, volume, dvoxel, lo, hi, seed, step, n):
     """sample_draw + sample_point for n points -> (points float32 [n, 3], targets float32 [n]); no coordinate may leave [lo, hi]."""
-    paths = [os.path.join(workdir, name + ".f32") for name in ("volume", "drawn", "targets")]
-    np.ascontiguousarray(volume, dtype=np.float32).tofile(paths[0])
     box = [repr(float(np.float32(v))) for v in (*lo, *hi)]
-    words = _run([exe, "draw", *_grid_args(volume, dvoxel), str(n), str(int(seed)), str(int(step)), *box, *paths])
-    assert words == ["outside", "0"], words
-    return np.fromfile(paths[1], dtype=np.float32).reshape(n, 3), np.fromfile(paths[2], dtype=np.float32)
+    (points, targets), stdout = host_check.run(exe, ["draw", *_grid_args(volume, dvoxel), n, int(seed), int(step), *box], [volume],
+                                               [(np.float32, 3 * n), (np.float32, n)])
+    assert stdout.split() == ["outside", "0"], stdout
+    return points.reshape(n, 3), targets
 
 
 def check_offsets(exe):
-    assert _run([exe, "offsets"]) == ["offsets", "0"]
+    assert host_check.run(exe, ["offsets"])[1].split() == ["offsets", "0"]
 
 
 def check_shape(O, exe, workdir, dims, dvoxel, exact_centres):
