@@ -161,13 +161,14 @@ def reference_rays(n, S, pattern):
     return sorted(probes + extra)
 
 
-def oracle_net(seed, log2T=12, scale=0.5, L=16, C=2):
+def oracle_net(seed, log2T=12, scale=0.5, L=16, C=2, act="sigmoid"):
     """The canonical network's oracle twin with a random table (for the CPU tests; the GPU tests take _naf_helpers.naf_pair's).
-    L x C = 32: the level shape of the encoder (tests/_mlp32_oracle.py runs 8 x 4 and 4 x 8)."""
+    L x C = 32: the level shape of the encoder (tests/_mlp32_oracle.py runs 8 x 4 and 4 x 8).  act: the output head (HEADS); the
+    weights of a seed do not depend on it."""
     torch.manual_seed(seed)
     enc = HashEncoderRef(3, L, C, 16, log2T)
     enc.embeddings.data.uniform_(-scale, scale)
-    return DensityNetworkRef(enc, bound=BOUND, num_layers=4, hidden_dim=32, skips=(2,), out_dim=1, last_activation="sigmoid")
+    return DensityNetworkRef(enc, bound=BOUND, num_layers=4, hidden_dim=32, skips=(2,), out_dim=1, last_activation=act)
 
 
 def round_table_once(ref):
@@ -192,22 +193,61 @@ def mlp_params(layers, rnd, dtype):
     return W, b, layers[3].weight.detach().to(dtype)
 
 
-def forward_points(x, params, rnd):
-    """x [N, 32]: the (rounded) features.  -> h1, h2, h3, sigma [N]."""
+# The output head (naf_render_cfg.last_activation 0..3; "relu" is the reference's name for LeakyReLU(0.01), network.py) as last_act and
+# last_act_grad of csrc/field_mlp.h write it.  float64: the reference.  float32: the kernel's own formula, the cancellation in
+# 1 - y y included.
+HEADS = ("sigmoid", "relu", "tanh", "none")
+
+
+def head(z, act):
+    """last_act in z's dtype."""
+    if act == "sigmoid":
+        return torch.sigmoid(z)
+    if act == "relu":
+        return _leaky(z)
+    if act == "tanh":
+        return torch.tanh(z)
+    if act != "none":
+        raise ValueError(act)
+    return z
+
+
+def head_grad(z, y, act, slope=LEAK, flip=None):
+    """last_act_grad, THROUGH THE OUTPUT y as the kernels form it: y (1 - y), z > 0 ? 1 : 0.01, 1 - y y, 1.  slope: the leaky head's
+    value for z <= 0 (fault injection); flip [N] bool: points whose z > 0 is decided the other way (the undecided points of
+    tests/_mlp32_oracle.py's head cases)."""
+    if act == "sigmoid":
+        return y * (1 - y)
+    if act == "relu":
+        up = z > 0
+        if flip is not None:
+            up = up ^ flip.reshape(up.shape)
+        return torch.where(up, torch.ones_like(z), torch.full_like(z, slope))
+    if act == "tanh":
+        return 1 - y * y
+    if act != "none":
+        raise ValueError(act)
+    return torch.ones_like(z)
+
+
+def forward_points(x, params, rnd, act="sigmoid", with_z=False):
+    """x [N, 32]: the (rounded) features.  -> h1, h2, h3, sigma [N] (and z4 [N], the output unit before its head: with_z)."""
     W, b, w3 = params
     h1 = _leaky(x @ W[0].T + b[0])
     h2 = _leaky(rnd(h1) @ W[1].T + b[1])
     h3 = _leaky(torch.cat([x, rnd(h2)], -1) @ W[2].T + b[2])
-    sig = torch.sigmoid(h3 @ w3.T + b[3]).reshape(-1)
-    return h1, h2, h3, sig
+    z4 = h3 @ w3.T + b[3]
+    sig = head(z4, act).reshape(-1)
+    return (h1, h2, h3, sig, z4.reshape(-1)) if with_z else (h1, h2, h3, sig)
 
 
-def backward_points(x, gsig, params, rnd):
-    """Backward of points with features x [N, 32] and d loss / d sigma gsig [N] (the kernels recompute the forward from the features):
-    the operands of the weight-gradient products and the feature gradients dx [N, 32] (unrounded)."""
+def backward_points(x, gsig, params, rnd, act="sigmoid", slope=LEAK, flip=None):
+    """Backward of points with features x [N, 32] and d loss / d sigma gsig [N] (the kernels recompute the forward from the features,
+    sigma and its derivative with their own copy of `act`): the operands of the weight-gradient products and the feature gradients
+    dx [N, 32] (unrounded).  slope, flip: see head_grad."""
     W, b, w3 = params
-    h1, h2, h3, sig = forward_points(x, params, rnd)
-    g4 = (gsig * (sig * (1 - sig))).reshape(-1, 1)
+    h1, h2, h3, sig, z4 = forward_points(x, params, rnd, act, with_z=True)
+    g4 = (gsig * head_grad(z4, sig, act, slope, flip)).reshape(-1, 1)
     G3 = rnd((w3 * g4) * _mask(h3))
     G2 = rnd((G3 @ W[2][:, 32:]) * _mask(h2))
     G1 = rnd((G2 @ W[1]) * _mask(h1))
@@ -262,15 +302,17 @@ def unpack(flat):
     return out
 
 
-def rehearse(x, dist, target, weight, layers, rnd=bf16_round, dtype=torch.float64, fault=None, order=None, sample_order=None, chunks=1):
+def rehearse(x, dist, target, weight, layers, rnd=bf16_round, dtype=torch.float64, fault=None, order=None, sample_order=None, chunks=1,
+             act="sigmoid", flip=None):
     """One training step on rays with features x [n, S, 32] (encoder output, not yet rounded), sample distances dist [n, S], targets and
     weights [n].  acc comes from the rehearsal's own forward, dacc = 2 w (acc - target), loss = sum w (acc - target)^2.
 
     `order` (a permutation of the n * S points), `sample_order` (a permutation of a ray's S samples) and `chunks`: every sum over
     points / over the samples of a ray is formed in that order, as `chunks` partial sums added at the end.
     `fault`: dict of deviations a wrong kernel would make, see the fault_* builders.
+    `act`: the output head (HEADS).  `flip` [n * S] bool: points whose leaky-head decision z4 > 0 the backward takes the other way.
 
-    -> dict: acc [n], loss, dacc [n], blocks (list of 8), packed [4225], dx [n * S, 32] (rounded: stored as bf16)."""
+    -> dict: acc [n], loss, dacc [n], blocks (list of 8), packed [4225], dx [n * S, 32] (rounded: stored as bf16), z4 [n, S]."""
     fault = fault or {}
     n, S, _ = x.shape
     params = mlp_params(layers, rnd, dtype)
@@ -278,7 +320,12 @@ def rehearse(x, dist, target, weight, layers, rnd=bf16_round, dtype=torch.float6
     dist = dist.to(dtype)
     target = target.to(dtype)
     weight = weight.to(dtype)
-    sig = forward_points(xr, params, rnd)[3].reshape(n, S)
+    fwd = forward_points(xr, params, rnd, act, with_z=True)
+    sig, z4 = fwd[3].reshape(n, S), fwd[4].reshape(n, S)
+    if "head_forward_items" in fault:                                     # work items whose forward got the default head (0: sigmoid)
+        sig = sig.clone()
+        for r, a, e in fault["head_forward_items"]:
+            sig[r, a:e] = head(z4[r, a:e], "sigmoid")
     terms = sig * dist
     if sample_order is not None:
         terms = terms[:, sample_order]
@@ -300,7 +347,10 @@ def rehearse(x, dist, target, weight, layers, rnd=bf16_round, dtype=torch.float6
         xb = torch.cat([xb, xr.reshape(n, S, 32)[er, es]])
         gsig = torch.cat([gsig, dacc[er] * ed.to(dtype)])
         m = torch.cat([torch.ones(n * S, dtype=dtype) if m is None else m, torch.ones(len(er), dtype=dtype)])
-    bp = backward_points(xb, gsig, params, rnd)
+    if flip is not None and flip.numel() != gsig.numel():
+        raise ValueError("flip and extra points do not combine")
+    # head_backward: the backward's own copy of `act` is another head's; head_slope: its leaky derivative for z4 <= 0 is not 0.01
+    bp = backward_points(xb, gsig, params, rnd, fault.get("head_backward", act), fault.get("head_slope", LEAK), flip)
 
     def widen(v):
         if v is None or v.numel() == gsig.numel():
@@ -312,7 +362,7 @@ def rehearse(x, dist, target, weight, layers, rnd=bf16_round, dtype=torch.float6
     dx = rnd(bp["dx"][:n * S])
     if "stored" in fault:                                                 # feature gradients that were never written
         dx = dx * fault["stored"].reshape(-1, 1).to(dtype)
-    return dict(acc=acc, loss=loss, dacc=dacc, blocks=blocks, packed=pack(blocks), dx=dx)
+    return dict(acc=acc, loss=loss, dacc=dacc, blocks=blocks, packed=pack(blocks), dx=dx, z4=z4)
 
 
 def geometry(rays, t_rand, S):
@@ -337,7 +387,7 @@ def table_gradient(dx, pts, ref):
 
 def step_reference(ref, rays, t_rand, target, weight, ray_ids, S, **kw):
     """rehearse() for the rays `ray_ids` of a batch (weight: the whole batch's), on the oracle encoder's features of the table as
-    stored.  -> the rehearsal's dict plus emb_g (the table gradient) and rays (ray_ids)."""
+    stored (kw: rehearse()'s, `act` among them).  -> the rehearsal's dict plus emb_g (the table gradient) and rays (ray_ids)."""
     ids = torch.as_tensor(list(ray_ids))
     with torch.no_grad():
         _, pts, dist = geometry(rays[ids], t_rand[ids], S)
@@ -466,3 +516,20 @@ def fault_first_tile_rounded_up(n, S, ids):
             src[:, a:e] = (torch.arange(a, e) + 16 * (hi[p] - lo[p])).clamp(max=S - 1)
             hit += 1
     return dict(feature_source=src) if hit else None
+
+
+# ---- head faults: a kernel whose output head is not the one of the cfg ----------------------------------------------------------------------
+def fault_head_backward(other):
+    """The backward kernel got another head than the forward: sigma and its derivative recomputed with `other`."""
+    return dict(head_backward=other)
+
+
+def fault_head_slope(slope):
+    """The leaky head's derivative for z4 <= 0 is `slope` (1: the identity's; 0: a plain ReLU's) where 0.01 belongs."""
+    return dict(head_slope=float(slope))
+
+
+def fault_head_forward_items(ids, ranges):
+    """`ranges`: (global ray, first sample, end sample) of the work items or tiles whose forward took head 0."""
+    loc = _local(ids)
+    return dict(head_forward_items=[(loc[r], a, e) for r, a, e in ranges])

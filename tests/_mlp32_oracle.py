@@ -71,6 +71,8 @@ Layout = collections.namedtuple("Layout", "L C table_dtype rnd")
 LAYOUTS = {"f32": Layout(16, 2, torch.float32, identity),
            "bf16-8x4": Layout(8, 4, torch.bfloat16, bf16_round),
            "bf16-4x8": Layout(4, 8, torch.bfloat16, bf16_round)}
+# the layouts of the head cases (OUTPUT HEADS below): the 16-point kernels' own (C = 2, bf16: _mlp16_oracle's plan and probes) beside two of the above
+HEAD_LAYOUTS = dict(LAYOUTS, **{"bf16-16x2": Layout(16, 2, torch.bfloat16, bf16_round)})
 
 CASES = ((1024, 192), (300, 64), (37, 50), (1, 33), (3, 70), (24, 7), (6, 1030), (2100, 40), (4500, 20), (8300, 20))
 LAYOUT_CASES = {"f32": CASES, "bf16-8x4": CASES, "bf16-4x8": ((1024, 192), (37, 50), (2100, 40))}
@@ -179,10 +181,10 @@ def reference_rays(n, S, pattern):
     return sorted(probes + extra)
 
 
-def oracle_net(layout, seed, log2T=12):
+def oracle_net(layout, seed, log2T=12, act="sigmoid"):
     """The oracle twin of a layout's network with a random table, the table rounded once where the layout stores bf16."""
-    lay = LAYOUTS[layout]
-    ref = O.oracle_net(seed, log2T=log2T, L=lay.L, C=lay.C)
+    lay = HEAD_LAYOUTS[layout]
+    ref = O.oracle_net(seed, log2T=log2T, L=lay.L, C=lay.C, act=act)
     return ref if lay.table_dtype == torch.float32 else O.round_table_once(ref)
 
 
@@ -191,7 +193,7 @@ _SWAP = list(range(4)) + list(range(8, 12)) + list(range(4, 8)) + list(range(12,
 
 
 def reference(layout, ref, n, S, pattern, fault=None, **kw):
-    """_mlp16_oracle.step_reference of a case in a layout's rounding (kw: dtype, order, sample_order, chunks).  The fault key
+    """_mlp16_oracle.step_reference of a case in a layout's rounding (kw: dtype, order, sample_order, chunks, act, flip).  The fault key
     'swap_features' (fault_chunks_swapped) acts on the finished blocks; every other key is rehearse()'s."""
     fault = dict(fault or {})
     swap = fault.pop("swap_features", None)
@@ -228,11 +230,11 @@ def table_gradient_f32(dx, n, S, pattern, ref, order=None):
     return acc
 
 
-def summation_orders(n, S, pattern):
+def summation_orders(n, S, pattern, ids=None):
     """name -> kwargs of rehearse(): the four orders the f32 tolerances are measured in.  'waves': the points in the order the
     backward's waves take them (wave w: rays w, w + 4 slabs, ..., waves in slab order), as partial sums of 32 consecutive points
     -- the kernel's tiles wherever S is a multiple of 32 -- added one after the other."""
-    ids = reference_rays(n, S, pattern)
+    ids = reference_rays(n, S, pattern) if ids is None else list(ids)
     N = len(ids) * S
     g = torch.Generator().manual_seed(3 * n + S)
     waves = 4 * backward_slabs(n)
@@ -244,7 +246,7 @@ def summation_orders(n, S, pattern):
             "waves": dict(order=wave_order, chunks=-(-N // TILE))}
 
 
-def rehearse_in_float32(layout, ref, n, S, pattern):
+def rehearse_in_float32(layout, ref, n, S, pattern, **kw_all):
     """order name -> the float32 rehearsal of a case in that order (reference()'s dict).  One thread, so that the BLAS behind the
     partial products sums the same way wherever this runs.  f32 layout: the table gradient is scattered in fp32 too, in the same
     point order."""
@@ -253,7 +255,7 @@ def rehearse_in_float32(layout, ref, n, S, pattern):
     try:
         out = {}
         for name, kw in summation_orders(n, S, pattern).items():
-            got = reference(layout, ref, n, S, pattern, dtype=torch.float32, **kw)
+            got = reference(layout, ref, n, S, pattern, dtype=torch.float32, **kw, **kw_all)
             if layout == "f32":
                 got["emb_g"] = table_gradient_f32(got["dx"], n, S, pattern, ref, kw.get("order"))
             out[name] = got
@@ -392,3 +394,124 @@ def fault_chunks_swapped(operand):
     'X': the input tiles X0 / H1 / H2 -- columns of dW0 / dW1 / dW2 permuted."""
     assert operand in ("G", "X")
     return dict(swap_features=operand)
+
+
+# ---- OUTPUT HEADS ------------------------------------------------------------------------------------------------------------------------------
+# The cases above restate the sigmoid head.  The other three heads of naf_render_cfg.last_activation (relu: LeakyReLU(0.01), tanh, none)
+# run on a few cases per kernel family (tests/test_hip_mlp_heads_reference.py; tests/test_mlp_heads_oracle_cpu.py checks what follows
+# without a GPU).  (rays, S, pattern) per layout; bf16-16x2 is _mlp16_oracle's plan: mlp16_train_kernel<12>, its 4-wave form on a ragged
+# tile, the pair above the one-launch limit with a wave's second item, and a dense case; the 32-point kernels: a ragged tile, the
+# one-point tile, a wave's second ray and its prefetched tile.
+HEAD_ACTS = ("relu", "tanh", "none")
+HEAD_CASES = {"bf16-16x2": ((1024, 192, "probe"), (700, 100, "probe"), (3100, 40, "probe"), (24, 7, "dense")),
+              "f32": ((37, 50, "dense"), (1, 33, "dense"), (2100, 40, "probe")),
+              "bf16-8x4": ((37, 50, "dense"), (1, 33, "dense"), (2100, 40, "probe"))}
+HEAD_ZERO_CASE = (24, 7)
+# Network seed per head (_naf_helpers.naf_pair and oracle_net give the same weights for a seed).  tanh and none keep 37, the seed of
+# every sigmoid case: |z4| < 0.19 there, no point anywhere near tanh's saturation (the fraction of points with |y| > 0.99 is 0, so
+# neither `scale` nor b3 had to move).  relu: see THE LEAKY HEAD'S DECISION.
+HEAD_SEEDS = {"sigmoid": 37, "relu": 222, "tanh": 37, "none": 37}
+
+# f32 layout, per head: worst float32-against-float64 figure of each class over MEASURE_CASES x summation_orders(), as F32_MEASURED
+# (whose sigmoid figures stay as they are), and 8 x that rounded up to one digit.
+#   relu  acc 2.203e-7 (37, 50) waves -> 2e-6 | loss 1.118e-7 (300, 64) shuffled-7 -> 9e-7 | grad 4.777e-7 (300, 64) waves -> 4e-6 | table 1.552e-7 -> 2e-6
+#   tanh  acc 1.951e-7 (1024, 192) waves -> 2e-6 | loss 9.366e-8 (1024, 192) waves -> 8e-7 | grad 3.993e-7 (300, 64) waves -> 4e-6 | table 1.594e-7 -> 2e-6
+#   none  acc 2.017e-7 (1024, 192) waves -> 2e-6 | loss 9.775e-8 (37, 50) shuffled-7 -> 8e-7 | grad 6.018e-7 (300, 64) waves -> 5e-6 | table 1.440e-7 -> 2e-6
+# (smallest figure of a class over the twelve runs of a head: acc 3.6e-8, loss 7.7e-10, grad 7.1e-8, table 1.06e-7.)  tanh's gradient figure is
+# that of the other heads: nothing saturates in these cases, see HEAD_SEEDS.
+HEAD_F32_MEASURED = {"sigmoid": F32_MEASURED,
+                     "relu": {"acc": 2.21e-7, "loss": 1.12e-7, "grad": 4.78e-7, "table": 1.56e-7},
+                     "tanh": {"acc": 1.96e-7, "loss": 9.37e-8, "grad": 4.00e-7, "table": 1.60e-7},
+                     "none": {"acc": 2.02e-7, "loss": 9.78e-8, "grad": 6.02e-7, "table": 1.45e-7}}
+HEAD_F32_TOL = {act: {k: derived_tolerance(v) for k, v in m.items()} for act, m in HEAD_F32_MEASURED.items()}
+
+# THE LEAKY HEAD'S DECISION.  z4 > 0 is a discontinuity of the leaky head's derivative: a weighted point that the kernel's fp32 z4 puts
+# on the other side of 0 than the reference's moves a block by far more than any tolerance here.  Per precision, delta = 8 x the worst
+# |z4(float32 rehearsal) - z4(float64 rehearsal)| over the relu cases x summation_orders() (worst figures below, rounded up to one
+# digit like the tolerances); a weighted point with |z4| < delta is UNDECIDED.  The relu seed is chosen so that no f32 case and no
+# f32 MEASURE_CASE has one and every bf16 case at most HEAD_MAX_UNDECIDED; for those the reference supplies both branches and the
+# comparison takes the best combination (head_references / best_ratios), as _raymarch_oracle does for its thresholds.
+#   f32 2.97e-8 at (300, 64) dense -> 3e-7;  bf16 1.53e-5 at bf16-16x2 (1024, 192) probe (a hidden activation on a bf16 rounding boundary) -> 2e-4
+HEAD_Z4_MEASURED = {"f32": 3.0e-8, "bf16": 1.6e-5}
+HEAD_DELTA = {k: derived_tolerance(v) for k, v in HEAD_Z4_MEASURED.items()}
+HEAD_MAX_UNDECIDED = {"f32": 0, "bf16": 2}
+
+
+def head_precision(layout):
+    return "f32" if layout == "f32" else "bf16"
+
+
+def head_inputs(layout, n, S, pattern):
+    """-> rays, t_rand, target, weight (the batch's), reference rays of a head case, on the layout's plan and probes."""
+    if layout == "bf16-16x2":
+        rays, t_rand, target, _ = O.case_inputs(n, S)
+        return rays, t_rand, target, O.case_weight(n, S, pattern), O.reference_rays(n, S, pattern)
+    rays, t_rand, target, _ = case_inputs(n, S)
+    return rays, t_rand, target, case_weight(n, S, pattern), reference_rays(n, S, pattern)
+
+
+def head_reference(layout, ref, n, S, pattern, act, **kw):
+    """_mlp16_oracle.step_reference of a head case in the layout's rounding (kw: rehearse()'s)."""
+    rays, t_rand, target, weight, ids = head_inputs(layout, n, S, pattern)
+    return O.step_reference(ref, rays, t_rand, target, weight, ids, S, rnd=HEAD_LAYOUTS[layout].rnd, act=act, **kw)
+
+
+def head_rehearse_in_float32(layout, ref, n, S, pattern, act):
+    """order name -> the float32 rehearsal of a head case in that order, as rehearse_in_float32 (which it is for the 32-point layouts)."""
+    if layout != "bf16-16x2":
+        return rehearse_in_float32(layout, ref, n, S, pattern, act=act)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        ids = head_inputs(layout, n, S, pattern)[4]
+        return {name: head_reference(layout, ref, n, S, pattern, act, dtype=torch.float32, **kw)
+                for name, kw in summation_orders(n, S, pattern, ids).items()}
+    finally:
+        torch.set_num_threads(threads)
+
+
+def undecided_points(layout, n, S, pattern, want):
+    """-> (flat indices into the reference's n_ids * S points of the weighted points with |z4| < delta, the smallest |z4| / delta
+    among the weighted points)."""
+    _, _, _, weight, ids = head_inputs(layout, n, S, pattern)
+    delta = HEAD_DELTA[head_precision(layout)]
+    z = torch.as_tensor(want["z4"]).abs().double()
+    live = (weight[torch.as_tensor(ids)] > 0)[:, None].expand_as(z)
+    if not bool(live.any()):
+        return [], float("inf")
+    und = torch.nonzero((live & (z < delta)).reshape(-1)).reshape(-1).tolist()
+    return und, float(z[live].min()) / delta
+
+
+def head_references(layout, ref, n, S, pattern, act):
+    """The references a kernel may match: one, or -- leaky head with k <= HEAD_MAX_UNDECIDED undecided points -- the 2^k combinations
+    of their branches (the first is the reference's own)."""
+    base = head_reference(layout, ref, n, S, pattern, act)
+    if act != "relu":
+        return [base]
+    und, _ = undecided_points(layout, n, S, pattern, base)
+    assert len(und) <= HEAD_MAX_UNDECIDED[head_precision(layout)], (layout, n, S, pattern, und)
+    out = [base]
+    for combo in range(1, 1 << len(und)):
+        flip = torch.zeros(base["z4"].numel(), dtype=torch.bool)
+        flip[[p for i, p in enumerate(und) if combo >> i & 1]] = True
+        out.append(head_reference(layout, ref, n, S, pattern, act, flip=flip))
+    return out
+
+
+def head_tolerances(layout, act):
+    """acc / loss / grad / table of a head in a layout: measured per head in f32, _mlp16_oracle's in every bf16 layout."""
+    if layout == "f32":
+        return HEAD_F32_TOL[act]
+    return {"acc": O.TOL_ACC, "loss": O.TOL_LOSS, "grad": O.TOL_GRAD, "table": O.TOL_TABLE}
+
+
+def head_ratios(layout, act, got, want):
+    """Every figure as a fraction of the head's tolerance in `layout`."""
+    tol = head_tolerances(layout, act)
+    return {k: v / tol.get(k, tol["grad"]) for k, v in figures(got, want).items()}
+
+
+def best_ratios(layout, act, got, wants):
+    """head_ratios against the reference of `wants` that suits `got` best (smallest worst fraction)."""
+    return min((head_ratios(layout, act, got, numpy_dict(w) if torch.is_tensor(w["acc"]) else w) for w in wants), key=lambda r: max(r.values()))
