@@ -842,6 +842,32 @@ int naf_align_shift_scores(const float *b, const float *p, const float *w, uint3
 int naf_align_peak(const double *scores, uint32_t N, uint32_t Rv, uint32_t Ru, float *shifts, int32_t *flags, void *stream);
 int naf_align_shift_views(const float *views, const float *shifts, uint32_t N, uint32_t H, uint32_t W, float *out, void *stream);
 
+/* A2  sinogram stripe removal by sorting (Vo, Atwood and Drakopoulos, Opt. Express 2018, algorithm 3; stripe.py).  DESIGN.md section
+ * 27; the integer arithmetic is csrc/stripe_device.h.  There is no floating-point arithmetic and no float comparison: every output
+ * is one of the input's bit patterns.
+ *   p     f32 [N, H, W] C-contiguous: N views, H detector rows (v), W detector columns (u)
+ *   size  = 2 h + 1, the width of the median window along u
+ *   key(x)  the order-preserving uint32 of a float's bits: sign bit set -> all bits inverted, otherwise the sign bit set.  A total
+ *           order on all bit patterns: -0 sorts before +0 and NaNs sort at the two ends by payload.
+ * For every (v, u) the N pairs (key(p[i, v, u]), i) are sorted ascending, the view index breaking ties:
+ *     perm[j, v, u]  the view of rank j,          s[j, v, u] = p[perm[j, v, u], v, u]
+ *     m[j, v, u]     the element of rank h, by key, among s[j, v, r(u + t)], t = -h .. h, where r reflects with the edge sample
+ *                    repeated (-1 -> 0, -2 -> 1, W -> W - 1, W + 1 -> W - 2); equal keys are equal bits
+ *     out[perm[j, v, u], v, u] = m[j, v, u]
+ * Limits, refused before any launch: 1 <= N <= NAF_STRIPE_MAX_VIEWS (perm is uint16); size odd, 3 <= size <= NAF_STRIPE_MAX_SIZE and
+ * size <= W; H, W <= 2^24; pointers non-null and 4-byte aligned, the workspace 8-byte aligned.  N H W == 0 returns NAF_OK without
+ * examining anything else.  out may be p: the second kernel reads only the workspace.  Non-finite inputs sort as their bits say.
+ * naf_stripe_workspace_bytes: the bytes for `rows` detector rows (1 <= rows <= H): s as f32 [rows, N, W] then perm as uint16
+ *   [rows, N, W], each rounded up to 8 bytes; 0 for arguments the call would refuse.
+ * naf_stripe_remove_sorting: detector rows are independent; the call walks them in groups of floor(ws_bytes / bytes of one row) rows
+ *   (at most H), two launches per group, and refuses a workspace smaller than one row.  Any grouping returns the same bits.  It
+ *   takes the stream, allocates nothing and never synchronises; element offsets are 64-bit. */
+#define NAF_STRIPE_MAX_SIZE 63u
+#define NAF_STRIPE_MAX_VIEWS 4096u
+size_t naf_stripe_workspace_bytes(uint32_t N, uint32_t H, uint32_t W, uint32_t rows);
+int naf_stripe_remove_sorting(const float *p, uint32_t N, uint32_t H, uint32_t W, uint32_t size, void *ws, size_t ws_bytes, float *out,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

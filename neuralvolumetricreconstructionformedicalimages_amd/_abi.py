@@ -187,6 +187,8 @@ SIGNATURES = {
     "naf_align_shift_scores": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, ctypes.c_size_t, _vp, _vp]),
     "naf_align_peak": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "naf_align_shift_views": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp]),
+    "naf_stripe_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32, _u32]),
+    "naf_stripe_remove_sorting": (_i32, [_vp, _u32, _u32, _u32, _u32, _vp, ctypes.c_size_t, _vp, _vp]),
 }
 
 

@@ -282,3 +282,24 @@ def add_noise(projs, noise, generator, i0=NOISE_I0):
     counts = torch.poisson(i0 * torch.exp(-projs.double()), generator=generator)
     counts = counts + float(noise) * torch.randn(counts.shape, generator=generator, device=counts.device, dtype=counts.dtype)
     return (-torch.log(counts.clamp(min=1.0) / i0)).float()
+
+
+def add_stripes(projs, fraction, sigma, generator):
+    """Detector pixels with a wrong gain, on line integrals `projs` [N, H, W] (numpy array or CPU tensor; host side): each of the
+    H W pixels is defective with probability `fraction`, a defective pixel has the gain 1 + sigma n with n standard normal (kept
+    at 0.1 or above), and the gain multiplies the transmission: p' = -ln(gain exp(-p)).  The gain of a pixel is the same in every
+    view, which is what draws a stripe in the sinogram and a ring in the volume.  `generator` is a numpy Generator or an int seed
+    for one; equal seeds give equal bits.  Returns float32 of the kind given; `projs` is left as it is."""
+    if not 0.0 <= float(fraction) <= 1.0 or float(sigma) < 0.0:
+        raise ValueError(f"add_stripes: fraction must be in [0, 1] and sigma >= 0, got {fraction}, {sigma}")
+    as_tensor = isinstance(projs, torch.Tensor)
+    if as_tensor and projs.is_cuda:
+        raise ValueError("add_stripes: projs must be on the host")
+    p = (projs.numpy() if as_tensor else np.asarray(projs)).astype(np.float64)
+    if p.ndim != 3:
+        raise ValueError(f"add_stripes: projs must be [N, H, W], got {p.shape}")
+    rng = generator if isinstance(generator, np.random.Generator) else np.random.default_rng(generator)
+    defective = rng.random(p.shape[1:]) < float(fraction)
+    gain = np.where(defective, np.maximum(1.0 + float(sigma) * rng.standard_normal(p.shape[1:]), 0.1), 1.0)
+    out = (-np.log(np.exp(-p) * gain[None])).astype(np.float32)
+    return torch.from_numpy(out) if as_tensor else out

@@ -1,0 +1,97 @@
+"""The entry points of sinogram stripe removal (include/naf_hip.h A2) are exported, declared and bound, refuse bad arguments before
+any launch, and the ABI version is the one existing callers pin.  No GPU needed: nothing is launched."""
+import ctypes
+import os
+import re
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = {"naf_stripe_workspace_bytes": 4, "naf_stripe_remove_sorting": 9}
+
+
+def test_symbols_are_declared_bound_and_exported():
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi, build, stripe
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "naf_hip.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(naf_[a-z0-9_]+)\s*\(", text))
+    lib = _abi.lib()
+    raw = ctypes.CDLL(build.LIB_PATH)
+    for name, n_args in NAMES.items():
+        assert name in declared and name in _abi.SIGNATURES and hasattr(raw, name)
+        assert len(_abi.SIGNATURES[name][1]) == n_args
+    assert lib.naf_stripe_workspace_bytes.restype is ctypes.c_size_t
+    assert lib.naf_stripe_remove_sorting.restype is ctypes.c_int
+    assert lib.naf_abi_version() == 5
+    assert "#define NAF_STRIPE_MAX_SIZE 63u" in text and stripe.MAX_SIZE == 63
+    assert "#define NAF_STRIPE_MAX_VIEWS 4096u" in text and stripe.MAX_VIEWS == 4096
+    assert any(p.endswith("stripe.hip") for p in build.sources())
+    assert any(p.endswith("stripe_device.h") for p in build._deps())
+
+
+def test_workspace_size_is_a_float_and_a_uint16_per_element_each_rounded_to_8_bytes():
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi
+    size = _abi.lib().naf_stripe_workspace_bytes
+    assert size(1, 1, 3, 1) == 16 + 8                                        # 12 -> 16 bytes of s, 6 -> 8 bytes of perm
+    assert size(50, 512, 512, 512) == 50 * 512 * 512 * 6
+    assert size(50, 512, 512, 1) == 50 * 512 * 6
+    assert size(65, 2, 37, 2) == 65 * 2 * 37 * 4 + (65 * 2 * 37 * 2 + 4)    # 19 240 bytes of s, 9 620 -> 9 624 bytes of perm
+    assert size(4096, 1 << 24, 1 << 24, 1) == 4096 * (1 << 24) * 6
+    for bad in ((0, 4, 8, 1), (4097, 4, 8, 1), (3, 0, 8, 1), (3, 4, 0, 1), (3, (1 << 24) + 1, 8, 1), (3, 4, (1 << 24) + 1, 1),
+                (3, 4, 8, 0), (3, 4, 8, 5)):
+        assert size(*bad) == 0
+
+
+def test_arguments_are_refused_before_any_launch():
+    from neuralvolumetricreconstructionformedicalimages_amd import _abi
+    lib = _abi.lib()
+    p, ws, out = (ctypes.c_void_p(v) for v in (4096, 8192, 12288))
+    err = lib.naf_last_error
+    run = lib.naf_stripe_remove_sorting
+    big = 1 << 30
+    # N H W == 0 is a successful no-op whatever the pointers, the size and the workspace
+    for shape in ((0, 4, 8), (3, 0, 8), (3, 4, 0)):
+        assert run(None, *shape, 4, None, 0, None, None) == 0
+    for args in ((None, ws, out), (p, None, out), (p, ws, None)):
+        assert run(args[0], 3, 4, 8, 5, args[1], big, args[2], None) == -1 and b"null pointer" in err()
+    assert run(p, 4097, 4, 8, 5, ws, big, out, None) == -1 and b"more than 4096 views" in err()
+    assert run(p, 3, (1 << 24) + 1, 8, 5, ws, big, out, None) == -1 and b"above 2^24" in err()
+    assert run(p, 3, 4, (1 << 24) + 1, 5, ws, 1 << 40, out, None) == -1 and b"above 2^24" in err()
+    for size in (0, 1, 2, 4, 6, 64, 65):
+        assert run(p, 3, 4, 80, size, ws, big, out, None) == -1 and b"odd and in [3, 63]" in err()
+    assert run(p, 3, 4, 8, 9, ws, big, out, None) == -1 and b"size above the number of detector columns" in err()
+    assert run(p, 3, 4, 4, 5, ws, big, out, None) == -1 and b"size above" in err()
+    assert run(ctypes.c_void_p(4098), 3, 4, 8, 5, ws, big, out, None) == -1 and b"4-byte aligned" in err()
+    assert run(p, 3, 4, 8, 5, ws, big, ctypes.c_void_p(12290), None) == -1 and b"4-byte aligned" in err()
+    assert run(p, 3, 4, 8, 5, ctypes.c_void_p(8196), big, out, None) == -1 and b"8-byte aligned" in err()
+    one_row = lib.naf_stripe_workspace_bytes(3, 4, 8, 1)
+    assert one_row == 3 * 8 * 6
+    assert run(p, 3, 4, 8, 5, ws, one_row - 1, out, None) == -1 and b"workspace too small" in err()
+    assert run(p, 3, 4, 8, 5, ws, 0, out, None) == -1 and b"workspace too small" in err()
+    assert err().startswith(b"stripe_remove_sorting: ")
+
+
+def test_python_front_end_refuses_without_a_gpu():
+    import pytest
+    import torch
+    from neuralvolumetricreconstructionformedicalimages_amd import stripe
+    cpu = torch.zeros(3, 4, 8)
+    with pytest.raises(ValueError, match="no CPU path"):
+        stripe.remove_stripes(cpu)
+    with pytest.raises(ValueError, match="no CPU path"):
+        stripe.remove_stripes(cpu, size=3)
+    with pytest.raises(ValueError, match=r"float32 \[N, H, W\]"):
+        stripe.remove_stripes(cpu.double())
+    with pytest.raises(ValueError, match=r"float32 \[N, H, W\]"):
+        stripe.remove_stripes(cpu[0])
+    with pytest.raises(ValueError, match="must be a tensor"):
+        stripe.remove_stripes(cpu.numpy())
+    for size in (4, 1, 65, 0, -3):
+        with pytest.raises(ValueError, match="odd and in"):
+            stripe.remove_stripes(cpu, size=size)
+    for size in (2.5, True, "5"):
+        with pytest.raises(ValueError, match="must be an int"):
+            stripe.remove_stripes(cpu, size=size)
+    with pytest.raises(ValueError, match="above the 8 detector columns"):
+        stripe.remove_stripes(cpu, size=9)
+    assert stripe.check_size(7, 8) == 7 and stripe.check_size(63, 63) == 63
+    assert stripe.workspace_bytes(50, 512, 512) == 50 * 512 * 512 * 6 and stripe.workspace_bytes(50, 512, 512, rows=1) == 50 * 512 * 6
+    with pytest.raises(ValueError, match="illegal shape"):
+        stripe.workspace_bytes(4097, 4, 8)
