@@ -548,7 +548,7 @@ scatter_bin2_kernel(SrcRays src, const uint16_t *__restrict__ grad, const int32_
 // scatter_binned.h (every wave streams one contiguous range of tiles, eight runs in flight per lane, tails of two runs share an
 // instruction); accumulators acc[channel][local row], 64-bit fixed point (ds_add_u64), filled through the integer pipe (see the header).
 // kAdam: the workgroup finishes its rows with their Adam update (naf_render_train_adam) -- a plain stream over contiguous memory,
-// 16 bytes per lane and array (two rows x two channels), operands requested in front of the record phase; kFast picks the form of
+// 16 bytes per lane and array (two rows x two channels), operands requested in front of the record phase and behind its last loads; kFast picks the form of
 // adam_math.h (tables with a 16-bit shadow).
 __device__ __forceinline__ int cvt_rpi(float v) {                // floor(v + 0.5): one instruction, no bias towards zero
     int i;                                                        // (plain truncation measured the same: profiles/round4_ab_*)
@@ -608,25 +608,39 @@ scatter_reduce2_kernel(const PairFx *__restrict__ blocks, const uint32_t *__rest
                                  // records queue behind them and the record phase starts at 18 000 of the workgroup's 43 000 cycles.  Same-box
                                  // A/B, 1 / 2 / 3 / 4 quads: 0.092 / 0.090 / 0.090-0.091 / 0.092-0.093 ms at 1 024 rays, flat at 65 536
                                  // (profiles/round4_ab_reducer_adam_prefetch_depth.jsonl; A/B builds override the macro).
-    constexpr uint32_t kPreQ = kAdam ? NAF_RED_PREQ : 0u;       // quads (two rows x two channels) prefetched per thread
-    Quad preq_p[kPreQ ? kPreQ : 1u], preq_m[kPreQ ? kPreQ : 1u], preq_v[kPreQ ? kPreQ : 1u];
+#ifndef NAF_RED_LATEQ
+#define NAF_RED_LATEQ 2u         // The other two are requested BEHIND the records: by each wave right after it has issued its last group of
+#endif                           // record loads, in front of that group's LDS adds and of the barrier -- they travel while the slowest wave
+                                 // finishes its adds, instead of being requested one by one in the tail that consumes them.
+                                 // 24 more registers across the record phase; 0 gives the old order back (A/B builds).
+    constexpr uint32_t kPreQ = kAdam ? NAF_RED_PREQ : 0u;       // quads (two rows x two channels) requested in front of the record phase,
+    constexpr uint32_t kLateQ = kAdam ? NAF_RED_LATEQ : 0u;     // ... and behind it, per thread
+    constexpr uint32_t kHeldQ = kPreQ + kLateQ;
+    Quad preq_p[kHeldQ ? kHeldQ : 1u], preq_m[kHeldQ ? kHeldQ : 1u], preq_v[kHeldQ ? kHeldQ : 1u];
     // quad q = local rows 2q, 2q + 1 = two CONSECUTIVE table rows when chunks hold at least two rows (s >= 1) and both exist
     const uint32_t n_quads = (rows_local + 1u) >> 1;
     auto quad_row = [&](uint32_t q) { return map.row(bucket, 2u * q); };
     auto quad_full = [&](uint32_t row0) { return map.s != 0u && row0 + 1u < T; };
+    auto request_quad = [&](uint32_t k) __attribute__((always_inline)) {     // thread's quad k: the loads the tail would issue, same condition
+        const uint32_t q = threadIdx.x + k * T_;
+        const uint32_t row0 = quad_row(q);
+        preq_p[k] = preq_m[k] = preq_v[k] = Quad{0.0f, 0.0f, 0.0f, 0.0f};
+        if (q < n_quads && quad_full(row0)) {
+            const size_t e = ((size_t)off + row0) * 2u;
+            preq_p[k] = *reinterpret_cast<const Quad *>(adam.param + e);
+            preq_m[k] = *reinterpret_cast<const Quad *>(adam.m + e);
+            preq_v[k] = *reinterpret_cast<const Quad *>(adam.v + e);
+        }
+    };
+    auto request_late = [&]() __attribute__((always_inline)) {
+        if constexpr (kLateQ != 0u) {
+#pragma unroll
+            for (uint32_t k = kPreQ; k < kHeldQ; ++k) request_quad(k);
+        }
+    };
     if constexpr (kPreQ != 0u) {
 #pragma unroll
-        for (uint32_t k = 0; k < kPreQ; ++k) {
-            const uint32_t q = threadIdx.x + k * T_;
-            const uint32_t row0 = quad_row(q);
-            preq_p[k] = preq_m[k] = preq_v[k] = Quad{0.0f, 0.0f, 0.0f, 0.0f};
-            if (q < n_quads && quad_full(row0)) {
-                const size_t e = ((size_t)off + row0) * 2u;
-                preq_p[k] = *reinterpret_cast<const Quad *>(adam.param + e);
-                preq_m[k] = *reinterpret_cast<const Quad *>(adam.m + e);
-                preq_v[k] = *reinterpret_cast<const Quad *>(adam.v + e);
-            }
-        }
+        for (uint32_t k = 0; k < kPreQ; ++k) request_quad(k);
     }
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n_waves = T_ >> 6;
     const size_t run0 = run_index(plan, ly, bucket, 0);
@@ -660,6 +674,7 @@ scatter_reduce2_kernel(const PairFx *__restrict__ blocks, const uint32_t *__rest
         }
     };
     constexpr uint32_t kGroup = 8u, kTail = 32u;
+    if (t_begin >= t_end) request_late();                        // a wave without tiles has no record load to put them behind
     if (plan.log2_w < 6u) {
         // many buckets (T >= 2^20): short runs -- a wave takes G = 64 / W runs per instruction, W lanes each (scatter_binned.h)
         const uint32_t W = 1u << plan.log2_w, G = 64u >> plan.log2_w, g = lane >> plan.log2_w, j = lane & (W - 1u);
@@ -679,6 +694,7 @@ scatter_reduce2_kernel(const PairFx *__restrict__ blocks, const uint32_t *__rest
                     b4[u] = blocks + block_index(plan, ly, t0 + min(tl, n_here - 1u)) + (word & 0xffffu);
                     r4[u] = load_record(b4[u] + (j < n4[u] ? j : 0u));
                 }
+                if (t0 + 64u >= t_end && s0 + kSteps * G >= n_here) request_late();       // the wave's last group (uniform)
 #pragma unroll
                 for (uint32_t u = 0; u < kSteps; ++u)
                     if (j < n4[u]) add(r4[u]);
@@ -721,6 +737,7 @@ scatter_reduce2_kernel(const PairFx *__restrict__ blocks, const uint32_t *__rest
                     }
                     rt[q] = load_record(bq + (slot < nt[q] ? slot : 0u));
                 }
+                if (t0 + 64u >= t_end && j + kGroup >= n_here) request_late();            // the wave's last group (uniform)
 #pragma unroll
                 for (uint32_t u = 0; u < kGroup; ++u)
                     if (lane < n[u]) add(ra[u]);
@@ -833,9 +850,9 @@ scatter_reduce2_kernel(const PairFx *__restrict__ blocks, const uint32_t *__rest
             }
         };
 #pragma unroll
-        for (uint32_t k = 0; k < kPreQ; ++k) finish(threadIdx.x + k * T_, true, preq_p[k], preq_m[k], preq_v[k]);
+        for (uint32_t k = 0; k < kHeldQ; ++k) finish(threadIdx.x + k * T_, true, preq_p[k], preq_m[k], preq_v[k]);
         const Quad none{0.0f, 0.0f, 0.0f, 0.0f};
-        for (uint32_t q = threadIdx.x + kPreQ * T_; q < n_quads; q += T_) finish(q, false, none, none, none);
+        for (uint32_t q = threadIdx.x + kHeldQ * T_; q < n_quads; q += T_) finish(q, false, none, none, none);
     } else {
         // gradient table += sums: in place and coalesced when this workgroup is the sole owner of its rows, with one fp32 atomic per
         // element when the bucket's tiles were split between gridDim.z workgroups
