@@ -129,10 +129,19 @@ int naf_fine_depths(const float *rays, const float *t_rand, const float *sigma, 
  *   poses   f32 [n_projections, 3, 4]  = [R | t] of angle2pose (tigre.py:530-572), cast to fp32 like torch.Tensor(pose)
  *   pixels  i64 [n] flat pixel index  proj*H*W + row*W + col, or NULL for the dense range first_pixel .. first_pixel+n-1
  *   rays    f32 [n, 8] out (16-byte aligned): origin, direction (cone: un-normalised, tigre.py:434-437), near, far
+ *   det     the detector, the one description every entry point that makes rays of a scan takes: pixel (row, col) sits at
+ *           u = (col + 1/2 - det_w / 2) * du + ou along the columns and v = (row + 1/2 - det_h / 2) * dv + ov along the rows
+ *           (tigre.py:423-429); a cone beam's rays leave the source through it at distance DSD, a parallel beam's leave it along
+ *           the pose's axis and DSD is not read; every ray carries near and far.  HOST memory, read during the call; a null `det`
+ *           is refused like any other null pointer ("<entry point>: null pointer")
  */
+typedef struct naf_detector {
+    uint32_t det_w, det_h;                  /* columns, rows */
+    float du, dv, ou, ov, DSD, near, far;   /* metres; near/far as get_near_far */
+    int32_t parallel;                       /* 0 cone, 1 parallel */
+} naf_detector;
 int naf_generate_rays(const float *poses, const int64_t *pixels, int64_t first_pixel, float *rays, uint64_t n,
-                      uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
-                      float DSD, float near, float far, int parallel, void *stream);
+                      uint32_t n_projections, const naf_detector *det, void *stream);
 
 /* G6  the data side of a training step (replaces np.random.choice(..., replace=False) + the fancy-indexing gathers of
  * TIGREDataset.__getitem__, tigre.py:354-372): for each of `n_segments` projections, `rays_per_segment` DISTINCT entries of
@@ -140,6 +149,7 @@ int naf_generate_rays(const float *poses, const int64_t *pixels, int64_t first_p
  * random through a keyed bijection of [0, n_valid) -- draw index i -> valid[perm_seed(i)] -- then the measured value is
  * gathered and the ray generated, all in one launch and without any host round trip.
  *   pixels  i64 [n_draws] out, optional      target  f32 [n_draws] out, optional (= projections[pixel])
+ *   det     the detector of naf_generate_rays (naf_detector, G3)
  *   rays    f32 [n_draws, 8] out
  * [first_draw, first_draw + n_draws) is a slice of the n_segments * rays_per_segment draws (segment-major): ranks of a
  * data-parallel job that pass the same seed each take their slice of ONE draw.  A list shorter than rays_per_segment is
@@ -152,8 +162,7 @@ typedef struct naf_scan_draw {
     uint32_t n_valid[NAF_MAX_DRAW_SEGMENTS];
 } naf_scan_draw;
 int naf_draw_scan_rays(const naf_scan_draw *draw, const float *poses, const float *projections, int64_t *pixels, float *target,
-                       float *rays, uint32_t first_draw, uint32_t n_draws, uint32_t n_projections, uint32_t det_w, uint32_t det_h,
-                       float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel, uint64_t seed,
+                       float *rays, uint32_t first_draw, uint32_t n_draws, uint32_t n_projections, const naf_detector *det, uint64_t seed,
                        void *stream);
 
 /* R4  line integral acc = sum_s sigma_s * dist_s  (render.py:192-201), and its backward.
@@ -368,9 +377,8 @@ typedef struct naf_next_draw {
     int64_t *pixels;           /* optional */
     float *target;             /* optional */
     float *rays;
-    uint32_t first_draw, n_draws, n_projections, det_w, det_h;
-    float du, dv, ou, ov, DSD, near, far;
-    int32_t parallel;
+    uint32_t first_draw, n_draws, n_projections;
+    naf_detector det;
     uint64_t seed;
 } naf_next_draw;
 int naf_render_train_adam_draw(const float *rays, const float *t_rand, const float *target, const float *ray_weight,
@@ -448,17 +456,17 @@ int naf_normalize_inputs(const float *x, uint64_t n, float size, float *out01, i
  *   sample k is evaluated as fma(s_k, d, fma(t0, d, o)) with s_k = (k + 1/2) * seg, straight from k
  * naf_project_rays: rays f32 [n_rays, 8] (16-byte aligned) -> out f32 [n_rays].
  * naf_project_scan: out f32 [n_projections, det_h, det_w]; pixel (p, row, col) integrates the ray naf_generate_rays makes for
- *   flat pixel p*H*W + row*W + col (same poses / detector arguments), generated in the kernel and never stored.
+ *   flat pixel p*H*W + row*W + col (same poses, the same `det`: naf_detector, G3), generated in the kernel and never stored.
  * Empty batches (n_rays == 0, n_projections == 0) return NAF_OK without examining the pointers. */
 int naf_project_rays(const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, const float *rays,
                      uint64_t n_rays, float step, float *out, void *stream);
 int naf_project_scan(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_projections,
-                     uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
-                     int parallel, float step, float *out, void *stream);
+                     const naf_detector *det, float step, float *out, void *stream);
 
 /* P2  back-projector: the transpose of P1.  With A the linear map volume -> projections of naf_project_rays / naf_project_scan,
  * these add A^T y into `volume`.
  *   values / projections  f32, one value y_r per ray: [n_rays], or [n_projections, det_h, det_w] with the rays of naf_project_scan
+ *           (the same poses and `det`: naf_detector, G3)
  *   volume  f32 [n1, n2, n3] as in P1, ACCUMULATED INTO (+=): the caller zeroes it, so a scan can be back-projected in groups of views
  * Ray r takes P1's own t0, t1, len, n and seg in fp32, the same sample positions fma(s_k, d, fma(t0, d, o)) and the same trilinear
  * cell and weights (u_a clamped, i_a = min(floor(u_a), n_a - 2), w_a = u_a - i_a, an axis of one voxel constant: its w_a is 0).
@@ -471,8 +479,7 @@ int naf_project_scan(const float *volume, const uint32_t *dims, const float *dvo
 int naf_backproject_rays(const float *values, const float *rays, uint64_t n_rays, uint32_t n1, uint32_t n2, uint32_t n3,
                          const float *dvoxel, float step, float *volume, void *stream);
 int naf_backproject_scan(const float *projections, const uint32_t *dims, const float *dvoxel, const float *poses,
-                         uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD,
-                         float near, float far, int parallel, float step, float *volume, void *stream);
+                         uint32_t n_projections, const naf_detector *det, float step, float *volume, void *stream);
 
 /* P3  detector-row filter: every row of a stack of projections convolved with one symmetric tap array, the ramp filter of the FDK
  * baseline (reconstruct.fdk).
@@ -508,7 +515,7 @@ int naf_filter_rows_views(const float *in, uint32_t n_views, uint32_t H, uint32_
  *                adds nothing in the transpose; nothing is read or written through it)
  *   poses        f32 [n_scan_views, 12] and  projections  f32 [n_scan_views, det_h, det_w]: the WHOLE scan, read in place
  *   y, r         f32 [n_sub, det_h, det_w], indexed by launch view
- *   the other geometry arguments are naf_project_scan's / naf_backproject_scan's
+ *   det and the other geometry arguments are naf_project_scan's / naf_backproject_scan's
  * naf_sart_residual_scan: pixel (j, row, col) takes the ray naf_generate_rays makes for (v, row, col), P1's own t0, t1, len, n, sample
  *   positions and trilinear cell, and sums A x exactly as P1 does (same operations in the same order), then writes
  *     r = b - A x  (r may be NULL)  and  y = r / len,  b = projections[v, row, col], len = (t1 - t0) * |d| as P1 holds it in fp32
@@ -527,12 +534,10 @@ int naf_filter_rows_views(const float *in, uint32_t n_views, uint32_t H, uint32_
  *   No reduction and no atomics: two calls on the same inputs return the same bits, whatever the alignment of the three pointers.
  * Empty calls (n_sub == 0, n == 0) return NAF_OK without examining the pointers. */
 int naf_sart_residual_scan(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub,
-                           uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
-                           int parallel, float step, const uint32_t *view_index, uint32_t n_scan_views, const float *projections,
+                           const naf_detector *det, float step, const uint32_t *view_index, uint32_t n_scan_views, const float *projections,
                            float *y, float *r, void *stream);
 int naf_sart_backproject_scan(const float *y, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views, const uint32_t *dims,
-                              const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h, float du, float dv, float ou,
-                              float ov, float DSD, float near, float far, int parallel, float step, float *num, float *den,
+                              const float *dvoxel, const float *poses, const naf_detector *det, float step, float *num, float *den,
                               void *stream);
 int naf_sart_update(float *x, float *num, float *den, uint64_t n, float relax, int nonneg, int den_is_reciprocal, int zero_den,
                     void *stream);
@@ -542,6 +547,7 @@ int naf_sart_update(float *x, float *num, float *den, uint64_t n, float relax, i
  *   view_index, n_sub, n_scan_views, poses  as in P4: launch view j is scan view v = view_index[j] (j itself when NULL, then
  *                n_sub <= n_scan_views); poses f32 [n_scan_views, 12] is the whole scan, read in place; an index >= n_scan_views
  *                adds nothing and nothing is read through it
+ *   det          the detector of P1 (naf_detector, G3)
  *   volume       f32 [n1, n2, n3], ACCUMULATED INTO: volume += A_s^T values
  *   den          f32 [n1, n2, n3] or NULL, another volume, ACCUMULATED INTO: den += A_s^T 1, from the same march.  Whether den is
  *                given does not change a bit of `volume`
@@ -561,14 +567,13 @@ int naf_sart_update(float *x, float *num, float *den, uint64_t n, float relax, i
  * n_sub == 0 returns NAF_OK without examining the pointers; a pixel pitch that is 0 or not finite is refused. */
 #define NAF_GATHER_SPAN_BYTES 40u
 int naf_backproject_scan_gather(const float *values, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
-                                const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h,
-                                float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel, float step,
+                                const uint32_t *dims, const float *dvoxel, const float *poses, const naf_detector *det, float step,
                                 float *volume, float *den, void *workspace, size_t workspace_bytes, void *stream);
 
 /* P6  ray-voxel intersection ("Siddon") forward projector: the second forward model beside P1, the one TIGRE's `Ax` takes by
  * default (bit-parity with TIGRE is not pinned).  The volume is piecewise constant: voxel (i, j, k) is the box
  *   [-h_a + i_a * dvoxel_a, -h_a + (i_a + 1) * dvoxel_a] per axis,  h_a = fp32(n_a * dvoxel_a / 2) as in P1,
- * the value is volume[i, j, k] inside it and zero outside the volume.  volume, dvoxel, dims, rays, poses and the detector arguments
+ * the value is volume[i, j, k] inside it and zero outside the volume.  volume, dvoxel, dims, rays, poses and the detector `det`
  * are P1's; there is no sample step (TIGRE's geo.accuracy plays no part).
  * A ray (o, d, near, far) is clipped exactly as P1 clips it: the same float32 slab test intersected with [near, far] in the same
  * order, p0 = fma(t0, d, o), s_end = t1 - t0.  The result is
@@ -591,8 +596,7 @@ int naf_backproject_scan_gather(const float *values, const uint32_t *view_index,
 int naf_project_rays_siddon(const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, const float *rays,
                             uint64_t n_rays, float *out, void *stream);
 int naf_project_scan_siddon(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_projections,
-                            uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
-                            int parallel, float *out, void *stream);
+                            const naf_detector *det, float *out, void *stream);
 
 /* P7  the transpose of P6.  Let A be P6's linear map volume -> projections.  Its entry for ray r and voxel v
  * is the fp32 number P6's walk itself forms for that step, a_rv = fl(fl(s_next - s_prev) * |d|); a ray visits a voxel at most once
@@ -612,8 +616,7 @@ int naf_project_scan_siddon(const float *volume, const uint32_t *dims, const flo
 int naf_backproject_rays_siddon(const float *values, const float *rays, uint64_t n_rays, uint32_t n1, uint32_t n2, uint32_t n3,
                                 const float *dvoxel, float *volume, void *stream);
 int naf_backproject_scan_siddon(const float *projections, const uint32_t *dims, const float *dvoxel, const float *poses,
-                                uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
-                                float DSD, float near, float far, int parallel, float *volume, void *stream);
+                                uint32_t n_projections, const naf_detector *det, float *volume, void *stream);
 
 /* P8  the subset step of OS-SART on the Siddon pair (reconstruct.os_sart(kind="siddon")): P4's step with A
  * = P6 and A^T = P7 restricted to a list of views.  view_index, n_sub, n_scan_views, poses, projections, y and r are P4's (the whole
@@ -635,12 +638,10 @@ int naf_backproject_scan_siddon(const float *projections, const uint32_t *dims, 
  *   and summation order, as in P7.  P6's INVARIANT carries over: no atomic can land outside the volume.
  * Both refuse what their P4 counterparts refuse, before any launch; n_sub == 0 returns NAF_OK without examining the pointers. */
 int naf_sart_residual_scan_siddon(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub,
-                                  uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near,
-                                  float far, int parallel, const uint32_t *view_index, uint32_t n_scan_views, const float *projections,
+                                  const naf_detector *det, const uint32_t *view_index, uint32_t n_scan_views, const float *projections,
                                   float *y, float *r, void *stream);
 int naf_sart_backproject_scan_siddon(const float *y, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
-                                     const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h,
-                                     float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel,
+                                     const uint32_t *dims, const float *dvoxel, const float *poses, const naf_detector *det,
                                      float *num, float *den, void *stream);
 
 /* M1 3-D SSIM of two volumes: the `ssim_3d` evaluation metric of the reference (src/utils/util.py:87-139, train.py:220-288),

@@ -83,20 +83,27 @@ class ScanDraw(ctypes.Structure):
     ]
 
 
+class Detector(ctypes.Structure):
+    """struct naf_detector (include/naf_hip.h): the detector of a scan, as every entry point that makes its rays takes it."""
+    _fields_ = [
+        ("det_w", ctypes.c_uint32), ("det_h", ctypes.c_uint32), ("du", ctypes.c_float), ("dv", ctypes.c_float), ("ou", ctypes.c_float),
+        ("ov", ctypes.c_float), ("DSD", ctypes.c_float), ("near", ctypes.c_float), ("far", ctypes.c_float), ("parallel", ctypes.c_int32),
+    ]
+
+
 class NextDraw(ctypes.Structure):
     """struct naf_next_draw (include/naf_hip.h): the arguments of naf_draw_scan_rays for the NEXT step's pixels."""
     _fields_ = [
         ("draw", ScanDraw), ("poses", ctypes.c_void_p), ("projections", ctypes.c_void_p), ("pixels", ctypes.c_void_p),
         ("target", ctypes.c_void_p), ("rays", ctypes.c_void_p),
-        ("first_draw", ctypes.c_uint32), ("n_draws", ctypes.c_uint32), ("n_projections", ctypes.c_uint32), ("det_w", ctypes.c_uint32),
-        ("det_h", ctypes.c_uint32),
-        ("du", ctypes.c_float), ("dv", ctypes.c_float), ("ou", ctypes.c_float), ("ov", ctypes.c_float), ("DSD", ctypes.c_float),
-        ("near", ctypes.c_float), ("far", ctypes.c_float), ("parallel", ctypes.c_int32), ("seed", ctypes.c_uint64),
+        ("first_draw", ctypes.c_uint32), ("n_draws", ctypes.c_uint32), ("n_projections", ctypes.c_uint32), ("det", Detector),
+        ("seed", ctypes.c_uint64),
     ]
 
 
 # name -> (restype, argtypes); mirrors include/naf_hip.h one to one (checked by tests/test_abi_symbols.py)
 _vp, _u32, _u64, _i32, _f32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_float
+_det, _u32x3, _f32x3 = ctypes.POINTER(Detector), ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3)
 SIGNATURES = {
     "naf_last_error": (ctypes.c_char_p, []),
     "naf_abi_version": (_i32, []),
@@ -109,9 +116,8 @@ SIGNATURES = {
                                            ctypes.c_size_t, _vp]),
     "naf_sample_rays": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _i32, _f32, _u64, _u32, _vp]),
     "naf_fine_depths": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _i32, _i32, _u64, _u32, _vp, _vp]),
-    "naf_draw_scan_rays": (_i32, [ctypes.POINTER(ScanDraw), _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32,
-                                  _f32, _f32, _f32, _i32, _u64, _vp]),
-    "naf_generate_rays": (_i32, [_vp, _vp, ctypes.c_int64, _vp, _u64, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "naf_draw_scan_rays": (_i32, [ctypes.POINTER(ScanDraw), _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _det, _u64, _vp]),
+    "naf_generate_rays": (_i32, [_vp, _vp, ctypes.c_int64, _vp, _u64, _u32, _det, _vp]),
     "naf_integrate_forward": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "naf_integrate_backward": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp]),
     "naf_scatter_overflow_count": (_i32, [ctypes.POINTER(RenderCfg), _u64, _vp, ctypes.POINTER(ctypes.c_uint32)]),
@@ -133,43 +139,30 @@ SIGNATURES = {
     "naf_levels_scatter": (_i32, [_vp, _vp, _vp, ctypes.c_size_t, _u32, _vp, _vp, _u32, ctypes.POINTER(RenderCfg), _u32, _u32, _vp,
                                   ctypes.POINTER(TableAdam), ctypes.POINTER(ctypes.c_int), _vp]),
     "naf_field_forward": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, ctypes.POINTER(RenderCfg), _vp, _vp]),
-    "naf_field_forward_grid": (_i32, [ctypes.POINTER(ctypes.c_double * 3), ctypes.POINTER(ctypes.c_double * 3),
-                                      ctypes.POINTER(ctypes.c_uint32 * 3), _vp, _vp, _vp, _vp, ctypes.POINTER(RenderCfg), _vp,
-                                      ctypes.c_size_t, _vp]),
+    "naf_field_forward_grid": (_i32, [ctypes.POINTER(ctypes.c_double * 3), ctypes.POINTER(ctypes.c_double * 3), _u32x3, _vp, _vp, _vp, _vp,
+                                      ctypes.POINTER(RenderCfg), _vp, ctypes.c_size_t, _vp]),
     "naf_adam_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _u64, _f32, _f32, _f32, _f32, _u32, _f32, _i32, _vp]),
     "naf_normalize_inputs": (_i32, [_vp, _u64, _f32, _vp, _vp, _vp]),
-    "naf_project_rays": (_i32, [_vp, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _u64, _f32, _vp, _vp]),
-    "naf_project_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
-                                _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),
-    "naf_project_rays_siddon": (_i32, [_vp, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _u64, _vp, _vp]),
-    "naf_project_scan_siddon": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32,
-                                       _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
-    "naf_backproject_rays": (_i32, [_vp, _vp, _u64, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _f32, _vp, _vp]),
-    "naf_backproject_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
-                                    _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp]),
-    "naf_backproject_rays_siddon": (_i32, [_vp, _vp, _u64, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _vp]),
-    "naf_backproject_scan_siddon": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32,
-                                           _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp]),
+    "naf_project_rays": (_i32, [_vp, _u32, _u32, _u32, _f32x3, _vp, _u64, _f32, _vp, _vp]),
+    "naf_project_scan": (_i32, [_vp, _u32x3, _f32x3, _vp, _u32, _det, _f32, _vp, _vp]),
+    "naf_project_rays_siddon": (_i32, [_vp, _u32, _u32, _u32, _f32x3, _vp, _u64, _vp, _vp]),
+    "naf_project_scan_siddon": (_i32, [_vp, _u32x3, _f32x3, _vp, _u32, _det, _vp, _vp]),
+    "naf_backproject_rays": (_i32, [_vp, _vp, _u64, _u32, _u32, _u32, _f32x3, _f32, _vp, _vp]),
+    "naf_backproject_scan": (_i32, [_vp, _u32x3, _f32x3, _vp, _u32, _det, _f32, _vp, _vp]),
+    "naf_backproject_rays_siddon": (_i32, [_vp, _vp, _u64, _u32, _u32, _u32, _f32x3, _vp, _vp]),
+    "naf_backproject_scan_siddon": (_i32, [_vp, _u32x3, _f32x3, _vp, _u32, _det, _vp, _vp]),
     "naf_filter_rows": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "naf_filter_rows_views": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "naf_sart_residual_scan": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _u32,
-                                      _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _u32, _vp, _vp, _vp, _vp]),
-    "naf_sart_backproject_scan": (_i32, [_vp, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),
-                                         _vp, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp, _vp]),
+    "naf_sart_residual_scan": (_i32, [_vp, _u32x3, _f32x3, _vp, _u32, _det, _f32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "naf_sart_backproject_scan": (_i32, [_vp, _vp, _u32, _u32, _u32x3, _f32x3, _vp, _det, _f32, _vp, _vp, _vp]),
     "naf_sart_update": (_i32, [_vp, _vp, _vp, _u64, _f32, _i32, _i32, _i32, _vp]),
-    "naf_sart_residual_scan_siddon": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3), _vp, _u32,
-                                             _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _u32, _vp, _vp, _vp, _vp]),
-    "naf_sart_backproject_scan_siddon": (_i32, [_vp, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint32 * 3),
-                                                ctypes.POINTER(ctypes.c_float * 3), _vp, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32,
-                                                _f32, _i32, _vp, _vp, _vp]),
-    "naf_backproject_scan_gather": (_i32, [_vp, _vp, _u32, _u32, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),
-                                           _vp, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _vp, _vp, _vp,
-                                           ctypes.c_size_t, _vp]),
+    "naf_sart_residual_scan_siddon": (_i32, [_vp, _u32x3, _f32x3, _vp, _u32, _det, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "naf_sart_backproject_scan_siddon": (_i32, [_vp, _vp, _u32, _u32, _u32x3, _f32x3, _vp, _det, _vp, _vp, _vp]),
+    "naf_backproject_scan_gather": (_i32, [_vp, _vp, _u32, _u32, _u32x3, _f32x3, _vp, _det, _f32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "naf_ssim_3d_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32]),
     "naf_ssim_3d": (_i32, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, ctypes.c_size_t, _vp]),
-    "naf_resize_volume_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_uint32 * 3)]),
-    "naf_resize_volume": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), _f32, _f32, _vp, ctypes.POINTER(ctypes.c_uint32 * 3), _vp,
-                                 _vp, ctypes.c_size_t, _vp]),
+    "naf_resize_volume_workspace_bytes": (ctypes.c_size_t, [_u32x3, _u32x3]),
+    "naf_resize_volume": (_i32, [_vp, _u32x3, _f32, _f32, _vp, _u32x3, _vp, _vp, ctypes.c_size_t, _vp]),
     "naf_tv_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32]),
     "naf_tv_gradient": (_i32, [_vp, _u32, _u32, _u32, _f32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "naf_tv_descent": (_i32, [_vp, _vp, _u32, _u32, _u32, _f32, _u32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
@@ -179,10 +172,8 @@ SIGNATURES = {
     "naf_cgls_wdot": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
     "naf_cgls_residual_step": (_i32, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
     "naf_cgls_direction_step": (_i32, [_vp, _vp, _vp, _u64, _u32, _u32, _vp, ctypes.c_size_t, _vp]),
-    "naf_volume_sample_points": (_i32, [_vp, _u32, _u32, _u32, ctypes.POINTER(ctypes.c_float * 3), _vp, _u64, _vp, _vp]),
-    "naf_volume_draw_sample": (_i32, [_vp, ctypes.POINTER(ctypes.c_uint32 * 3), ctypes.POINTER(ctypes.c_float * 3),
-                                      ctypes.POINTER(ctypes.c_float * 3), ctypes.POINTER(ctypes.c_float * 3), _u64, _u32, _u32, _vp, _vp,
-                                      _vp]),
+    "naf_volume_sample_points": (_i32, [_vp, _u32, _u32, _u32, _f32x3, _vp, _u64, _vp, _vp]),
+    "naf_volume_draw_sample": (_i32, [_vp, _u32x3, _f32x3, _f32x3, _f32x3, _u64, _u32, _u32, _vp, _vp, _vp]),
     "naf_align_scores_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32, _u32, _u32]),
     "naf_align_shift_scores": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp, ctypes.c_size_t, _vp, _vp]),
     "naf_align_peak": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),

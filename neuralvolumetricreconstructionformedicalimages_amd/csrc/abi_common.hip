@@ -14,6 +14,11 @@ int fail(int code, const char *msg) {
     return code;
 }
 
+int fail_who(const char *who, const char *what) {
+    std::snprintf(g_last_error, sizeof(g_last_error), "%s: %s", who, what);
+    return NAF_ERR_INVALID_ARGUMENT;
+}
+
 int check_launch(const char *kernel) {
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) return NAF_OK;
@@ -87,4 +92,4 @@ extern "C" int naf_profile_collect(char *buf, size_t buflen) {
 }
 
 extern "C" const char *naf_last_error(void) { return naf::g_last_error; }
-extern "C" int naf_abi_version(void) { return 5; }      // 4: naf_hash_encode_workspace_bytes / _backward_ws, NAF_CFG_SCATTER_PAIR12; 5: naf_render_train_adam_draw
+extern "C" int naf_abi_version(void) { return 6; }      // 4: naf_hash_encode_workspace_bytes / _backward_ws, NAF_CFG_SCATTER_PAIR12; 5: naf_render_train_adam_draw; 6: naf_detector in place of the ten detector scalars

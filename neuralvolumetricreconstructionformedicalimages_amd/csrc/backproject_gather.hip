@@ -146,32 +146,27 @@ backproject_gather_kernel(ProjVolume v, GatherGrid grid, float *__restrict__ num
 using namespace naf;
 
 extern "C" int naf_backproject_scan_gather(const float *values, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
-                                           const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w,
-                                           uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
-                                           int parallel, float step, float *volume, float *den, void *workspace,
+                                           const uint32_t *dims, const float *dvoxel, const float *poses, const naf_detector *det,
+                                           float step, float *volume, float *den, void *workspace,
                                            size_t workspace_bytes, void *stream) {
     if (n_sub == 0) return NAF_OK;
     const char *who = "backproject_scan_gather";
     ScanLaunch s;
-    const int rc = make_scan_launch(who, volume, {values}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou, ov, DSD, near, far,
-                                    parallel, step, &s, kScanVoxels, view_index, n_scan_views);
+    const int rc = make_scan_launch(who, volume, {values}, dims, dvoxel, poses, n_sub, det, step, &s, kScanVoxels, view_index,
+                                    n_scan_views);
     if (rc != NAF_OK) return rc;
     const ProjVolume &v = s.v;
     const RayGeo &g = s.g;
-    const uint64_t per_view = (uint64_t)det_w * det_h;
+    const uint64_t per_view = (uint64_t)g.W * g.H;
     const uint64_t bricks_x = (dims[0] + 3u) / 4u, bricks_y = (dims[1] + 3u) / 4u, blocks_z = (dims[2] + 15u) / 16u;
     const char *what = nullptr;
-    if (!(du != 0.0f) || !(dv != 0.0f) || !std::isfinite(du) || !std::isfinite(dv)) what = "pixel pitch must be finite and not 0";
+    if (!(g.du != 0.0f) || !(g.dv != 0.0f) || !std::isfinite(g.du) || !std::isfinite(g.dv)) what = "pixel pitch must be finite and not 0";
     else if (den == volume) what = "volume and den must be two volumes";
     else if (per_view > 0x7fffffffull) what = "too many pixels in a view";
     else if (bricks_x * bricks_y * blocks_z > 0x7fffffffull) what = "too many voxels for one call";
     else if (workspace && (((uintptr_t)workspace) & 7u)) what = "workspace must be 8-byte aligned";
     else if (workspace && workspace_bytes < per_view * NAF_GATHER_SPAN_BYTES) what = "workspace too small for the spans of one view";
-    if (what) {
-        char msg[160];
-        std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (what) return fail_who(who, what);
     GatherGrid grid;
     for (int a = 0; a < 3; ++a) {
         grid.n[a] = v.n[a];

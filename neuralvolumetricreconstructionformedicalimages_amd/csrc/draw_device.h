@@ -18,6 +18,17 @@ struct RayGeo {
     int parallel;           // 0 cone, 1 parallel
 };
 
+// Host: the ABI's detector (include/naf_hip.h, G3) as the kernels take it.  The one place that spells the fields out.
+inline RayGeo ray_geo(const naf_detector &d) { return RayGeo{d.det_w, d.det_h, d.du, d.dv, d.ou, d.ov, d.DSD, d.near, d.far, d.parallel}; }
+
+// Host: the detector checks the entry points share, as the text of the refusal or null.  `n_views`: the views the call's pixels
+// range over.  `marched`: the call marches the rays it makes through a volume, so a cone beam must have its source distance.
+inline const char *detector_refusal(const naf_detector &d, uint32_t n_views, bool marched) {
+    if (d.det_w == 0 || d.det_h == 0 || n_views == 0) return "empty detector";
+    if (marched && !d.parallel && !(d.DSD > 0.0f)) return "DSD must be > 0 for a cone beam";
+    return nullptr;
+}
+
 // The ray of pixel (row, col) of the view with pose P (3x4 row-major [R | t]).
 __device__ __forceinline__ void make_pixel_ray(const float *__restrict__ P, uint32_t row, uint32_t col, const RayGeo &g, float4 *out) {
     // tigre.py:423-429: uu along columns, vv along rows
@@ -114,8 +125,7 @@ __device__ __forceinline__ void draw_one(const DrawJob &j, uint32_t t) {
 
 // host side (render_ops.hip): argument checks of naf_draw_scan_rays -> a DrawJob; the stand-alone launch
 int make_draw_job(const naf_scan_draw *draw, const float *poses, const float *projections, int64_t *pixels, float *target, float *rays,
-                  uint32_t first_draw, uint32_t n_draws, uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou,
-                  float ov, float DSD, float near, float far, int parallel, uint64_t seed, DrawJob *job);
+                  uint32_t first_draw, uint32_t n_draws, uint32_t n_projections, const naf_detector *det, uint64_t seed, DrawJob *job);
 int launch_draw(const DrawJob &job, hipStream_t stream);
 
 }  // namespace naf

@@ -12,6 +12,8 @@ namespace naf {
 
 // Records `msg` as the calling thread's last error and returns `code` (see naf_last_error()).
 int fail(int code, const char *msg);
+// The same for a refused argument, NAF_ERR_INVALID_ARGUMENT, with the message "<who>: <what>".
+int fail_who(const char *who, const char *what);
 // hipGetLastError() -> NAF_OK / NAF_ERR_LAUNCH (message names the kernel).
 int check_launch(const char *kernel);
 

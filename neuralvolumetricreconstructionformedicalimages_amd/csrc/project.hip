@@ -65,12 +65,10 @@ extern "C" int naf_project_rays(const float *volume, uint32_t n1, uint32_t n2, u
 }
 
 extern "C" int naf_project_scan(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses,
-                                uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
-                                float DSD, float near, float far, int parallel, float step, float *out, void *stream) {
+                                uint32_t n_projections, const naf_detector *det, float step, float *out, void *stream) {
     if (n_projections == 0) return NAF_OK;
     ScanLaunch s;
-    const int rc = make_scan_launch("project_scan", volume, {out}, dims, dvoxel, poses, n_projections, det_w, det_h, du, dv, ou, ov, DSD,
-                                    near, far, parallel, step, &s, kLayout);
+    const int rc = make_scan_launch("project_scan", volume, {out}, dims, dvoxel, poses, n_projections, det, step, &s, kLayout);
     if (rc != NAF_OK) return rc;
     { ProfScope prof_("project_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(project_scan_kernel, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream, s.v, poses,

@@ -255,8 +255,7 @@ extern "C" int naf_render_train_adam_draw(const float *rays, const float *t_rand
         return fail(NAF_ERR_INVALID_ARGUMENT, "render_train_adam_draw: the next step's rays / targets must not be the buffers this step reads");
     DrawJob job;
     if (int rc = make_draw_job(&next->draw, next->poses, next->projections, next->pixels, next->target, next->rays, next->first_draw, next->n_draws,
-                               next->n_projections, next->det_w, next->det_h, next->du, next->dv, next->ou, next->ov, next->DSD, next->near,
-                               next->far, next->parallel, next->seed, &job)) return rc;
+                               next->n_projections, &next->det, next->seed, &job)) return rc;
     if (int rc = render_train_adam_impl(b, f, t, adam, &job)) return rc;
     return launch_draw(job, (hipStream_t)stream);            // count == 0 when pass 1 took it along
 }

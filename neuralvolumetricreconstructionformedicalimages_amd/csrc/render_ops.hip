@@ -336,13 +336,13 @@ draw_scan_rays_kernel(DrawJob job) {
 }  // namespace naf
 
 int naf::make_draw_job(const naf_scan_draw *draw, const float *poses, const float *projections, int64_t *pixels, float *target, float *rays,
-                       uint32_t first_draw, uint32_t n_draws, uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv,
-                       float ou, float ov, float DSD, float near, float far, int parallel, uint64_t seed, DrawJob *job) {
-    if (!draw || (n_draws != 0 && (!poses || !rays))) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: null pointer");
+                       uint32_t first_draw, uint32_t n_draws, uint32_t n_projections, const naf_detector *det, uint64_t seed,
+                       DrawJob *job) {
+    if (!draw || !det || (n_draws != 0 && (!poses || !rays))) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: null pointer");
     if (n_draws != 0 && target && !projections) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: target without projections");
     if (draw->n_segments == 0 || draw->n_segments > NAF_MAX_DRAW_SEGMENTS || draw->rays_per_segment == 0)
         return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: n_segments must be in [1, 16] and rays_per_segment > 0");
-    if (det_w == 0 || det_h == 0 || n_projections == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: empty detector");
+    if (const char *what = detector_refusal(*det, n_projections, /*marched=*/false)) return fail_who("draw_scan_rays", what);
     if (n_draws != 0 && (((uintptr_t)rays) & 15u)) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: rays must be 16-byte aligned");
     const uint64_t total = (uint64_t)draw->n_segments * draw->rays_per_segment;
     if (total > 0xffffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: more than 2^32 - 1 draws per call");
@@ -361,8 +361,8 @@ int naf::make_draw_job(const naf_scan_draw *draw, const float *poses, const floa
     }
     job->poses = poses; job->projections = projections; job->pixels = pixels; job->target = target; job->rays = rays;
     job->first = first_draw; job->count = n_draws;
-    job->g = RayGeo{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
-    job->seed = seed; job->n_pixels = (uint64_t)n_projections * det_w * det_h;
+    job->g = ray_geo(*det);
+    job->seed = seed; job->n_pixels = (uint64_t)n_projections * det->det_w * det->det_h;
     return NAF_OK;
 }
 
@@ -375,25 +375,22 @@ int naf::launch_draw(const DrawJob &job, hipStream_t stream) {
 
 extern "C" int naf_draw_scan_rays(const naf_scan_draw *draw, const float *poses, const float *projections, int64_t *pixels,
                                   float *target, float *rays, uint32_t first_draw, uint32_t n_draws, uint32_t n_projections,
-                                  uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near,
-                                  float far, int parallel, uint64_t seed, void *stream) {
+                                  const naf_detector *det, uint64_t seed, void *stream) {
     DrawJob job;
-    if (int rc = make_draw_job(draw, poses, projections, pixels, target, rays, first_draw, n_draws, n_projections, det_w, det_h, du, dv, ou, ov,
-                               DSD, near, far, parallel, seed, &job)) return rc;
+    if (int rc = make_draw_job(draw, poses, projections, pixels, target, rays, first_draw, n_draws, n_projections, det, seed, &job)) return rc;
     return launch_draw(job, (hipStream_t)stream);
 }
 
 extern "C" int naf_generate_rays(const float *poses, const int64_t *pixels, int64_t first_pixel, float *rays, uint64_t n,
-                                 uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou,
-                                 float ov, float DSD, float near, float far, int parallel, void *stream) {
-    if (n != 0 && (!poses || !rays)) return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: null pointer");
-    if (det_w == 0 || det_h == 0 || n_projections == 0) return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: empty detector");
+                                 uint32_t n_projections, const naf_detector *det, void *stream) {
+    if (!det || (n != 0 && (!poses || !rays))) return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: null pointer");
+    if (const char *what = detector_refusal(*det, n_projections, /*marched=*/false)) return fail_who("generate_rays", what);
+    const uint64_t n_pixels = (uint64_t)n_projections * det->det_w * det->det_h;
     if (((uintptr_t)rays) & 15u) return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: rays must be 16-byte aligned");
-    if (!pixels && (first_pixel < 0 || (uint64_t)first_pixel + n > (uint64_t)n_projections * det_w * det_h))
+    if (!pixels && (first_pixel < 0 || (uint64_t)first_pixel + n > n_pixels))
         return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: pixel range outside the scan");
     if (n == 0) return NAF_OK;
-    RayGeo g{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
     { ProfScope prof_("generate_rays_kernel", (hipStream_t)stream); hipLaunchKernelGGL(generate_rays_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, poses, pixels,
-                       first_pixel, rays, n, g, (uint64_t)n_projections * det_w * det_h); }
+                       first_pixel, rays, n, ray_geo(*det), n_pixels); }
     return check_launch("generate_rays_kernel");
 }

@@ -110,13 +110,12 @@ sart_update_kernel(float *__restrict__ x, float *__restrict__ num, float *__rest
 using namespace naf;
 
 extern "C" int naf_sart_residual_scan(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub,
-                                      uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near,
-                                      float far, int parallel, float step, const uint32_t *view_index, uint32_t n_scan_views,
+                                      const naf_detector *det, float step, const uint32_t *view_index, uint32_t n_scan_views,
                                       const float *projections, float *y, float *r, void *stream) {
     if (n_sub == 0) return NAF_OK;
     ScanLaunch s;
-    const int rc = make_scan_launch("sart_residual_scan", volume, {projections, y}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou,
-                                    ov, DSD, near, far, parallel, step, &s, kScanTiles, view_index, n_scan_views);
+    const int rc = make_scan_launch("sart_residual_scan", volume, {projections, y}, dims, dvoxel, poses, n_sub, det, step, &s, kScanTiles,
+                                    view_index, n_scan_views);
     if (rc != NAF_OK) return rc;
     { ProfScope prof_("sart_residual_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(sart_residual_scan_kernel, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream, s.v, poses, s.g,
@@ -125,13 +124,12 @@ extern "C" int naf_sart_residual_scan(const float *volume, const uint32_t *dims,
 }
 
 extern "C" int naf_sart_backproject_scan(const float *y, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
-                                         const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w, uint32_t det_h,
-                                         float du, float dv, float ou, float ov, float DSD, float near, float far, int parallel,
+                                         const uint32_t *dims, const float *dvoxel, const float *poses, const naf_detector *det,
                                          float step, float *num, float *den, void *stream) {
     if (n_sub == 0) return NAF_OK;
     ScanLaunch s;
-    const int rc = make_scan_launch("sart_backproject_scan", num, {y}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou, ov, DSD,
-                                    near, far, parallel, step, &s, kScanTiles, view_index, n_scan_views);
+    const int rc = make_scan_launch("sart_backproject_scan", num, {y}, dims, dvoxel, poses, n_sub, det, step, &s, kScanTiles, view_index,
+                                    n_scan_views);
     if (rc != NAF_OK) return rc;
     if (den == num) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_backproject_scan: num and den must be two volumes");
     { ProfScope prof_("sart_backproject_scan_kernel", (hipStream_t)stream);

@@ -42,33 +42,26 @@ struct ScanLaunch {
 // Host: the checks of a scan call and what its launch needs.  `volume` is any of the call's volume pointers and `others` its
 // further device pointers, all checked for null.  Without a view list, launch view j is scan view j.
 inline int make_scan_launch(const char *who, const float *volume, std::initializer_list<const void *> others, const uint32_t *dims,
-                            const float *dvoxel, const float *poses, uint32_t n_sub, uint32_t det_w, uint32_t det_h, float du, float dv,
-                            float ou, float ov, float DSD, float near, float far, int parallel, float step, ScanLaunch *s,
+                            const float *dvoxel, const float *poses, uint32_t n_sub, const naf_detector *det, float step, ScanLaunch *s,
                             ScanLayout layout = kScanTiles, const uint32_t *view_index = nullptr, uint32_t n_scan_views = 0xffffffffu) {
-    char msg[160];
-    if (!dims) {
-        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (!dims) return fail_who(who, "null pointer");
     const int rc = make_volume(who, volume, dims[0], dims[1], dims[2], dvoxel, step, &s->v);
     if (rc != NAF_OK) return rc;
-    const uint32_t tile_w = layout == kScanRowStrip ? kScanStrip : kProjTile, tile_h = layout == kScanRowStrip ? 1u : kProjTile;
-    const uint32_t tx = (det_w + tile_w - 1u) / tile_w, ty = (det_h + tile_h - 1u) / tile_h;
-    const uint64_t tiles = layout == kScanVoxels ? 0u : (uint64_t)tx * ty;
-    const char *what = nullptr;
-    bool null = !poses;
+    bool null = !poses || !det;
     for (const void *p : others) null |= !p;
-    if (null) what = "null pointer";
-    else if (det_w == 0 || det_h == 0) what = "empty detector";
-    else if (!parallel && !(DSD > 0.0f)) what = "DSD must be > 0 for a cone beam";
-    else if (!view_index && n_sub > n_scan_views) what = "without a view list n_sub must be <= n_scan_views";
-    else if (n_scan_views == 0) what = "a scan of zero views";
-    else if (tiles * n_sub > 0x7fffffffull) what = "too many pixels for one call";
-    if (what) {
-        std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
+    const char *what = null ? "null pointer" : detector_refusal(*det, n_sub, /*marched=*/true);
+    uint32_t tx = 0;
+    uint64_t tiles = 0;
+    if (!what) {
+        const uint32_t tile_w = layout == kScanRowStrip ? kScanStrip : kProjTile, tile_h = layout == kScanRowStrip ? 1u : kProjTile;
+        tx = (det->det_w + tile_w - 1u) / tile_w;
+        tiles = layout == kScanVoxels ? 0u : (uint64_t)tx * ((det->det_h + tile_h - 1u) / tile_h);
+        if (!view_index && n_sub > n_scan_views) what = "without a view list n_sub must be <= n_scan_views";
+        else if (n_scan_views == 0) what = "a scan of zero views";
+        else if (tiles * n_sub > 0x7fffffffull) what = "too many pixels for one call";
     }
-    s->g = RayGeo{det_w, det_h, du, dv, ou, ov, DSD, near, far, parallel};
+    if (what) return fail_who(who, what);
+    s->g = ray_geo(*det);
     s->tiles_x = tx;
     s->tiles_per_view = (uint32_t)tiles;
     return NAF_OK;
@@ -81,11 +74,7 @@ inline int make_ray_launch(const char *who, const float *rays, const void *other
     if (!rays || !other) what = "null pointer";
     else if (((uintptr_t)rays) & 15u) what = "rays must be 16-byte aligned";
     else if ((n_rays + 255u) / 256u > 0x7fffffffull) what = "too many rays for one call";
-    if (what) {
-        char msg[160];
-        std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (what) return fail_who(who, what);
     *blocks = (uint32_t)((n_rays + 255u) / 256u);
     return NAF_OK;
 }

@@ -59,13 +59,11 @@ extern "C" int naf_project_rays_siddon(const float *volume, uint32_t n1, uint32_
 }
 
 extern "C" int naf_project_scan_siddon(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses,
-                                       uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
-                                       float DSD, float near, float far, int parallel, float *out, void *stream) {
+                                       uint32_t n_projections, const naf_detector *det, float *out, void *stream) {
     if (n_projections == 0) return NAF_OK;
     ScanLaunch s;
     SiddonGrid grid;
-    const int rc = make_siddon_scan_launch("project_scan_siddon", volume, {out}, dims, dvoxel, poses, n_projections, det_w, det_h, du, dv,
-                                           ou, ov, DSD, near, far, parallel, &s, &grid);
+    const int rc = make_siddon_scan_launch("project_scan_siddon", volume, {out}, dims, dvoxel, poses, n_projections, det, &s, &grid);
     if (rc != NAF_OK) return rc;
     { ProfScope prof_("siddon_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(siddon_scan_kernel, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream, grid, volume,

@@ -54,13 +54,12 @@ extern "C" int naf_backproject_rays_siddon(const float *values, const float *ray
 }
 
 extern "C" int naf_backproject_scan_siddon(const float *projections, const uint32_t *dims, const float *dvoxel, const float *poses,
-                                           uint32_t n_projections, uint32_t det_w, uint32_t det_h, float du, float dv, float ou,
-                                           float ov, float DSD, float near, float far, int parallel, float *volume, void *stream) {
+                                           uint32_t n_projections, const naf_detector *det, float *volume, void *stream) {
     if (n_projections == 0) return NAF_OK;
     ScanLaunch s;
     SiddonGrid grid;
-    const int rc = make_siddon_scan_launch("backproject_scan_siddon", volume, {projections}, dims, dvoxel, poses, n_projections, det_w,
-                                           det_h, du, dv, ou, ov, DSD, near, far, parallel, &s, &grid);
+    const int rc = make_siddon_scan_launch("backproject_scan_siddon", volume, {projections}, dims, dvoxel, poses, n_projections, det, &s,
+                                           &grid);
     if (rc != NAF_OK) return rc;
     { ProfScope prof_("siddon_backproject_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(siddon_backproject_scan_kernel, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream,

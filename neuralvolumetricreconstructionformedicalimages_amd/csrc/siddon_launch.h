@@ -45,12 +45,10 @@ inline int make_siddon_grid(const char *who, const float *volume, uint32_t n1, u
 
 // Host: make_scan_launch for a scan call that has no sample step, and the grid of its volume.
 inline int make_siddon_scan_launch(const char *who, const float *volume, std::initializer_list<const void *> others,
-                                   const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub, uint32_t det_w,
-                                   uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near, float far,
-                                   int parallel, ScanLaunch *s, SiddonGrid *grid, const uint32_t *view_index = nullptr,
+                                   const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t n_sub,
+                                   const naf_detector *det, ScanLaunch *s, SiddonGrid *grid, const uint32_t *view_index = nullptr,
                                    uint32_t n_scan_views = 0xffffffffu) {
-    const int rc = make_scan_launch(who, volume, others, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou, ov, DSD, near, far,
-                                    parallel, 1.0f, s, kScanTiles, view_index, n_scan_views);
+    const int rc = make_scan_launch(who, volume, others, dims, dvoxel, poses, n_sub, det, 1.0f, s, kScanTiles, view_index, n_scan_views);
     if (rc == NAF_OK) siddon_grid(dims[0], dims[1], dims[2], dvoxel, grid);
     return rc;
 }

@@ -63,14 +63,13 @@ siddon_sart_backproject_scan_kernel(SiddonGrid grid, float *__restrict__ num, fl
 using namespace naf;
 
 extern "C" int naf_sart_residual_scan_siddon(const float *volume, const uint32_t *dims, const float *dvoxel, const float *poses,
-                                             uint32_t n_sub, uint32_t det_w, uint32_t det_h, float du, float dv, float ou, float ov,
-                                             float DSD, float near, float far, int parallel, const uint32_t *view_index,
+                                             uint32_t n_sub, const naf_detector *det, const uint32_t *view_index,
                                              uint32_t n_scan_views, const float *projections, float *y, float *r, void *stream) {
     if (n_sub == 0) return NAF_OK;
     ScanLaunch s;
     SiddonGrid grid;
-    const int rc = make_siddon_scan_launch("sart_residual_scan_siddon", volume, {projections, y}, dims, dvoxel, poses, n_sub, det_w, det_h,
-                                           du, dv, ou, ov, DSD, near, far, parallel, &s, &grid, view_index, n_scan_views);
+    const int rc = make_siddon_scan_launch("sart_residual_scan_siddon", volume, {projections, y}, dims, dvoxel, poses, n_sub, det, &s, &grid,
+                                           view_index, n_scan_views);
     if (rc != NAF_OK) return rc;
     { ProfScope prof_("siddon_sart_residual_scan_kernel", (hipStream_t)stream);
       hipLaunchKernelGGL(siddon_sart_residual_scan_kernel, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream, grid,
@@ -79,14 +78,13 @@ extern "C" int naf_sart_residual_scan_siddon(const float *volume, const uint32_t
 }
 
 extern "C" int naf_sart_backproject_scan_siddon(const float *y, const uint32_t *view_index, uint32_t n_sub, uint32_t n_scan_views,
-                                                const uint32_t *dims, const float *dvoxel, const float *poses, uint32_t det_w,
-                                                uint32_t det_h, float du, float dv, float ou, float ov, float DSD, float near,
-                                                float far, int parallel, float *num, float *den, void *stream) {
+                                                const uint32_t *dims, const float *dvoxel, const float *poses, const naf_detector *det,
+                                                float *num, float *den, void *stream) {
     if (n_sub == 0) return NAF_OK;
     ScanLaunch s;
     SiddonGrid grid;
-    const int rc = make_siddon_scan_launch("sart_backproject_scan_siddon", num, {y}, dims, dvoxel, poses, n_sub, det_w, det_h, du, dv, ou,
-                                           ov, DSD, near, far, parallel, &s, &grid, view_index, n_scan_views);
+    const int rc = make_siddon_scan_launch("sart_backproject_scan_siddon", num, {y}, dims, dvoxel, poses, n_sub, det, &s, &grid, view_index,
+                                           n_scan_views);
     if (rc != NAF_OK) return rc;
     if (den == num) return fail(NAF_ERR_INVALID_ARGUMENT, "sart_backproject_scan_siddon: num and den must be two volumes");
     { ProfScope prof_("siddon_sart_backproject_scan_kernel", (hipStream_t)stream);

@@ -8,6 +8,8 @@
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -86,81 +88,71 @@ class RayGenerator:
             raise NotImplementedError("Unknown CT scanner type!")
         poses = np.stack([angle2pose(geo.DSO, a, geo.tilt_angle)[:3, :4] for a in angles])
         self.poses = torch.Tensor(poses).contiguous().to(self.device)       # float64 -> float32 like tigre.py:419
+        # struct naf_detector, passed by reference to every entry point that makes rays of this scan (projector.Scan's too)
+        self.detector = _abi.Detector(self.W, self.H, float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]),
+                                      float(geo.offDetector[1]), float(geo.DSD), float(self.near), float(self.far),
+                                      int(geo.mode == "parallel"))
 
     @property
     def pixels_per_projection(self):
         return self.W * self.H
 
     def _call(self, pixels, first, n, out):
-        g = self.geo
         if out is None:
             out = torch.empty(n, 8, device=self.device, dtype=torch.float32)
         _abi.check(_abi.lib().naf_generate_rays(
-            _abi.ptr(self.poses), _abi.ptr(pixels), int(first), _abi.ptr(out), int(n), self.n_projections, self.W, self.H,
-            float(g.dDetector[0]), float(g.dDetector[1]), float(g.offDetector[0]), float(g.offDetector[1]), float(g.DSD),
-            float(self.near), float(self.far), int(g.mode == "parallel"), _abi.stream_ptr()), "generate_rays")
+            _abi.ptr(self.poses), _abi.ptr(pixels), int(first), _abi.ptr(out), int(n), self.n_projections, ctypes.byref(self.detector),
+            _abi.stream_ptr()), "generate_rays")
         return out
 
-    def draw(self, valid_lists, rays_per_list, seed, projections=None, first=0, count=None, rays_out=None, want_pixels=True,
-             target_out=None):
-        """`rays_per_list` distinct entries of each list in `valid_lists` (int64 device tensors of flat pixel indices),
-        drawn on the device by `naf_draw_scan_rays` -> (pixels [n] or None, target [n] or None, rays [n, 8]).
-        `first` / `count` select a slice of the len(valid_lists) * rays_per_list draws (data-parallel shards)."""
-        g = self.geo
-        k = len(valid_lists)
-        total = k * int(rays_per_list)
-        count = total - first if count is None else int(count)
+    @staticmethod
+    def _scan_draw(valid_lists, rays_per_list):
+        """The valid-pixel lists of a draw, checked, as a `_abi.ScanDraw` (struct naf_scan_draw)."""
         st = _abi.ScanDraw()
-        st.n_segments, st.rays_per_segment = k, int(rays_per_list)
+        st.n_segments, st.rays_per_segment = len(valid_lists), int(rays_per_list)
         for j, v in enumerate(valid_lists):
             if v.dtype != torch.int64 or not v.is_cuda or not v.is_contiguous():
                 raise RuntimeError("draw: valid-pixel lists must be contiguous int64 device tensors")
             if v.numel() < rays_per_list:
                 raise ValueError("Cannot take a larger sample than population when 'replace=False'")      # tigre.py:357
             st.valid[j], st.n_valid[j] = v.data_ptr(), v.numel()
+        return st
+
+    def _draw_call(self, st, projections, pixels, target, rays, first, count, seed):
+        """One launch of `naf_draw_scan_rays`; the buffers are device pointers (`_abi.ptr`, an address or None)."""
+        _abi.check(_abi.lib().naf_draw_scan_rays(
+            ctypes.byref(st), _abi.ptr(self.poses), projections, pixels, target, rays, first, count, self.n_projections,
+            ctypes.byref(self.detector), seed, _abi.stream_ptr()), "draw_scan_rays")
+
+    def draw(self, valid_lists, rays_per_list, seed, projections=None, first=0, count=None, rays_out=None, want_pixels=True,
+             target_out=None):
+        """`rays_per_list` distinct entries of each list in `valid_lists` (int64 device tensors of flat pixel indices),
+        drawn on the device by `naf_draw_scan_rays` -> (pixels [n] or None, target [n] or None, rays [n, 8]).
+        `first` / `count` select a slice of the len(valid_lists) * rays_per_list draws (data-parallel shards)."""
+        count = len(valid_lists) * int(rays_per_list) - first if count is None else int(count)
+        st = self._scan_draw(valid_lists, rays_per_list)
         rays = rays_out if rays_out is not None else torch.empty(count, 8, device=self.device, dtype=torch.float32)
         pixels = torch.empty(count, device=self.device, dtype=torch.int64) if want_pixels else None
         target = None
         if projections is not None:
             target = target_out if target_out is not None else torch.empty(count, device=self.device, dtype=torch.float32)
-        import ctypes
-        _abi.check(_abi.lib().naf_draw_scan_rays(
-            ctypes.byref(st), _abi.ptr(self.poses), _abi.ptr(projections), _abi.ptr(pixels), _abi.ptr(target), _abi.ptr(rays),
-            int(first), count, self.n_projections, self.W, self.H, float(g.dDetector[0]), float(g.dDetector[1]),
-            float(g.offDetector[0]), float(g.offDetector[1]), float(g.DSD), float(self.near), float(self.far),
-            int(g.mode == "parallel"), int(seed) & (2 ** 64 - 1), _abi.stream_ptr()), "draw_scan_rays")
+        self._draw_call(st, _abi.ptr(projections), _abi.ptr(pixels), _abi.ptr(target), _abi.ptr(rays), int(first), count,
+                        int(seed) & (2 ** 64 - 1))
         return pixels, target, rays
 
     def plan_draw(self, valid_lists, rays_per_list, seed, projections, rays_out, target_out, first=0, count=None):
         """The arguments of `draw` as a `_abi.NextDraw` (struct naf_next_draw) instead of a launch: `NAFEngine.train_step(...,
         next_draw=plan)` lets step k carry the pixel draw of step k + 1 in spare workgroups of its own launches.  `rays_out` [count, 8]
         and `target_out` [count] must not be the buffers step k reads (double-buffer them).  `plan.launch()` runs it stand-alone."""
-        g = self.geo
-        k = len(valid_lists)
-        count = k * int(rays_per_list) - first if count is None else int(count)
         nd = _abi.NextDraw()
-        nd.draw.n_segments, nd.draw.rays_per_segment = k, int(rays_per_list)
-        for j, v in enumerate(valid_lists):
-            if v.dtype != torch.int64 or not v.is_cuda or not v.is_contiguous():
-                raise RuntimeError("draw: valid-pixel lists must be contiguous int64 device tensors")
-            if v.numel() < rays_per_list:
-                raise ValueError("Cannot take a larger sample than population when 'replace=False'")      # tigre.py:357
-            nd.draw.valid[j], nd.draw.n_valid[j] = v.data_ptr(), v.numel()
+        nd.draw = self._scan_draw(valid_lists, rays_per_list)
         nd.poses, nd.projections = self.poses.data_ptr(), projections.data_ptr()
         nd.pixels, nd.target, nd.rays = None, target_out.data_ptr(), rays_out.data_ptr()
-        nd.first_draw, nd.n_draws, nd.n_projections, nd.det_w, nd.det_h = int(first), count, self.n_projections, self.W, self.H
-        nd.du, nd.dv, nd.ou, nd.ov = float(g.dDetector[0]), float(g.dDetector[1]), float(g.offDetector[0]), float(g.offDetector[1])
-        nd.DSD, nd.near, nd.far, nd.parallel = float(g.DSD), float(self.near), float(self.far), int(g.mode == "parallel")
-        nd.seed = int(seed) & (2 ** 64 - 1)
+        nd.first_draw = int(first)
+        nd.n_draws = len(valid_lists) * int(rays_per_list) - first if count is None else int(count)
+        nd.n_projections, nd.det, nd.seed = self.n_projections, self.detector, int(seed) & (2 ** 64 - 1)
         nd._keep = (valid_lists, projections, rays_out, target_out)        # the struct holds raw pointers
-
-        def launch():
-            import ctypes
-            _abi.check(_abi.lib().naf_draw_scan_rays(
-                ctypes.byref(nd.draw), nd.poses, nd.projections, None, nd.target, nd.rays, nd.first_draw, nd.n_draws, nd.n_projections,
-                nd.det_w, nd.det_h, nd.du, nd.dv, nd.ou, nd.ov, nd.DSD, nd.near, nd.far, nd.parallel, nd.seed, _abi.stream_ptr()),
-                "draw_scan_rays")
-        nd.launch = launch
+        nd.launch = lambda: self._draw_call(nd.draw, nd.projections, None, nd.target, nd.rays, nd.first_draw, nd.n_draws, nd.seed)
         return nd
 
     def rays_for_pixels(self, pixels, out=None):

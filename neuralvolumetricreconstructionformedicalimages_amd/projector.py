@@ -76,57 +76,49 @@ class Scan:
         self._dvoxel = _dvoxel(geo.dVoxel)
         self._step = sample_step(geo.dVoxel, geo.accuracy)
 
-    def detector_args(self):
-        g = self.geo
-        return (self.W, self.H, float(g.dDetector[0]), float(g.dDetector[1]), float(g.offDetector[0]), float(g.offDetector[1]),
-                float(g.DSD), float(self.raygen.near), float(self.raygen.far), int(g.mode == "parallel"), self._step)
-
     def _grid_and_poses(self, first=0):
         return ctypes.byref(self._cdims), ctypes.byref(self._dvoxel), _abi.ptr(self.raygen.poses[first:])
 
+    def _detector(self, kind="interpolated"):
+        """The detector and, for the interpolated entry points, the sample step; the Siddon ones have none."""
+        det = ctypes.byref(self.raygen.detector)
+        return (det,) if kind == "siddon" else (det, self._step)
+
+    @staticmethod
+    def _entry(name, kind):
+        """The scan entry point `naf_<name>` of that `kind`, and its name for the error message."""
+        what = name + "_siddon" if kind == "siddon" else name
+        return getattr(_abi.lib(), "naf_" + what), what
+
     def project(self, volume, out, first, count, kind):
         """out[first:first + count] = A volume for those views."""
-        args = (_abi.ptr(volume), *self._grid_and_poses(first), count, *self.detector_args())
-        dst = _abi.ptr(out[first:first + count])
-        if kind == "siddon":                                    # no sample step
-            _abi.check(_abi.lib().naf_project_scan_siddon(*args[:-1], dst, _abi.stream_ptr()), "project_scan_siddon")
-        else:
-            _abi.check(_abi.lib().naf_project_scan(*args, dst, _abi.stream_ptr()), "project_scan")
+        fn, what = self._entry("project_scan", kind)
+        _abi.check(fn(_abi.ptr(volume), *self._grid_and_poses(first), count, *self._detector(kind), _abi.ptr(out[first:first + count]),
+                      _abi.stream_ptr()), what)
 
     def backproject(self, projections, out, first, count, kind="interpolated"):
         """out += A^T projections over the views [first, first + count), by the scatter of that `kind`."""
-        if kind == "siddon":                                    # no sample step
-            _abi.check(_abi.lib().naf_backproject_scan_siddon(
-                _abi.ptr(projections[first:first + count]), *self._grid_and_poses(first), count, *self.detector_args()[:-1],
-                _abi.ptr(out), _abi.stream_ptr()), "backproject_scan_siddon")
-            return
-        _abi.check(_abi.lib().naf_backproject_scan(
-            _abi.ptr(projections[first:first + count]), *self._grid_and_poses(first), count, *self.detector_args(), _abi.ptr(out),
-            _abi.stream_ptr()), "backproject_scan")
+        fn, what = self._entry("backproject_scan", kind)
+        _abi.check(fn(_abi.ptr(projections[first:first + count]), *self._grid_and_poses(first), count, *self._detector(kind),
+                      _abi.ptr(out), _abi.stream_ptr()), what)
 
     def residual(self, volume, views, m, projections, y, r, kind="interpolated"):
         """y, r of the `m` views `views` (None: the first m) by the fused forward walk of that `kind`."""
-        args = (_abi.ptr(volume), *self._grid_and_poses(), m, *self.detector_args())
-        rest = (_index_ptr(views), self.N, _abi.ptr(projections), _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr())
-        if kind == "siddon":                                    # no sample step
-            _abi.check(_abi.lib().naf_sart_residual_scan_siddon(*args[:-1], *rest), "sart_residual_scan_siddon")
-        else:
-            _abi.check(_abi.lib().naf_sart_residual_scan(*args, *rest), "sart_residual_scan")
+        fn, what = self._entry("sart_residual_scan", kind)
+        _abi.check(fn(_abi.ptr(volume), *self._grid_and_poses(), m, *self._detector(kind), _index_ptr(views), self.N,
+                      _abi.ptr(projections), _abi.ptr(y), _abi.ptr(r), _abi.stream_ptr()), what)
 
     def backproject_views(self, y, views, m, num, den, kind="interpolated"):
         """num += A_s^T y and, where `den` is given, den += A_s^T 1 over the same views, by the paired scatter of that `kind`."""
-        args = (_abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self.detector_args())
-        rest = (_abi.ptr(num), _abi.ptr(den), _abi.stream_ptr())
-        if kind == "siddon":                                    # no sample step
-            _abi.check(_abi.lib().naf_sart_backproject_scan_siddon(*args[:-1], *rest), "sart_backproject_scan_siddon")
-        else:
-            _abi.check(_abi.lib().naf_sart_backproject_scan(*args, *rest), "sart_backproject_scan")
+        fn, what = self._entry("sart_backproject_scan", kind)
+        _abi.check(fn(_abi.ptr(y), _index_ptr(views), m, self.N, *self._grid_and_poses(), *self._detector(kind), _abi.ptr(num),
+                      _abi.ptr(den), _abi.stream_ptr()), what)
 
     def gather(self, values, views, m, num, den, workspace, first=0, n_scan_views=None):
         """The gather transpose of `m` launch views: a view list into the whole scan, or without one the views from `first` on."""
         _abi.check(_abi.lib().naf_backproject_scan_gather(
             _abi.ptr(values), _index_ptr(views), m, self.N if n_scan_views is None else n_scan_views, *self._grid_and_poses(first),
-            *self.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.ptr(workspace), 0 if workspace is None else workspace.numel(),
+            *self._detector(), _abi.ptr(num), _abi.ptr(den), _abi.ptr(workspace), 0 if workspace is None else workspace.numel(),
             _abi.stream_ptr()), "backproject_scan_gather")
 
 

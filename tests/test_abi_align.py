@@ -20,7 +20,7 @@ def test_symbols_are_declared_bound_and_exported():
     assert lib.naf_align_scores_workspace_bytes.restype is ctypes.c_size_t
     for name in ("naf_align_shift_scores", "naf_align_peak", "naf_align_shift_views"):
         assert getattr(lib, name).restype is ctypes.c_int
-    assert lib.naf_abi_version() == 5
+    assert lib.naf_abi_version() == 6
     assert "#define NAF_ALIGN_MAX_SHIFT 16u" in text and align.MAX_SHIFT == 16
     assert (align.FLAG_BORDER, align.FLAG_NON_FINITE) == (1, 2)
     assert any(p.endswith("align.hip") for p in build.sources())

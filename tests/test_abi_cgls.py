@@ -18,7 +18,7 @@ def test_symbols_are_declared_bound_and_exported():
         assert name in declared and name in _abi.SIGNATURES and hasattr(raw, name)
         assert len(_abi.SIGNATURES[name][1]) == n_args
     assert lib.naf_cgls_wdot.restype is ctypes.c_int and lib.naf_cgls_workspace_bytes.restype is ctypes.c_size_t
-    assert lib.naf_abi_version() == 5
+    assert lib.naf_abi_version() == 6
     # the layout constants of the header and of the Python module agree
     defines = dict(re.findall(r"#define (NAF_CGLS_[A-Z_]+) (\d+)u", text))
     assert int(defines["NAF_CGLS_SLOT_DELTA"]) == cgls_kernels.SLOT_DELTA and cgls_kernels.SLOT_GAMMA == (0, 1)

@@ -6,7 +6,7 @@ import os
 import re
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"naf_project_rays_siddon": 9, "naf_project_scan_siddon": 17}
+NAMES = {"naf_project_rays_siddon": 9, "naf_project_scan_siddon": 8}
 
 
 def test_symbols_are_declared_bound_and_exported():
@@ -19,8 +19,8 @@ def test_symbols_are_declared_bound_and_exported():
         assert name in declared and name in _abi.SIGNATURES and hasattr(raw, name)
         assert len(_abi.SIGNATURES[name][1]) == n_args and getattr(lib, name).restype is ctypes.c_int
     # one argument fewer than the interpolated counterparts: there is no sample step
-    assert len(_abi.SIGNATURES["naf_project_rays"][1]) == 10 and len(_abi.SIGNATURES["naf_project_scan"][1]) == 18
-    assert lib.naf_abi_version() == 5
+    assert len(_abi.SIGNATURES["naf_project_rays"][1]) == 10 and len(_abi.SIGNATURES["naf_project_scan"][1]) == 9
+    assert lib.naf_abi_version() == 6
 
 
 def test_arguments_are_refused_before_any_launch():
@@ -34,14 +34,15 @@ def test_arguments_are_refused_before_any_launch():
     def project_rays(volume=vol, n=(17, 9, 33), dvoxel=dv, r=rays, n_rays=64, o=out):
         return lib.naf_project_rays_siddon(volume, *n, ctypes.byref(dvoxel) if dvoxel is not None else None, r, n_rays, o, None)
 
-    def project_scan(volume=vol, d=dims, dvoxel=dv, p=poses, n_proj=2, w=24, h=24, DSD=1.5, parallel=0, o=out):
+    def project_scan(volume=vol, d=dims, dvoxel=dv, p=poses, n_proj=2, w=24, h=24, DSD=1.5, parallel=0, o=out, null_det=False):
+        det = _abi.Detector(w, h, 1e-3, 1e-3, 0.0, 0.0, DSD, 0.9, 1.1, parallel)
         return lib.naf_project_scan_siddon(volume, ctypes.byref(d) if d is not None else None,
-                                           ctypes.byref(dvoxel) if dvoxel is not None else None, p, n_proj, w, h, 1e-3, 1e-3, 0.0, 0.0,
-                                           DSD, 0.9, 1.1, parallel, o, None)
+                                           ctypes.byref(dvoxel) if dvoxel is not None else None, p, n_proj,
+                                           None if null_det else ctypes.byref(det), o, None)
 
     # empty batches are successful no-ops whatever the pointers
     assert project_rays(volume=None, dvoxel=None, r=None, n_rays=0, o=None) == 0
-    assert project_scan(volume=None, d=None, dvoxel=None, p=None, n_proj=0, o=None) == 0
+    assert project_scan(volume=None, d=None, dvoxel=None, p=None, n_proj=0, o=None, null_det=True) == 0
     # rays
     assert project_rays(volume=None) == -1 and b"null pointer" in err()
     assert project_rays(dvoxel=None) == -1 and b"null pointer" in err()
@@ -63,6 +64,7 @@ def test_arguments_are_refused_before_any_launch():
     assert project_scan(dvoxel=None) == -1 and b"null pointer" in err()
     assert project_scan(p=None) == -1 and b"null pointer" in err()
     assert project_scan(o=None) == -1 and b"null pointer" in err()
+    assert project_scan(null_det=True) == -1 and b"project_scan_siddon: null pointer" in err()
     assert project_scan(d=(ctypes.c_uint32 * 3)(17, 0, 33)) == -1 and b"zero volume dimension" in err()
     assert project_scan(w=0) == -1 and b"empty detector" in err()
     assert project_scan(h=0) == -1 and b"empty detector" in err()

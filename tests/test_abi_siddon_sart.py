@@ -7,7 +7,7 @@ import os
 import re
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"naf_sart_residual_scan_siddon": 21, "naf_sart_backproject_scan_siddon": 20}
+NAMES = {"naf_sart_residual_scan_siddon": 12, "naf_sart_backproject_scan_siddon": 11}
 
 
 def test_symbols_are_declared_bound_and_exported():
@@ -24,7 +24,7 @@ def test_symbols_are_declared_bound_and_exported():
         assert len(interpolated) == n_args + 1
         assert [a for a in interpolated if a is not ctypes.c_float] == [a for a in _abi.SIGNATURES[name][1] if a is not ctypes.c_float]
     assert "naf_sart_update_siddon" not in declared                     # the third launch is P4's own
-    assert lib.naf_abi_version() == 5
+    assert lib.naf_abi_version() == 6
 
 
 def test_arguments_are_refused_before_any_launch():
@@ -41,25 +41,30 @@ def test_arguments_are_refused_before_any_launch():
     def ref(p):
         return ctypes.byref(p) if p is not None else None
 
+    def detector(w, h, DSD, parallel, null_det):
+        return None if null_det else ctypes.byref(_abi.Detector(w, h, 1e-3, 1e-3, 0.0, 0.0, DSD, 0.9, 1.1, parallel))
+
     def residual(volume=vol, d=dims, dvoxel=dv, p=poses, n_sub=2, w=24, h=24, DSD=1.5, parallel=0, index=None, n_scan=2, b=proj,
-                 y=values, r=None):
-        return lib.naf_sart_residual_scan_siddon(volume, ref(d), ref(dvoxel), p, n_sub, w, h, 1e-3, 1e-3, 0.0, 0.0, DSD, 0.9, 1.1,
-                                                 parallel, index, n_scan, b, y, r, None)
+                 y=values, r=None, null_det=False):
+        return lib.naf_sart_residual_scan_siddon(volume, ref(d), ref(dvoxel), p, n_sub, detector(w, h, DSD, parallel, null_det), index,
+                                                 n_scan, b, y, r, None)
 
     def transpose(y=values, index=None, n_sub=2, n_scan=2, d=dims, dvoxel=dv, p=poses, w=24, h=24, DSD=1.5, parallel=0, num=vol,
-                  den=None):
-        return lib.naf_sart_backproject_scan_siddon(y, index, n_sub, n_scan, ref(d), ref(dvoxel), p, w, h, 1e-3, 1e-3, 0.0, 0.0, DSD,
-                                                    0.9, 1.1, parallel, num, den, None)
+                  den=None, null_det=False):
+        return lib.naf_sart_backproject_scan_siddon(y, index, n_sub, n_scan, ref(d), ref(dvoxel), p,
+                                                    detector(w, h, DSD, parallel, null_det), num, den, None)
 
     R, B = b"sart_residual_scan_siddon", b"sart_backproject_scan_siddon"
     # empty calls are successful no-ops whatever the pointers
-    assert residual(volume=None, d=None, dvoxel=None, p=None, n_sub=0, b=None, y=None) == 0
-    assert transpose(y=None, n_sub=0, d=None, dvoxel=None, p=None, num=None) == 0
+    assert residual(volume=None, d=None, dvoxel=None, p=None, n_sub=0, b=None, y=None, null_det=True) == 0
+    assert transpose(y=None, n_sub=0, d=None, dvoxel=None, p=None, num=None, null_det=True) == 0
     assert transpose(n_sub=0, den=vol) == 0
     for name in ("volume", "d", "dvoxel", "p", "b", "y"):
         assert refused(residual(**{name: None}), b"null pointer", R), name
     for name in ("y", "d", "dvoxel", "p", "num"):
         assert refused(transpose(**{name: None}), b"null pointer", B), name
+    assert refused(residual(null_det=True), b"null pointer", R)
+    assert refused(transpose(null_det=True), b"null pointer", B)
     assert refused(transpose(den=vol), b"two volumes", B)
     for call, who in ((residual, R), (transpose, B)):
         assert refused(call(d=(ctypes.c_uint32 * 3)(17, 0, 33)), b"zero volume dimension", who)

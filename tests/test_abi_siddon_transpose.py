@@ -7,7 +7,7 @@ import os
 import re
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"naf_backproject_rays_siddon": 9, "naf_backproject_scan_siddon": 17}
+NAMES = {"naf_backproject_rays_siddon": 9, "naf_backproject_scan_siddon": 8}
 
 
 def test_symbols_are_declared_bound_and_exported():
@@ -20,8 +20,8 @@ def test_symbols_are_declared_bound_and_exported():
         assert name in declared and name in _abi.SIGNATURES and hasattr(raw, name)
         assert len(_abi.SIGNATURES[name][1]) == n_args and getattr(lib, name).restype is ctypes.c_int
     # one argument fewer than the interpolated counterparts: there is no sample step
-    assert len(_abi.SIGNATURES["naf_backproject_rays"][1]) == 10 and len(_abi.SIGNATURES["naf_backproject_scan"][1]) == 18
-    assert lib.naf_abi_version() == 5
+    assert len(_abi.SIGNATURES["naf_backproject_rays"][1]) == 10 and len(_abi.SIGNATURES["naf_backproject_scan"][1]) == 9
+    assert lib.naf_abi_version() == 6
 
 
 def test_arguments_are_refused_before_any_launch():
@@ -38,15 +38,16 @@ def test_arguments_are_refused_before_any_launch():
     def rays_call(y=values, r=rays, n_rays=64, n=(17, 9, 33), dvoxel=dv, volume=vol):
         return lib.naf_backproject_rays_siddon(y, r, n_rays, *n, ctypes.byref(dvoxel) if dvoxel is not None else None, volume, None)
 
-    def scan_call(y=values, d=dims, dvoxel=dv, p=poses, n_proj=2, w=24, h=24, DSD=1.5, parallel=0, volume=vol):
+    def scan_call(y=values, d=dims, dvoxel=dv, p=poses, n_proj=2, w=24, h=24, DSD=1.5, parallel=0, volume=vol, null_det=False):
+        det = _abi.Detector(w, h, 1e-3, 1e-3, 0.0, 0.0, DSD, 0.9, 1.1, parallel)
         return lib.naf_backproject_scan_siddon(y, ctypes.byref(d) if d is not None else None,
-                                               ctypes.byref(dvoxel) if dvoxel is not None else None, p, n_proj, w, h, 1e-3, 1e-3, 0.0,
-                                               0.0, DSD, 0.9, 1.1, parallel, volume, None)
+                                               ctypes.byref(dvoxel) if dvoxel is not None else None, p, n_proj,
+                                               None if null_det else ctypes.byref(det), volume, None)
 
     R, C = b"backproject_rays_siddon", b"backproject_scan_siddon"
     # empty batches are successful no-ops whatever the pointers
     assert rays_call(y=None, r=None, n_rays=0, dvoxel=None, volume=None) == 0
-    assert scan_call(y=None, d=None, dvoxel=None, p=None, n_proj=0, volume=None) == 0
+    assert scan_call(y=None, d=None, dvoxel=None, p=None, n_proj=0, volume=None, null_det=True) == 0
     # rays
     assert refused(rays_call(volume=None), b"null pointer", R)
     assert refused(rays_call(dvoxel=None), b"null pointer", R)
@@ -68,6 +69,7 @@ def test_arguments_are_refused_before_any_launch():
     assert refused(scan_call(dvoxel=None), b"null pointer", C)
     assert refused(scan_call(p=None), b"null pointer", C)
     assert refused(scan_call(y=None), b"null pointer", C)
+    assert refused(scan_call(null_det=True), b"null pointer", C)
     assert refused(scan_call(d=(ctypes.c_uint32 * 3)(17, 0, 33)), b"zero volume dimension", C)
     assert refused(scan_call(w=0), b"empty detector", C)
     assert refused(scan_call(h=0), b"empty detector", C)

@@ -19,7 +19,7 @@ def test_symbols_are_declared_bound_and_exported():
         assert len(_abi.SIGNATURES[name][1]) == n_args
     assert lib.naf_stripe_workspace_bytes.restype is ctypes.c_size_t
     assert lib.naf_stripe_remove_sorting.restype is ctypes.c_int
-    assert lib.naf_abi_version() == 5
+    assert lib.naf_abi_version() == 6
     assert "#define NAF_STRIPE_MAX_SIZE 63u" in text and stripe.MAX_SIZE == 63
     assert "#define NAF_STRIPE_MAX_VIEWS 4096u" in text and stripe.MAX_VIEWS == 4096
     assert any(p.endswith("stripe.hip") for p in build.sources())

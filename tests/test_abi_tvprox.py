@@ -18,7 +18,7 @@ def test_symbols_are_declared_bound_and_exported():
         assert name in declared and name in _abi.SIGNATURES and hasattr(raw, name)
         assert getattr(lib, name).restype is ctypes.c_int
     assert len(_abi.SIGNATURES["naf_tv_prox_step"][1]) == 11 and len(_abi.SIGNATURES["naf_tv_prox_primal"][1]) == 9
-    assert lib.naf_abi_version() == 5
+    assert lib.naf_abi_version() == 6
 
 
 def test_arguments_are_refused_before_any_launch():

@@ -18,7 +18,7 @@ def test_symbols_are_declared_bound_and_exported():
         assert name in declared and name in _abi.SIGNATURES and hasattr(raw, name)
         assert len(_abi.SIGNATURES[name][1]) == n_args
     assert lib.naf_volume_sample_points.restype is ctypes.c_int and lib.naf_volume_draw_sample.restype is ctypes.c_int
-    assert lib.naf_abi_version() == 5
+    assert lib.naf_abi_version() == 6
     assert "#define NAF_VOLUME_SAMPLE_MAX_EXTENT 16777216u" in text
     # the new sources are part of what a build compiles and of the staleness fingerprint
     assert any(p.endswith("volume_sample.hip") for p in build.sources())

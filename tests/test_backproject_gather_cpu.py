@@ -106,12 +106,14 @@ def test_entry_point_refusals_need_no_gpu():
     dims, dv = (ctypes.c_uint32 * 3)(4, 4, 4), (ctypes.c_float * 3)(1e-3, 1e-3, 1e-3)
 
     def call(values=one, index=None, n_sub=2, n_scan=2, poses=one, w=8, h=8, du=1e-3, dvp=1e-3, dsd=1.5, volume=one, den=None,
-             work=None, size=0, d=dims):
-        return lib.naf_backproject_scan_gather(values, index, n_sub, n_scan, d and ctypes.byref(d), ctypes.byref(dv), poses, w, h, du,
-                                               dvp, 0.0, 0.0, dsd, 0.0, 2.0, 0, 5e-4, volume, den, work, size, None)
+             work=None, size=0, d=dims, null_det=False):
+        det = None if null_det else ctypes.byref(_abi.Detector(w, h, du, dvp, 0.0, 0.0, dsd, 0.0, 2.0, 0))
+        return lib.naf_backproject_scan_gather(values, index, n_sub, n_scan, d and ctypes.byref(d), ctypes.byref(dv), poses, det, 5e-4,
+                                               volume, den, work, size, None)
 
-    assert call(n_sub=0, values=None, poses=None, volume=None, d=None) == 0
+    assert call(n_sub=0, values=None, poses=None, volume=None, d=None, null_det=True) == 0
     for kwargs, text in (({"values": None}, b"null pointer"), ({"volume": None}, b"null pointer"), ({"w": 0}, b"empty detector"),
+                         ({"null_det": True}, b"backproject_scan_gather: null pointer"),
                          ({"dsd": 0.0}, b"DSD"), ({"du": 0.0}, b"pitch"), ({"dvp": float("nan")}, b"pitch"),
                          ({"n_sub": 3}, b"n_sub must be <="), ({"den": one}, b"two volumes"),
                          ({"work": ctypes.c_void_p(12), "size": 1 << 20}, b"8-byte aligned"),

@@ -82,14 +82,15 @@ def test_near_and_far_cut_through_the_volume():
     want = B.backproject_rays(c["y"].reshape(-1), geo.dVoxel, rays, dims, geo.accuracy)
     gen = RayGenerator(geo, c["angles"], "cuda")
     N, H, W = c["y"].shape
+    det = _abi.Detector(W, H, float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]), float(geo.offDetector[1]),
+                        float(geo.DSD), near, far, 0)
     for table in (True, False):
         out = torch.zeros(dims, device="cuda")
         work = projector.gather_workspace(N, H, W, "cuda", table)
         _abi.check(_abi.lib().naf_backproject_scan_gather(
             _abi.ptr(_dev(c["y"])), None, N, N, ctypes.byref((ctypes.c_uint32 * 3)(*dims)), ctypes.byref(projector._dvoxel(geo.dVoxel)),
-            _abi.ptr(gen.poses), W, H, float(geo.dDetector[0]), float(geo.dDetector[1]), float(geo.offDetector[0]),
-            float(geo.offDetector[1]), float(geo.DSD), near, far, 0, projector.sample_step(geo.dVoxel, geo.accuracy), _abi.ptr(out), None,
-            _abi.ptr(work), 0 if work is None else work.numel(), _abi.stream_ptr()), "backproject_scan_gather")
+            _abi.ptr(gen.poses), ctypes.byref(det), projector.sample_step(geo.dVoxel, geo.accuracy), _abi.ptr(out), None, _abi.ptr(work),
+            0 if work is None else work.numel(), _abi.stream_ptr()), "backproject_scan_gather")
         _check(out, want, f"near / far, span table {table}")
 
 
@@ -265,7 +266,7 @@ def test_out_of_range_view_index_adds_nothing():
         work = projector.gather_workspace(len(index), scan.H, scan.W, "cuda", table)
         _abi.check(_abi.lib().naf_backproject_scan_gather(
             _abi.ptr(values), _abi.ptr(idx), len(index), scan.N, ctypes.byref(scan._cdims), ctypes.byref(scan._dvoxel),
-            _abi.ptr(scan.raygen.poses), *scan.detector_args(), _abi.ptr(num), _abi.ptr(den), _abi.ptr(work),
+            _abi.ptr(scan.raygen.poses), ctypes.byref(scan.raygen.detector), scan._step, _abi.ptr(num), _abi.ptr(den), _abi.ptr(work),
             0 if work is None else work.numel(), _abi.stream_ptr()), "backproject_scan_gather")
         return num, den
 

@@ -37,13 +37,14 @@ def test_abi_entry_points_and_argument_checks():
     def rays(vol, n1, dvox, r, step, out):
         return lib.naf_project_rays(vol, n1, 4, 4, dvox, r, 10, step, out, None)
 
-    def scan(vol, d, dvox, poses, step, out):
-        return lib.naf_project_scan(vol, d, dvox, poses, 3, 8, 8, 1e-3, 1e-3, 0.0, 0.0, 1.5, 0.5, 1.5, 0, step, out, None)
+    def scan(vol, d, dvox, poses, step, out, det=ctypes.byref(_abi.Detector(8, 8, 1e-3, 1e-3, 0.0, 0.0, 1.5, 0.5, 1.5, 0))):
+        return lib.naf_project_scan(vol, d, dvox, poses, 3, det, step, out, None)
 
     for rc in (rays(None, 4, ctypes.byref(dv), one, 5e-4, one), rays(one, 4, None, one, 5e-4, one),
                rays(one, 4, ctypes.byref(dv), None, 5e-4, one), rays(one, 4, ctypes.byref(dv), one, 5e-4, None),
                scan(None, ctypes.byref(dims), ctypes.byref(dv), one, 5e-4, one), scan(one, None, ctypes.byref(dv), one, 5e-4, one),
-               scan(one, ctypes.byref(dims), ctypes.byref(dv), None, 5e-4, one), scan(one, ctypes.byref(dims), ctypes.byref(dv), one, 5e-4, None)):
+               scan(one, ctypes.byref(dims), ctypes.byref(dv), None, 5e-4, one), scan(one, ctypes.byref(dims), ctypes.byref(dv), one, 5e-4, None),
+               scan(one, ctypes.byref(dims), ctypes.byref(dv), one, 5e-4, one, det=None)):
         assert rc == -1
         assert b"null pointer" in lib.naf_last_error()
     assert rays(one, 0, ctypes.byref(dv), one, 5e-4, one) == -1
@@ -62,7 +63,11 @@ def test_abi_entry_points_and_argument_checks():
         _abi.check(rays(one, 4, ctypes.byref(bad), one, 5e-4, one), "project_rays")
     # empty batches are no-ops whose pointers are not examined
     assert lib.naf_project_rays(None, 0, 0, 0, None, None, 0, 0.0, None, None) == 0
-    assert lib.naf_project_scan(None, None, None, None, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0.0, None, None) == 0
+    assert lib.naf_project_scan(None, None, None, None, 0, None, 0.0, None, None) == 0
+    # the transpose takes the same detector: a null one is refused on a call that is not empty
+    assert lib.naf_backproject_scan(one, ctypes.byref(dims), ctypes.byref(dv), one, 3, None, 5e-4, one, None) == -1
+    assert b"backproject_scan: null pointer" in lib.naf_last_error()
+    assert lib.naf_backproject_scan(None, None, None, None, 0, None, 0.0, None, None) == 0
 
 
 def test_projector_refuses_cpu_tensors_and_origin_offsets():

@@ -133,15 +133,21 @@ def test_library_rejects_bad_arguments():
     dv = (ctypes.c_float * 3)(1e-3, 1e-3, 1e-3)
     det = (8, 8, 1e-3, 1e-3, 0.0, 0.0, 1.5, 0.5, 1.5, 0, 5e-4)          # det_w .. step
 
+    def geometry(geo):
+        """(struct naf_detector by reference, step); geo = None: a null detector."""
+        return (None, det[10]) if geo is None else (ctypes.byref(_abi.Detector(*geo[:10])), geo[10])
+
     def residual(volume=one, d=dims, voxel=dv, poses=two, n_sub=2, geo=det, index=None, n_scan=2, proj=three, y=three, r=None):
-        return lib.naf_sart_residual_scan(volume, d, voxel, poses, n_sub, *geo, index, n_scan, proj, y, r, None)
+        return lib.naf_sart_residual_scan(volume, d, voxel, poses, n_sub, *geometry(geo), index, n_scan, proj, y, r, None)
 
     def transpose(y=three, index=None, n_sub=2, n_scan=2, d=dims, voxel=dv, poses=two, geo=det, num=one, den=None):
-        return lib.naf_sart_backproject_scan(y, index, n_sub, n_scan, d, voxel, poses, *geo, num, den, None)
+        return lib.naf_sart_backproject_scan(y, index, n_sub, n_scan, d, voxel, poses, *geometry(geo), num, den, None)
 
     for call, word in ((lambda: residual(volume=None), b"null pointer"), (lambda: residual(d=None), b"null pointer"),
                        (lambda: residual(voxel=None), b"null pointer"), (lambda: residual(poses=None), b"null pointer"),
                        (lambda: residual(proj=None), b"null pointer"), (lambda: residual(y=None), b"null pointer"),
+                       (lambda: residual(geo=None), b"sart_residual_scan: null pointer"),
+                       (lambda: transpose(geo=None), b"sart_backproject_scan: null pointer"),
                        (lambda: residual(d=flat), b"zero volume dimension"),
                        (lambda: residual(geo=(0,) + det[1:]), b"empty detector"),
                        (lambda: residual(geo=det[:6] + (0.0,) + det[7:]), b"DSD"),
@@ -160,7 +166,7 @@ def test_library_rejects_bad_arguments():
                        (lambda: lib.naf_sart_update(ctypes.c_void_p(one.value + 2), two, three, 8, 1.0, 1, 0, 0, None), b"aligned")):
         assert call() == -1
         assert word in lib.naf_last_error(), (word, lib.naf_last_error())
-    assert residual(volume=None, d=None, voxel=None, poses=None, n_sub=0, proj=None, y=None) == 0
-    assert transpose(y=None, n_sub=0, d=None, voxel=None, poses=None, num=None) == 0
+    assert residual(volume=None, d=None, voxel=None, poses=None, n_sub=0, geo=None, proj=None, y=None) == 0
+    assert transpose(y=None, n_sub=0, d=None, voxel=None, poses=None, geo=None, num=None) == 0
     assert lib.naf_sart_update(None, None, None, 0, 1.0, 1, 0, 0, None) == 0
-    assert lib.naf_abi_version() == 5
+    assert lib.naf_abi_version() == 6
