@@ -1,4 +1,4 @@
-// backproject_device.h -- the ray scatter of the transpose (include/naf_hip.h P2), shared by backproject.hip
+// backproject_device.h -- the ray scatter of the transpose (include/naf_hip.h P2), shared by projector.hip
 // and sart.hip: the march over a ray's samples with the merge of consecutive samples that share a cell.  What a finished cell adds
 // to memory is the caller's `Deposit`: one volume for P2, the numerator / column-sum pair of the OS-SART subset step for P4.
 #pragma once

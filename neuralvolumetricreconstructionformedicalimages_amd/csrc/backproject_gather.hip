@@ -1,6 +1,6 @@
 // backproject_gather.hip -- the transpose of the forward projector in gather form for gfx950 (include/naf_hip.h P5, DESIGN.md
 // section 17): naf_backproject_scan_gather adds A^T y into a volume, and the column sums A^T 1 into a second one, with no atomics
-// and a fixed summation order, so two calls on the same inputs return the same bits.  It is the operator of backproject.hip and
+// and a fixed summation order, so two calls on the same inputs return the same bits.  It is the operator of projector.hip and
 // sart.hip, not a voxel-driven model: every weight is the scatter's own, from project_device.h (ray_span, span_point,
 // trilinear_cell); backproject_gather_device.h only decides which (pixel, sample) pairs a voxel has to look at.
 //

@@ -1,5 +1,5 @@
 // project_device.h -- the pieces of the projection definition (include/naf_hip.h P1) that the forward
-// projector (project.hip), its transpose (backproject.hip) and the OS-SART subset kernels (sart.hip) must share to the bit: the
+// projector, its transpose (both projector.hip) and the OS-SART subset kernels (sart.hip) must share to the bit: the
 // volume's grid, the clipped segment of a ray with its sample count, the sample positions, the trilinear cell with its three
 // weights, and the forward's sum over the samples.
 #pragma once

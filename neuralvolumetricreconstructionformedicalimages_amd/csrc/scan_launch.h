@@ -28,7 +28,7 @@ __device__ __forceinline__ uint32_t scan_view(const ViewList &l, uint32_t j) {
 
 enum ScanLayout {
     kScanTiles,      // 16 x 16 pixels per workgroup
-    kScanRowStrip,   // 256 consecutive pixels of one detector row per workgroup (project.hip's A/B)
+    kScanRowStrip,   // 256 consecutive pixels of one detector row per workgroup (the interpolated forward's A/B)
     kScanVoxels,     // no pixel grid: the launch is over the volume
 };
 constexpr uint32_t kScanStrip = 256;

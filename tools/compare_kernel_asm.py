@@ -6,16 +6,21 @@ amdgpu metadata.  The only normalisation: the running function number in local l
 comments, ...), which follows the ORDER of the functions in the unit, and the column of the comment behind such a label.  It reads the two files and nothing else.
 
     python tools/compare_kernel_asm.py before.s after.s        exit 0: every function identical
+
+--rename OLD=NEW (repeatable) reads the symbol NEW of after.s as OLD, for a kernel that the change renamed.
 """
+import argparse
 import re
 import sys
 
 LOCAL = re.compile(r"(\.L|\b)(BB|func_end|func_begin|JTI|tmp|CPI)\d+(?=_|\b)")
 
 
-def functions(path):
+def functions(path, rename=()):
     """-> ({symbol: text}, kernel symbols, the .ident line)."""
     text = open(path).read()
+    for old, new in rename:
+        text = text.replace(new, old)
     meta_at = text.index("\t.amdgpu_metadata")
     body, meta = text[:meta_at], text[meta_at:]
     out, kernels = {}, set()
@@ -41,11 +46,16 @@ def functions(path):
 
 
 def main():
-    a, ka, ia = functions(sys.argv[1])
-    b, kb, ib = functions(sys.argv[2])
+    ap = argparse.ArgumentParser()
+    ap.add_argument("before")
+    ap.add_argument("after")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
+    args = ap.parse_args()
+    a, ka, ia = functions(args.before)
+    b, kb, ib = functions(args.after, [r.split("=", 1) for r in args.rename])
     print("compiler:", ia if ia == ib else f"{ia} / {ib}")
     differ = sorted(n for n in a.keys() & b.keys() if a[n] != b[n])
-    for label, names in (("only in " + sys.argv[1], sorted(a.keys() - b.keys())), ("only in " + sys.argv[2], sorted(b.keys() - a.keys())),
+    for label, names in (("only in " + args.before, sorted(a.keys() - b.keys())), ("only in " + args.after, sorted(b.keys() - a.keys())),
                          ("differ", differ)):
         for n in names:
             print(f"{label}: {n}")

@@ -14,7 +14,7 @@
 //                     (so the sent terms are y * len), and it is not called at all for y == 0, an empty or a non-finite span;
 //   pair deposit      with a den: wanted() whatever y is, called with the same steps, y == 0 included; without a den: wanted() is
 //                     y != 0, called with the same steps, and nothing reaches den.
-// The deposits here record what siddon_transpose calls them with and add as csrc/siddon_launch.h's do (den before num); the device
+// The deposits here record what siddon_transpose calls them with and add as csrc/projector_pair.h's do (den before num); the device
 // deposits themselves, the kernels' ray generation and their tiling are not compiled into this program: the GPU tests cover them.
 // No GPU, no HIP.
 //
@@ -68,7 +68,7 @@ naf::SiddonKind restate(const naf::SiddonGrid &grid, const naf::SiddonRay &ray, 
     return kind;
 }
 
-// The deposits: csrc/siddon_launch.h's rules with `+=` for the atomic, and a record of every call.
+// The deposits: csrc/projector_pair.h's rules with `+=` for the atomic, and a record of every call.
 struct ValueDeposit {
     float *volume;
     float y;
