@@ -869,6 +869,46 @@ size_t naf_stripe_workspace_bytes(uint32_t N, uint32_t H, uint32_t W, uint32_t r
 int naf_stripe_remove_sorting(const float *p, uint32_t N, uint32_t H, uint32_t W, uint32_t size, void *ws, size_t ws_bytes, float *out,
                               void *stream);
 
+/* A3  raw-frame conditioning: flat-field, zinger / dead-pixel median and -log in one launch (frames.py).  DESIGN.md section 29; the
+ * per-pixel arithmetic is csrc/frames_device.h.  The inverse of the forward model of dataset.add_noise, I = i0 exp(-p), for measured
+ * frames.
+ *   raw        [N, H, W] C-contiguous, float32 (raw_dtype NAF_FRAMES_RAW_F32) or uint16 (NAF_FRAMES_RAW_U16, converted exactly)
+ *   dark, flat f32 [H, W], one averaged frame each
+ *   bad        u8 [H, W] or NULL: non-zero marks a known defective pixel
+ *   size       = 2 h + 1 in {3, 5, 7}, size <= H and size <= W
+ *   dif        f32 >= 0, finite;   t_min  f32 > 0, finite
+ *   flags      NAF_FRAMES_LOG: write -ln;  NAF_FRAMES_CLAMP_NONNEG (only with LOG): no result below zero
+ *   out        f32 [N, H, W];   counts  u32 [N, 2] (+=) or NULL
+ * Per view i and pixel (v, u), every operation one IEEE fp32 operation in the order written, the division correctly rounded:
+ *   1. den = flat[v,u] - dark[v,u],  num = raw[i,v,u] - dark[v,u],  t = num / den
+ *   2. the pixel is bad in this view iff bad[v,u] != 0, or !(den > 0), or t is not finite ((t - t) != 0)
+ *   3. the window is the size x size pixels (r(v + a), r(u + b)), a, b in [-h, h], of the same view, r the reflection of A2 (the edge
+ *      sample repeated: scipy's mode="reflect"); an entry counts once per occurrence.  With c entries that are not bad, m is the one
+ *      of rank (c - 1) / 2 (integer division: the lower median) in the order of A2's key of their bits; c == 0: m = 1.0f
+ *   4. t' = m for a bad pixel; otherwise t' = m if (t - m) > dif (bright outliers only), else t' = t
+ *   5. out = t', or with LOG  p = -logf(fmaxf(t', t_min)),  and with CLAMP_NONNEG on top  p > 0 ? p : +0  (fmaxf(p, 0) with the
+ *      zero's sign pinned: -logf(1) is -0, which the clamp returns as +0)
+ *   6. counts[i, 0] += the pixels of view i replaced as outliers, counts[i, 1] += those replaced as bad: summed within a workgroup and
+ *      added with one integer atomic each, so equal inputs give equal counts.  The caller zeroes them.
+ * Without LOG every output is a quotient of step 1 or one of the window's floats: equal inputs give equal bits, the bits of a float32
+ * numpy restatement (tests/_frames_oracle.py).  With LOG the result is as accurate as the device's logf.
+ * `out` must not overlap raw, dark, flat or bad: a workgroup reads the halo of its tile from `raw` while its neighbours store, so
+ * aliasing is refused rather than given a workspace.
+ * Refused before any launch (NAF_ERR_INVALID_ARGUMENT): a null raw, dark, flat or out; an unknown raw_dtype; H or W above 2^24; size
+ * not in {3, 5, 7} or above H or W; dif or t_min not finite or out of range; unknown flag bits, or CLAMP without LOG; a float32 raw,
+ * dark, flat, out or counts that is not 4-byte aligned, a uint16 raw that is not 2-byte aligned; out overlapping an input; more than
+ * 2^31 - 1 tiles of NAF_FRAMES_TILE_H x NAF_FRAMES_TILE_W pixels over all views.  N H W == 0 returns NAF_OK without examining anything
+ * else.  Element offsets are 64-bit.  The call takes the stream, allocates nothing and never synchronises. */
+#define NAF_FRAMES_RAW_F32 0
+#define NAF_FRAMES_RAW_U16 1
+#define NAF_FRAMES_LOG 1u
+#define NAF_FRAMES_CLAMP_NONNEG 2u
+#define NAF_FRAMES_MAX_SIZE 7u
+#define NAF_FRAMES_TILE_H 16u
+#define NAF_FRAMES_TILE_W 64u
+int naf_frames_condition(const void *raw, int raw_dtype, const float *dark, const float *flat, const uint8_t *bad, uint32_t N, uint32_t H,
+                         uint32_t W, uint32_t size, float dif, float t_min, uint32_t flags, float *out, uint32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

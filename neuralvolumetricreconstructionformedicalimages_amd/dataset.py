@@ -303,3 +303,75 @@ def add_stripes(projs, fraction, sigma, generator):
     gain = np.where(defective, np.maximum(1.0 + float(sigma) * rng.standard_normal(p.shape[1:]), 0.1), 1.0)
     out = (-np.log(np.exp(-p) * gain[None])).astype(np.float32)
     return torch.from_numpy(out) if as_tensor else out
+
+
+def _host_array(a, who, name, ndim):
+    """`a` (numpy array or CPU tensor) as a float64 array of `ndim` dimensions -> (array, whether it was a tensor)."""
+    as_tensor = isinstance(a, torch.Tensor)
+    if as_tensor and a.is_cuda:
+        raise ValueError(f"{who}: {name} must be on the host")
+    x = (a.numpy() if as_tensor else np.asarray(a)).astype(np.float64)
+    if x.ndim != ndim:
+        raise ValueError(f"{who}: {name} must have {ndim} dimensions, got {x.shape}")
+    return x, as_tensor
+
+
+def _numpy_generator(generator):
+    return generator if isinstance(generator, np.random.Generator) else np.random.default_rng(generator)
+
+
+def raw_frames(projs, i0, flat, dark, generator=None):
+    """The detector frames behind line integrals `projs` [N, H, W] (numpy array or CPU tensor; host side), the forward model whose
+    inverse `frames.condition` is: raw = dark + (flat - dark) exp(-p), with `flat` and `dark` one [H, W] frame each in counts.
+    `i0` is the photon count a transmission of one stands for: with a `generator` (a numpy Generator or an int seed for one) the
+    transmission takes the Poisson noise of `add_noise`, Poisson(i0 exp(-p)) / i0, before it is scaled; without one the frames are
+    noiseless and `i0` is not read.  Computed in float64, returned as float32 of the kind given; equal seeds give equal bits."""
+    who = "raw_frames"
+    p, as_tensor = _host_array(projs, who, "projs", 3)
+    f, _ = _host_array(flat, who, "flat", 2)
+    d, _ = _host_array(dark, who, "dark", 2)
+    if f.shape != p.shape[1:] or d.shape != p.shape[1:]:
+        raise ValueError(f"{who}: flat and dark must be {p.shape[1:]}, got {f.shape} and {d.shape}")
+    trans = np.exp(-p)
+    if generator is not None:
+        if not float(i0) > 0.0:
+            raise ValueError(f"{who}: i0 must be above zero, got {i0}")
+        trans = _numpy_generator(generator).poisson(float(i0) * trans) / float(i0)
+    out = (d[None] + (f - d)[None] * trans).astype(np.float32)
+    return torch.from_numpy(out) if as_tensor else out
+
+
+def add_zingers(raw, fraction, gain, generator, isolation=1):
+    """Zingers on frames `raw` [N, H, W] (numpy array or CPU tensor; host side): every sample is drawn with probability `fraction`,
+    independently in every view, and a hit sample is multiplied by `gain` (a stray photon adds counts: gain > 1).  A zinger is an
+    isolated pixel: walking a view in row-major order, a drawn sample is dropped when a hit already kept lies within `isolation`
+    pixels of it along both axes (1: no two hits touch; size - 1: no window of `size` holds two; 0: every draw is kept).  Returns
+    (frames as float32 of the kind given, the bool mask [N, H, W] of the hit samples); equal seeds give equal bits."""
+    if not 0.0 <= float(fraction) <= 1.0 or not float(gain) > 0.0 or int(isolation) < 0:
+        raise ValueError(f"add_zingers: fraction must be in [0, 1], gain above zero and isolation >= 0, got {fraction}, {gain}, "
+                         f"{isolation}")
+    x, as_tensor = _host_array(raw, "add_zingers", "raw", 3)
+    hit = _numpy_generator(generator).random(x.shape) < float(fraction)
+    k = int(isolation)
+    if k > 0:
+        for i, v, u in np.argwhere(hit):                 # row-major: the hits before (v, u) are final
+            if hit[i, max(v - k, 0):v, max(u - k, 0):u + k + 1].any() or hit[i, v, max(u - k, 0):u].any():
+                hit[i, v, u] = False
+    out = np.where(hit, x * float(gain), x).astype(np.float32)
+    return (torch.from_numpy(out), torch.from_numpy(hit)) if as_tensor else (out, hit)
+
+
+def add_dead_pixels(flat, dark, fraction, generator):
+    """Dead detector pixels: each of the H W pixels of `flat` and `dark` ([H, W], numpy arrays or CPU tensors; host side) is dead
+    with probability `fraction`, and a dead pixel reads its dark value whatever falls on it: flat = dark there.  Returns (flat as
+    float32 of the kind given, the bool mask [H, W] of the dead pixels); the frames of such a detector are `raw_frames` of the
+    returned flat.  Equal seeds give equal bits."""
+    if not 0.0 <= float(fraction) <= 1.0:
+        raise ValueError(f"add_dead_pixels: fraction must be in [0, 1], got {fraction}")
+    f, as_tensor = _host_array(flat, "add_dead_pixels", "flat", 2)
+    d, _ = _host_array(dark, "add_dead_pixels", "dark", 2)
+    if f.shape != d.shape:
+        raise ValueError(f"add_dead_pixels: flat and dark must have one shape, got {f.shape} and {d.shape}")
+    dead = _numpy_generator(generator).random(f.shape) < float(fraction)
+    out = np.where(dead, d, f).astype(np.float32)
+    return (torch.from_numpy(out), torch.from_numpy(dead)) if as_tensor else (out, dead)
