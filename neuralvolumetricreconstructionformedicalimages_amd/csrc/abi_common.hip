@@ -14,8 +14,19 @@ int fail(int code, const char *msg) {
     return code;
 }
 
-int fail_who(const char *who, const char *what) {
+int fail_who(const char *who, const char *what, int code) {
     std::snprintf(g_last_error, sizeof(g_last_error), "%s: %s", who, what);
+    return code;
+}
+
+int workspace_too_small(const char *who, uint64_t bytes, uint64_t need) {
+    std::snprintf(g_last_error, sizeof(g_last_error), "%s: workspace too small (%llu bytes, need %llu)", who, (unsigned long long)bytes,
+                  (unsigned long long)need);
+    return NAF_ERR_INVALID_ARGUMENT;
+}
+
+int misaligned(const char *who, const char *what, uint32_t bytes) {
+    std::snprintf(g_last_error, sizeof(g_last_error), "%s: %s must be %u-byte aligned", who, what, bytes);
     return NAF_ERR_INVALID_ARGUMENT;
 }
 

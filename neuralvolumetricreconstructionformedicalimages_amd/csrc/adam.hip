@@ -71,11 +71,11 @@ int naf::launch_adam(float *param, float *exp_avg, float *exp_avg_sq, float *gra
                      const AdamArgs &a, bool zero_grad, hipStream_t s) {
     if (n == 0) return NAF_OK;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n / 4 + 255) / 256, 256u * 16u));
-    if (!param_lp) { ProfScope prof_("adam_kernel", s); hipLaunchKernelGGL(adam_kernel<0>, dim3(grid), dim3(256), 0, s, param, exp_avg, exp_avg_sq, grad, nullptr, n, a, zero_grad); }
-    else if (lp_dtype == NAF_F16) { ProfScope prof_("adam_kernel", s); hipLaunchKernelGGL(adam_kernel<1>, dim3(grid), dim3(256), 0, s, param, exp_avg, exp_avg_sq, grad, param_lp, n, a, zero_grad); }
-    else if (lp_dtype == NAF_BF16) { ProfScope prof_("adam_kernel", s); hipLaunchKernelGGL(adam_kernel<2>, dim3(grid), dim3(256), 0, s, param, exp_avg, exp_avg_sq, grad, param_lp, n, a, zero_grad); }
-    else return fail(NAF_ERR_UNSUPPORTED, "adam_step: lp_dtype must be NAF_F16 or NAF_BF16 when param_lp is given");
-    return check_launch("adam_kernel");
+    const dim3 g(grid), b(256);
+    if (!param_lp) return launch("adam_kernel", adam_kernel<0>, g, b, 0, s, param, exp_avg, exp_avg_sq, grad, nullptr, n, a, zero_grad);
+    if (lp_dtype == NAF_F16) return launch("adam_kernel", adam_kernel<1>, g, b, 0, s, param, exp_avg, exp_avg_sq, grad, param_lp, n, a, zero_grad);
+    if (lp_dtype == NAF_BF16) return launch("adam_kernel", adam_kernel<2>, g, b, 0, s, param, exp_avg, exp_avg_sq, grad, param_lp, n, a, zero_grad);
+    return fail(NAF_ERR_UNSUPPORTED, "adam_step: lp_dtype must be NAF_F16 or NAF_BF16 when param_lp is given");
 }
 
 extern "C" int naf_adam_step(float *param, float *exp_avg, float *exp_avg_sq, float *grad, void *param_lp, int lp_dtype,

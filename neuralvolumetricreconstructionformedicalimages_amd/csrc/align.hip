@@ -20,7 +20,6 @@
 // scores do not depend on which other views are in the call.  T is the smallest multiple of 64 with ceil(S / T) = ceil(S / 256) for
 // S shifts, so that few lanes idle when S is just above a multiple of 256 (S = 289 for R = 8: 192 lanes with two shifts or one).
 #include <cmath>
-#include <cstdio>
 
 #include "naf_host.h"
 #include "align_device.h"
@@ -161,12 +160,6 @@ align_shift_kernel(const float *__restrict__ views, const float *__restrict__ sh
     out[view + (uint64_t)r * W + c] = align_sample(views + view, H, W, r, c, av, au);
 }
 
-int refuse(const char *who, const char *what) {
-    char msg[200];
-    std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-}
-
 // The window of a view: 0 <= R <= 16 and 2 R < extent on each axis, extents in 1 .. 2^24.
 const char *window_error(uint32_t H, uint32_t W, uint32_t Rv, uint32_t Ru) {
     if (H == 0 || W == 0) return "zero view dimension";
@@ -191,8 +184,6 @@ bool plan_scores(uint32_t N, uint32_t H, uint32_t W, uint32_t Rv, uint32_t Ru, S
     return true;
 }
 
-bool aligned(const void *a, uintptr_t mask) { return (((uintptr_t)a) & mask) == 0; }
-
 }  // namespace
 
 }  // namespace naf
@@ -210,62 +201,50 @@ extern "C" int naf_align_shift_scores(const float *b, const float *p, const floa
                                       uint32_t Ru, void *workspace, size_t workspace_bytes, double *scores, void *stream) {
     const char *who = "align_shift_scores";
     if (N == 0) return NAF_OK;
-    if (!b || !p || !scores || !workspace) return refuse(who, "null pointer");
-    if (const char *err = window_error(H, W, Rv, Ru)) return refuse(who, err);
-    if (!aligned(b, 3u) || !aligned(p, 3u) || !aligned(w, 3u)) return refuse(who, "views must be 4-byte aligned");
-    if (!aligned(scores, 7u) || !aligned(workspace, 7u)) return refuse(who, "scores and workspace must be 8-byte aligned");
+    if (!b || !p || !scores || !workspace) return fail_who(who, "null pointer");
+    if (const char *err = window_error(H, W, Rv, Ru)) return fail_who(who, err);
+    if (!aligned(b, 3u) || !aligned(p, 3u) || !aligned(w, 3u)) return misaligned(who, "views", 4);
+    if (!aligned(scores, 7u) || !aligned(workspace, 7u)) return misaligned(who, "scores and workspace", 8);
     ScorePlan g;
     uint64_t blocks;
-    if (!plan_scores(N, H, W, Rv, Ru, &g, &blocks)) return refuse(who, "too many tiles for one call");
+    if (!plan_scores(N, H, W, Rv, Ru, &g, &blocks)) return fail_who(who, "too many tiles for one call");
     const uint64_t need = blocks * g.S * sizeof(double);
-    if (workspace_bytes < need) {
-        char msg[160];
-        std::snprintf(msg, sizeof(msg), "workspace too small (%llu bytes, need %llu)", (unsigned long long)workspace_bytes,
-                      (unsigned long long)need);
-        return refuse(who, msg);
-    }
+    if (workspace_bytes < need) return workspace_too_small(who, workspace_bytes, need);
     const uint64_t total = (uint64_t)N * g.S;
     const uint64_t reduce_blocks = (total + kReduceThreads - 1u) / kReduceThreads;
     hipStream_t s = (hipStream_t)stream;
     double *partials = static_cast<double *>(workspace);
-    { ProfScope prof_("align_scores_kernel", s);
-      if (w) hipLaunchKernelGGL(align_scores_kernel<true>, dim3((uint32_t)blocks), dim3(g.threads), 0, s, b, p, w, g, partials);
-      else hipLaunchKernelGGL(align_scores_kernel<false>, dim3((uint32_t)blocks), dim3(g.threads), 0, s, b, p, w, g, partials); }
-    const int launched = check_launch("align_scores_kernel");
+    auto kernel = w ? align_scores_kernel<true> : align_scores_kernel<false>;
+    const int launched = launch("align_scores_kernel", kernel, dim3((uint32_t)blocks), dim3(g.threads), 0, s, b, p, w, g, partials);
     if (launched != NAF_OK) return launched;
-    { ProfScope prof_("align_reduce_kernel", s);
-      hipLaunchKernelGGL(align_reduce_kernel, dim3((uint32_t)reduce_blocks), dim3(kReduceThreads), 0, s, partials, total, g.S, g.tiles,
-                         scores); }
-    return check_launch("align_reduce_kernel");
+    return launch("align_reduce_kernel", align_reduce_kernel, dim3((uint32_t)reduce_blocks), dim3(kReduceThreads), 0, s, partials, total,
+                  g.S, g.tiles, scores);
 }
 
 extern "C" int naf_align_peak(const double *scores, uint32_t N, uint32_t Rv, uint32_t Ru, float *shifts, int32_t *flags, void *stream) {
     const char *who = "align_peak";
     if (N == 0) return NAF_OK;
-    if (!scores || !shifts || !flags) return refuse(who, "null pointer");
-    if (Rv > kMaxR || Ru > kMaxR) return refuse(who, "max shift above 16");
-    if (N > 0x7fffffffu) return refuse(who, "too many views for one call");
-    if (!aligned(scores, 7u) || !aligned(shifts, 3u) || !aligned(flags, 3u)) return refuse(who, "misaligned pointer");
+    if (!scores || !shifts || !flags) return fail_who(who, "null pointer");
+    if (Rv > kMaxR || Ru > kMaxR) return fail_who(who, "max shift above 16");
+    if (N > 0x7fffffffu) return fail_who(who, "too many views for one call");
+    if (!aligned(scores, 7u) || !aligned(shifts, 3u) || !aligned(flags, 3u)) return fail_who(who, "misaligned pointer");
     hipStream_t s = (hipStream_t)stream;
-    { ProfScope prof_("align_peak_kernel", s);
-      hipLaunchKernelGGL(align_peak_kernel, dim3(N), dim3(kPeakThreads), 0, s, scores, Rv, Ru, shifts, flags); }
-    return check_launch("align_peak_kernel");
+    return launch("align_peak_kernel", align_peak_kernel, dim3(N), dim3(kPeakThreads), 0, s, scores, Rv, Ru, shifts, flags);
 }
 
 extern "C" int naf_align_shift_views(const float *views, const float *shifts, uint32_t N, uint32_t H, uint32_t W, float *out,
                                      void *stream) {
     const char *who = "align_shift_views";
     if (N == 0) return NAF_OK;
-    if (!views || !shifts || !out) return refuse(who, "null pointer");
-    if (H == 0 || W == 0) return refuse(who, "zero view dimension");
-    if (H > kMaxExtent || W > kMaxExtent) return refuse(who, "view dimension above 2^24");
-    if (views == out) return refuse(who, "out must not be the views: every output pixel reads sixteen input pixels");
-    if (!aligned(views, 3u) || !aligned(shifts, 3u) || !aligned(out, 3u)) return refuse(who, "pointers must be 4-byte aligned");
+    if (!views || !shifts || !out) return fail_who(who, "null pointer");
+    if (H == 0 || W == 0) return fail_who(who, "zero view dimension");
+    if (H > kMaxExtent || W > kMaxExtent) return fail_who(who, "view dimension above 2^24");
+    if (views == out) return fail_who(who, "out must not be the views: every output pixel reads sixteen input pixels");
+    if (!aligned(views, 3u) || !aligned(shifts, 3u) || !aligned(out, 3u)) return misaligned(who, "pointers", 4);
     const uint32_t bx = (W + kShiftW - 1u) / kShiftW, by = (H + kShiftH - 1u) / kShiftH;
     const uint64_t blocks = (uint64_t)bx * by * N;
-    if (blocks > 0x7fffffffull) return refuse(who, "too many pixels for one call");
+    if (blocks > 0x7fffffffull) return fail_who(who, "too many pixels for one call");
     hipStream_t s = (hipStream_t)stream;
-    { ProfScope prof_("align_shift_kernel", s);
-      hipLaunchKernelGGL(align_shift_kernel, dim3((uint32_t)blocks), dim3(kShiftW * kShiftH), 0, s, views, shifts, H, W, bx, by, out); }
-    return check_launch("align_shift_kernel");
+    return launch("align_shift_kernel", align_shift_kernel, dim3((uint32_t)blocks), dim3(kShiftW * kShiftH), 0, s, views, shifts, H, W,
+                  bx, by, out);
 }

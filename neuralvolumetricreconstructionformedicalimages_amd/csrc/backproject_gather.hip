@@ -164,7 +164,7 @@ extern "C" int naf_backproject_scan_gather(const float *values, const uint32_t *
     else if (den == volume) what = "volume and den must be two volumes";
     else if (per_view > 0x7fffffffull) what = "too many pixels in a view";
     else if (bricks_x * bricks_y * blocks_z > 0x7fffffffull) what = "too many voxels for one call";
-    else if (workspace && (((uintptr_t)workspace) & 7u)) what = "workspace must be 8-byte aligned";
+    else if (!aligned(workspace, 7u)) what = "workspace must be 8-byte aligned";
     else if (workspace && workspace_bytes < per_view * NAF_GATHER_SPAN_BYTES) what = "workspace too small for the spans of one view";
     if (what) return fail_who(who, what);
     GatherGrid grid;
@@ -183,18 +183,14 @@ extern "C" int naf_backproject_scan_gather(const float *values, const uint32_t *
         GatherViews list{view_index, n_scan_views, first, std::min(group, n_sub - first)};
         if (workspace) {
             const uint64_t blocks = (per_view * list.count + 255u) / 256u;
-            { ProfScope prof_("gather_spans_kernel", (hipStream_t)stream);
-              hipLaunchKernelGGL(gather_spans_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream, v, poses, g, list,
-                                 spans); }
-            const int rs = check_launch("gather_spans_kernel");
+            const int rs = launch("gather_spans_kernel", gather_spans_kernel, dim3((uint32_t)blocks), dim3(256), 0, (hipStream_t)stream,
+                                  v, poses, g, list, spans);
             if (rs != NAF_OK) return rs;
         }
-        { ProfScope prof_("backproject_gather_kernel", (hipStream_t)stream);
-          auto kernel = workspace ? (den ? backproject_gather_kernel<true, true> : backproject_gather_kernel<true, false>)
-                                  : (den ? backproject_gather_kernel<false, true> : backproject_gather_kernel<false, false>);
-          hipLaunchKernelGGL(kernel, grid_dim, dim3(256), 0, (hipStream_t)stream, v, grid, volume, den, values, poses, g, list,
-                             (const GatherSpan *)spans, (uint32_t)bricks_y, (uint32_t)blocks_z); }
-        const int rk = check_launch("backproject_gather_kernel");
+        auto kernel = workspace ? (den ? backproject_gather_kernel<true, true> : backproject_gather_kernel<true, false>)
+                                : (den ? backproject_gather_kernel<false, true> : backproject_gather_kernel<false, false>);
+        const int rk = launch("backproject_gather_kernel", kernel, grid_dim, dim3(256), 0, (hipStream_t)stream, v, grid, volume, den, values,
+                              poses, g, list, (const GatherSpan *)spans, (uint32_t)bricks_y, (uint32_t)blocks_z);
         if (rk != NAF_OK) return rk;
     }
     return NAF_OK;

@@ -4,8 +4,8 @@
 //
 //   cgls_wdot_kernel       one fp64 partial of sum w a^2 per workgroup
 //   cgls_residual_kernel   the same partial of sum w r^2, then r <- r - alpha q and y <- w r in the same pass
-//   cgls_reduce_kernel     one workgroup adds the partials in a fixed order into one scalar (no atomics: two calls return the
-//                          same bits) and, after a residual pass, records a breakdown in the sticky stop mark
+//   cgls_reduce_kernel     one workgroup adds the partials in a fixed order into one scalar (csrc/block_sum.h: two calls return
+//                          the same bits) and, after a residual pass, records a breakdown in the sticky stop mark
 //   cgls_direction_kernel  x <- x + alpha p, p <- s + beta p: three arrays read, two written
 //
 // The scalars gamma, delta, the history and the stop mark live in device memory and every kernel reads them there, so a solve is
@@ -18,8 +18,8 @@
 // ascending order and the four terms of a group in ascending order; the grid is a function of n alone.  The float4 path and the
 // element path (for pointers that are not 16-byte aligned) therefore add the same terms in the same order.
 #include <cmath>
-#include <cstdio>
 
+#include "block_sum.h"
 #include "naf_host.h"
 #include "cgls_device.h"
 
@@ -44,16 +44,6 @@ uint32_t blocks_of(uint64_t n) {
 uint64_t scalar_count(uint32_t n_iter_max) { return ((uint64_t)kHeader + n_iter_max + 31u) & ~(uint64_t)31u; }
 
 uint64_t workspace_bytes(uint64_t n, uint32_t n_iter_max) { return (scalar_count(n_iter_max) + blocks_of(n)) * sizeof(double); }
-
-// Fixed-order tree over the workgroup's 256 sums (a NaN propagates: nothing is skipped); the result is in red[0] for thread 0.
-__device__ __forceinline__ void block_sum(double *red, double mine, uint32_t tid) {
-    red[tid] = mine;
-    __syncthreads();
-    for (uint32_t h = kThreads / 2; h > 0; h >>= 1) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-}
 
 // The four elements of group j, or fewer at the end of the array: `count` of them are valid.
 template <bool kVec>
@@ -99,7 +89,7 @@ cgls_wdot_kernel(const float *__restrict__ a, const float *__restrict__ w, uint6
         for (uint32_t e = 0; e < 4u; ++e)
             if (e < count) sum += kHasW ? cgls_term(av[e], wv[e]) : cgls_term(av[e]);
     }
-    block_sum(red, sum, threadIdx.x);
+    block_sum<kThreads>(red, sum, threadIdx.x);
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
 }
 
@@ -129,7 +119,7 @@ cgls_residual_kernel(float *__restrict__ r, const float *__restrict__ q, const f
         store_group<kVec>(r, j, count, rv);
         store_group<kVec>(y, j, count, yv);
     }
-    block_sum(red, sum, threadIdx.x);
+    block_sum<kThreads>(red, sum, threadIdx.x);
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
 }
 
@@ -141,9 +131,7 @@ cgls_reduce_kernel(const double *__restrict__ partials, uint32_t n_partials, dou
                    int64_t mark_k) {
     __shared__ double red[kReduceThreads];
     const uint32_t tid = threadIdx.x;
-    double t = 0.0;
-    for (uint32_t i = tid; i < n_partials; i += kReduceThreads) t += partials[i];
-    block_sum(red, t, tid);
+    block_sum<kReduceThreads>(red, strided_sum<kReduceThreads>(partials, n_partials, tid), tid);
     if (tid == 0) {
         scalars[slot] = red[0];
         if (mark_k >= 0) {
@@ -184,47 +172,31 @@ struct Workspace {
 
 // The checks every entry point shares; splits the workspace.
 int cgls_check(const char *who, uint64_t n, uint32_t n_iter_max, void *workspace, size_t bytes, Workspace *ws) {
-    char msg[160];
-    if (!workspace) {
-        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (((uintptr_t)workspace) & 7u) {
-        std::snprintf(msg, sizeof(msg), "%s: workspace must be 8-byte aligned", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (!workspace) return fail_who(who, "null pointer");
+    if (!aligned(workspace, 7u)) return misaligned(who, "workspace", 8);
     const uint64_t need = workspace_bytes(n, n_iter_max);
-    if (bytes < need) {
-        std::snprintf(msg, sizeof(msg), "%s: workspace too small (%llu bytes, need %llu)", who, (unsigned long long)bytes,
-                      (unsigned long long)need);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (bytes < need) return workspace_too_small(who, bytes, need);
     ws->scalars = static_cast<double *>(workspace);
     ws->partials = ws->scalars + scalar_count(n_iter_max);
     ws->blocks = blocks_of(n);
     return NAF_OK;
 }
 
-bool aligned16(const void *a) { return a == nullptr || (((uintptr_t)a) & 15u) == 0; }
-bool aligned4(const void *a) { return (((uintptr_t)a) & 3u) == 0; }
-
 int reduce(const Workspace &ws, uint32_t slot, int64_t mark_k, hipStream_t stream) {
-    { ProfScope prof_("cgls_reduce_kernel", stream);
-      hipLaunchKernelGGL(cgls_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, stream, ws.partials, ws.blocks, ws.scalars, slot,
-                         mark_k); }
-    return check_launch("cgls_reduce_kernel");
+    return launch("cgls_reduce_kernel", cgls_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, stream, ws.partials, ws.blocks, ws.scalars,
+                  slot, mark_k);
 }
 
 template <bool kVec, bool kHasW>
-void launch_wdot(const Workspace &ws, const float *a, const float *w, uint64_t n, hipStream_t stream) {
-    hipLaunchKernelGGL((cgls_wdot_kernel<kVec, kHasW>), dim3(ws.blocks), dim3(kThreads), 0, stream, a, w, n, ws.partials);
+int launch_wdot(const Workspace &ws, const float *a, const float *w, uint64_t n, hipStream_t stream) {
+    return launch("cgls_wdot_kernel", cgls_wdot_kernel<kVec, kHasW>, dim3(ws.blocks), dim3(kThreads), 0, stream, a, w, n, ws.partials);
 }
 
 template <bool kVec, bool kHasW>
-void launch_residual(const Workspace &ws, float *r, const float *q, const float *w, float *y, uint64_t n, uint32_t parity,
-                     hipStream_t stream) {
-    hipLaunchKernelGGL((cgls_residual_kernel<kVec, kHasW>), dim3(ws.blocks), dim3(kThreads), 0, stream, r, q, w, y, n, ws.scalars,
-                       parity, ws.partials);
+int launch_residual(const Workspace &ws, float *r, const float *q, const float *w, float *y, uint64_t n, uint32_t parity,
+                    hipStream_t stream) {
+    return launch("cgls_residual_kernel", cgls_residual_kernel<kVec, kHasW>, dim3(ws.blocks), dim3(kThreads), 0, stream, r, q, w, y, n,
+                  ws.scalars, parity, ws.partials);
 }
 
 }  // namespace
@@ -240,16 +212,14 @@ extern "C" int naf_cgls_wdot(const float *a, const float *w, uint64_t n, uint32_
     if (n == 0) return NAF_OK;
     if (!a) return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_wdot: null pointer");
     if (slot > kSlotDelta) return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_wdot: slot must be one of the two gamma slots or delta (0, 1, 2)");
-    if (!aligned4(a) || !aligned4(w)) return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_wdot: pointers must be 4-byte aligned");
+    if (!aligned(a, 3u) || !aligned(w, 3u)) return misaligned("cgls_wdot", "pointers", 4);
     Workspace ws;
     const int rc = cgls_check("cgls_wdot", n, n_iter_max, workspace, workspace_bytes, &ws);
     if (rc != NAF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = aligned16(a) && aligned16(w);
-    { ProfScope prof_("cgls_wdot_kernel", s);
-      if (w) vec ? launch_wdot<true, true>(ws, a, w, n, s) : launch_wdot<false, true>(ws, a, w, n, s);
-      else vec ? launch_wdot<true, false>(ws, a, w, n, s) : launch_wdot<false, false>(ws, a, w, n, s); }
-    const int launched = check_launch("cgls_wdot_kernel");
+    const bool vec = aligned(a, 15u) && aligned(w, 15u);
+    const int launched = w ? (vec ? launch_wdot<true, true>(ws, a, w, n, s) : launch_wdot<false, true>(ws, a, w, n, s))
+                           : (vec ? launch_wdot<true, false>(ws, a, w, n, s) : launch_wdot<false, false>(ws, a, w, n, s));
     if (launched != NAF_OK) return launched;
     return reduce(ws, slot, -1, s);
 }
@@ -261,18 +231,16 @@ extern "C" int naf_cgls_residual_step(float *r, const float *q, const float *w, 
     if (y == q || y == r || r == q || (w && (w == y || w == r)))
         return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_residual_step: y must not be q or r, and r, q, w, y must be four arrays");
     if (k >= n_iter_max) return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_residual_step: k has no history slot (k >= n_iter_max)");
-    if (!aligned4(r) || !aligned4(q) || !aligned4(w) || !aligned4(y))
-        return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_residual_step: pointers must be 4-byte aligned");
+    if (!aligned(r, 3u) || !aligned(q, 3u) || !aligned(w, 3u) || !aligned(y, 3u)) return misaligned("cgls_residual_step", "pointers", 4);
     Workspace ws;
     const int rc = cgls_check("cgls_residual_step", n, n_iter_max, workspace, workspace_bytes, &ws);
     if (rc != NAF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = aligned16(r) && aligned16(q) && aligned16(w) && aligned16(y);
+    const bool vec = aligned(r, 15u) && aligned(q, 15u) && aligned(w, 15u) && aligned(y, 15u);
     const uint32_t parity = k & 1u;
-    { ProfScope prof_("cgls_residual_kernel", s);
-      if (w) vec ? launch_residual<true, true>(ws, r, q, w, y, n, parity, s) : launch_residual<false, true>(ws, r, q, w, y, n, parity, s);
-      else vec ? launch_residual<true, false>(ws, r, q, w, y, n, parity, s) : launch_residual<false, false>(ws, r, q, w, y, n, parity, s); }
-    const int launched = check_launch("cgls_residual_kernel");
+    const int launched =
+        w ? (vec ? launch_residual<true, true>(ws, r, q, w, y, n, parity, s) : launch_residual<false, true>(ws, r, q, w, y, n, parity, s))
+          : (vec ? launch_residual<true, false>(ws, r, q, w, y, n, parity, s) : launch_residual<false, false>(ws, r, q, w, y, n, parity, s));
     if (launched != NAF_OK) return launched;
     return reduce(ws, kHeader + k, (int64_t)k, s);
 }
@@ -283,17 +251,12 @@ extern "C" int naf_cgls_direction_step(float *x, float *p, const float *s, uint6
     if (!x || !p || !s) return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_direction_step: null pointer");
     if (x == p || x == s || p == s) return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_direction_step: x, p and s must be three arrays");
     if (k >= n_iter_max) return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_direction_step: k is not an iteration of this workspace (k >= n_iter_max)");
-    if (!aligned4(x) || !aligned4(p) || !aligned4(s))
-        return fail(NAF_ERR_INVALID_ARGUMENT, "cgls_direction_step: pointers must be 4-byte aligned");
+    if (!aligned(x, 3u) || !aligned(p, 3u) || !aligned(s, 3u)) return misaligned("cgls_direction_step", "pointers", 4);
     Workspace ws;
     const int rc = cgls_check("cgls_direction_step", n, n_iter_max, workspace, workspace_bytes, &ws);
     if (rc != NAF_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t parity = k & 1u;
-    { ProfScope prof_("cgls_direction_kernel", st);
-      if (aligned16(x) && aligned16(p) && aligned16(s))
-          hipLaunchKernelGGL(cgls_direction_kernel<true>, dim3(ws.blocks), dim3(kThreads), 0, st, x, p, s, n, ws.scalars, parity);
-      else
-          hipLaunchKernelGGL(cgls_direction_kernel<false>, dim3(ws.blocks), dim3(kThreads), 0, st, x, p, s, n, ws.scalars, parity); }
-    return check_launch("cgls_direction_kernel");
+    auto kernel = aligned(x, 15u) && aligned(p, 15u) && aligned(s, 15u) ? cgls_direction_kernel<true> : cgls_direction_kernel<false>;
+    return launch("cgls_direction_kernel", kernel, dim3(ws.blocks), dim3(kThreads), 0, st, x, p, s, n, ws.scalars, parity);
 }

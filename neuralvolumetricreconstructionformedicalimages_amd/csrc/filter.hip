@@ -114,23 +114,15 @@ int filter_rows_launch(const char *name, const float *in, uint32_t n_views, uint
     }
     const uint64_t rows = (uint64_t)n_views * H;
     if (rows == 0) return NAF_OK;
-    if (!in || !taps || !out) {
-        std::snprintf(msg, sizeof(msg), "%s: null pointer", name);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (rows > 0x7fffffffull) {
-        std::snprintf(msg, sizeof(msg), "%s: more than 2^31 - 1 rows in one call", name);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (!in || !taps || !out) return fail_who(name, "null pointer");
+    if (rows > 0x7fffffffull) return fail_who(name, "more than 2^31 - 1 rows in one call");
     const uint32_t lanes = (W + kR - 1u) / kR;
     const uint32_t threads = std::min(kMaxThreads, (lanes + 63u) & ~63u);
     const uint32_t lds = filter_lds_bytes(W);
     int rc = raise_lds_limit(filter_rows_kernel, lds, "filter_rows: could not raise the dynamic LDS limit");
     if (rc != NAF_OK) return rc;
-    { ProfScope prof_("filter_rows_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(filter_rows_kernel, dim3((uint32_t)rows), dim3(threads), lds, (hipStream_t)stream, in, H, W, taps, pre, post,
-                         view_scale, col, out); }
-    return check_launch("filter_rows_kernel");
+    return launch("filter_rows_kernel", filter_rows_kernel, dim3((uint32_t)rows), dim3(threads), lds, (hipStream_t)stream, in, H, W, taps,
+                  pre, post, view_scale, col, out);
 }
 
 }  // namespace

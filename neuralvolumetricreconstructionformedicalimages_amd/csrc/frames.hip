@@ -15,7 +15,6 @@
 // indices lie in [-h, extent - 1 + h], inside what stripe_reflect maps for size <= extent.  The kernel holds no array of its own, so
 // it uses no scratch; LDS is 22 x 70 words at size 7.
 #include <cmath>
-#include <cstdio>
 
 #include "naf_host.h"
 #include "frames_device.h"
@@ -77,28 +76,24 @@ frames_condition_kernel(const Raw *__restrict__ raw, const float *__restrict__ d
 
 int refuse(const char *what) { return fail_who("frames_condition", what); }
 
-bool aligned(const void *a, uintptr_t mask) { return (((uintptr_t)a) & mask) == 0; }
-
 bool overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 template <typename Raw, uint32_t kSize>
-int launch(const void *raw, const float *dark, const float *flat, const uint8_t *bad, const FramesPlan &g, uint32_t blocks, float dif,
-           float t_min, uint32_t flags, float *out, uint32_t *counts, hipStream_t st) {
-    { ProfScope prof_("frames_condition_kernel", st);
-      hipLaunchKernelGGL((frames_condition_kernel<Raw, kSize>), dim3(blocks), dim3(kThreads), 0, st, static_cast<const Raw *>(raw), dark,
-                         flat, bad, g, dif, t_min, flags, out, counts); }
-    return check_launch("frames_condition_kernel");
+int launch_frames(const void *raw, const float *dark, const float *flat, const uint8_t *bad, const FramesPlan &g, uint32_t blocks, float dif,
+                  float t_min, uint32_t flags, float *out, uint32_t *counts, hipStream_t st) {
+    return launch("frames_condition_kernel", (frames_condition_kernel<Raw, kSize>), dim3(blocks), dim3(kThreads), 0, st,
+                  static_cast<const Raw *>(raw), dark, flat, bad, g, dif, t_min, flags, out, counts);
 }
 
 template <typename Raw>
 int launch_size(uint32_t size, const void *raw, const float *dark, const float *flat, const uint8_t *bad, const FramesPlan &g,
                 uint32_t blocks, float dif, float t_min, uint32_t flags, float *out, uint32_t *counts, hipStream_t st) {
-    if (size == 3u) return launch<Raw, 3u>(raw, dark, flat, bad, g, blocks, dif, t_min, flags, out, counts, st);
-    if (size == 5u) return launch<Raw, 5u>(raw, dark, flat, bad, g, blocks, dif, t_min, flags, out, counts, st);
-    return launch<Raw, 7u>(raw, dark, flat, bad, g, blocks, dif, t_min, flags, out, counts, st);
+    if (size == 3u) return launch_frames<Raw, 3u>(raw, dark, flat, bad, g, blocks, dif, t_min, flags, out, counts, st);
+    if (size == 5u) return launch_frames<Raw, 5u>(raw, dark, flat, bad, g, blocks, dif, t_min, flags, out, counts, st);
+    return launch_frames<Raw, 7u>(raw, dark, flat, bad, g, blocks, dif, t_min, flags, out, counts, st);
 }
 
 }  // namespace

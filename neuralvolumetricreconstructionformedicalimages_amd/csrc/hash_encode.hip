@@ -40,26 +40,23 @@ static int launch_forward(const float *inputs, const void *emb, const int32_t *o
     if constexpr (D == 3) {
         if (dy_dx == nullptr) return launch_encode<T, T, C, SrcUnit<3>>(SrcUnit<3>{inputs}, emb, offsets, out, B, H, L, 0u, s, 0u, ~0u, 0u, blc);
     }
-    { ProfScope prof_("hash_forward_kernel", s); hipLaunchKernelGGL((hash_forward_kernel<T, D, C, SrcUnit<D>>), dim3(hash_grid_x(B), L), dim3(256), 0, s,
-                       SrcUnit<D>{inputs}, (const S *)emb, offsets, (S *)out, B, L, H, blc, (S *)dy_dx, jac_mode); }
-    return check_launch("hash_forward_kernel");
+    return launch("hash_forward_kernel", (hash_forward_kernel<T, D, C, SrcUnit<D>>), dim3(hash_grid_x(B), L), dim3(256), 0, s,
+                  SrcUnit<D>{inputs}, (const S *)emb, offsets, (S *)out, B, L, H, blc, (S *)dy_dx, jac_mode, /*level_base=*/0u);
 }
 
 template <typename T, uint32_t D, uint32_t C>
 static int launch_input_backward(const void *grad, const void *dy_dx, float *ginp, uint32_t B, uint32_t L, bool blc, hipStream_t s) {
     using S = typename T::store_t;
-    { ProfScope prof_("input_backward_kernel", s); hipLaunchKernelGGL((input_backward_kernel<T, D, C>), dim3(((uint64_t)B * D + 255) / 256), dim3(256), 0, s,
-                       (const S *)grad, (const S *)dy_dx, ginp, B, L, blc); }
-    return check_launch("input_backward_kernel");
+    return launch("input_backward_kernel", (input_backward_kernel<T, D, C>), dim3(((uint64_t)B * D + 255) / 256), dim3(256), 0, s,
+                  (const S *)grad, (const S *)dy_dx, ginp, B, L, blc);
 }
 
 template <typename T, uint32_t D, uint32_t C>
 static int launch_backward(const void *grad, const float *inputs, const int32_t *offsets, float *gtab, uint32_t B,
                            uint32_t L, uint32_t H, bool blc, const void *dy_dx, float *ginp, hipStream_t s) {
     using S = typename T::store_t;
-    { ProfScope prof_("hash_backward_kernel", s); hipLaunchKernelGGL((hash_backward_kernel<T, D, C, SrcUnit<D>>), dim3(hash_grid_x(B), L), dim3(256), 0, s,
-                       SrcUnit<D>{inputs}, (const S *)grad, offsets, gtab, B, L, H, blc); }
-    int rc = check_launch("hash_backward_kernel");
+    int rc = launch("hash_backward_kernel", (hash_backward_kernel<T, D, C, SrcUnit<D>>), dim3(hash_grid_x(B), L), dim3(256), 0, s,
+                    SrcUnit<D>{inputs}, (const S *)grad, offsets, gtab, B, L, H, blc, /*level_base=*/0u);
     if (rc != NAF_OK || dy_dx == nullptr) return rc;
     return launch_input_backward<T, D, C>(grad, dy_dx, ginp, B, L, blc, s);
 }
@@ -119,8 +116,8 @@ static int binned_backward(const void *grad, const float *inputs, const int32_t 
     // overflow counters and gmax to zero, then gmax = max |grad|: what the MLP backward of a training step hands the reducer
     if (hipMemsetAsync(w.overflow, 0, 34 * sizeof(uint32_t), s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "hash_encode_backward_ws: memset failed");
     const uint64_t n = (uint64_t)B * cfg->L * C;
-    { ProfScope prof_("grad_absmax_kernel", s); hipLaunchKernelGGL((grad_absmax_kernel<T>), dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, s,
-                       (const typename T::store_t *)grad, n, w.gmax); }
+    if (int rc = launch("grad_absmax_kernel", grad_absmax_kernel<T>, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, s,
+                        (const typename T::store_t *)grad, n, w.gmax)) return rc;
     // 12-byte / fp32 records, four levels per bin workgroup at every batch size, no Adam tail
     using Rec = typename std::conditional<std::is_same<T, F32>::value, PairF32<C>, PairBF16<C>>::type;
     PairRecords<T, C, SrcUnit<3>, Rec, 4u, false> fam{SrcUnit<3>{inputs, B}, grad, B, blc ? 1u : B, blc ? cfg->L : 1u};
@@ -202,7 +199,7 @@ extern "C" int naf_hash_encode_backward_ws(const void *grad, const float *inputs
                                         dtype, grad_layout, stream);
     if (!grad || !inputs || !offsets || !grad_embeddings) return fail(NAF_ERR_INVALID_ARGUMENT, "hash_encode_backward_ws: null pointer");
     if (calc_grad_inputs && (!dy_dx || !grad_inputs)) return fail(NAF_ERR_INVALID_ARGUMENT, "hash_encode_backward_ws: calc_grad_inputs without dy_dx/grad_inputs");
-    if (((uintptr_t)workspace & 255u) != 0u) return fail(NAF_ERR_INVALID_ARGUMENT, "hash_encode_backward_ws: the workspace must be 256-byte aligned");
+    if (!aligned(workspace, 255u)) return misaligned("hash_encode_backward_ws", "the workspace", 256);
     const bool blc = grad_layout == NAF_LAYOUT_BLC;
     hipStream_t s = (hipStream_t)stream;
     cfg.H = H;

@@ -12,8 +12,15 @@ namespace naf {
 
 // Records `msg` as the calling thread's last error and returns `code` (see naf_last_error()).
 int fail(int code, const char *msg);
-// The same for a refused argument, NAF_ERR_INVALID_ARGUMENT, with the message "<who>: <what>".
-int fail_who(const char *who, const char *what);
+// The one refusal "<who>: <what>"; returns `code`.
+int fail_who(const char *who, const char *what, int code = NAF_ERR_INVALID_ARGUMENT);
+// "<who>: workspace too small (<bytes> bytes, need <need>)" and "<who>: <what> must be <bytes>-byte aligned", both
+// NAF_ERR_INVALID_ARGUMENT.  There is no combined workspace check: the entry points test null, size and alignment in different
+// orders, and each keeps its own.
+int workspace_too_small(const char *who, uint64_t bytes, uint64_t need);
+int misaligned(const char *who, const char *what, uint32_t bytes);
+// True when `a` has none of the low bits in `mask` set (a null pointer has none).
+inline bool aligned(const void *a, uintptr_t mask) { return (((uintptr_t)a) & mask) == 0; }
 // hipGetLastError() -> NAF_OK / NAF_ERR_LAUNCH (message names the kernel).
 int check_launch(const char *kernel);
 
@@ -40,5 +47,14 @@ class ProfScope {
     int slot_;
     hipStream_t stream_;
 };
+
+// One launch: times `kernel` under `name` when profiling is on, launches it, and reports a failed launch under the same name.  A site
+// that picks one of several instantiations under one name calls this once per branch.
+template <typename K, typename... Args>
+static int launch(const char *name, K kernel, dim3 grid, dim3 block, uint32_t lds_bytes, hipStream_t stream, Args... args) {
+    { ProfScope prof_(name, stream);
+      hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...); }
+    return check_launch(name);
+}
 
 }  // namespace naf

@@ -119,25 +119,12 @@ __device__ __forceinline__ float span_sum(const ProjVolume &v, const RaySpan &s)
 // Host: argument checks shared by the entry points, and the grid of a [n1, n2, n3] volume with voxel size dvoxel (HOST f32 [3]).
 inline int make_volume(const char *who, const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, float step,
                        ProjVolume *v) {
-    char msg[160];
-    if (!volume || !dvoxel) {
-        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (n1 == 0 || n2 == 0 || n3 == 0) {
-        std::snprintf(msg, sizeof(msg), "%s: zero volume dimension", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (!(step > 0.0f) || !std::isfinite(step)) {
-        std::snprintf(msg, sizeof(msg), "%s: step must be > 0", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (!volume || !dvoxel) return fail_who(who, "null pointer");
+    if (n1 == 0 || n2 == 0 || n3 == 0) return fail_who(who, "zero volume dimension");
+    if (!(step > 0.0f) || !std::isfinite(step)) return fail_who(who, "step must be > 0");
     const uint32_t n[3] = {n1, n2, n3};
     for (int a = 0; a < 3; ++a) {
-        if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) {
-            std::snprintf(msg, sizeof(msg), "%s: voxel size must be > 0", who);
-            return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-        }
+        if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) return fail_who(who, "voxel size must be > 0");
         v->n[a] = n[a];
         v->imax[a] = n[a] >= 2u ? n[a] - 2u : 0u;
         v->half[a] = (float)((double)n[a] * (double)dvoxel[a] / 2.0);

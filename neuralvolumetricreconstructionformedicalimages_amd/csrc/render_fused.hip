@@ -75,12 +75,6 @@ static int check_depths(const naf_render_cfg *cfg, const float *t_rand) {
         return fail(NAF_ERR_INVALID_ARGUMENT, "render: NAF_CFG_EXPLICIT_DEPTHS needs the depths in t_rand");
     return NAF_OK;
 }
-// fail() with the message "<who>: <what>"
-static int fail_in(int code, const char *who, const char *what) {
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "%s: %s", who, what);
-    return fail(code, msg);
-}
 
 // The checks a ray entry point opens with, in the one order all of them keep: the cfg, the depths, the level range of a level-parallel
 // call (`levels`); then, for a batch that is not empty, the buffers (`missing`: one the call needs is null) and the rank count
@@ -93,20 +87,20 @@ static int check_ray_call(const char *who, const naf_render_cfg *cfg, const floa
     if (levels != nullptr && (levels->begin >= levels->end || levels->end > cfg->L))
         return fail(NAF_ERR_INVALID_ARGUMENT, "levels: empty or out-of-range level range");
     if (n_rays == 0 && empty_ok == kEmptyOk) return NAF_OK;
-    if (n_rays != 0 && missing) return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "null pointer");
+    if (n_rays != 0 && missing) return fail_who(who, "null pointer");
     if (n_ranks != nullptr && (*n_ranks == 0 || n_rays % *n_ranks != 0))
-        return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "every rank must contribute the same number of rays");
-    if (cfg->n_samples < 2) return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "n_samples must be >= 2");
+        return fail_who(who, "every rank must contribute the same number of rays");
+    if (cfg->n_samples < 2) return fail_who(who, "n_samples must be >= 2");
     return check_points((uint64_t)n_rays * cfg->n_samples);
 }
 
 // naf_table_adam -> the reducer's Adam tail, after the checks every entry point that takes one makes (`who` names it)
 static int make_adam_tail(const char *who, const naf_table_adam *adam, const float *grad_embeddings, AdamTail *tail) {
-    if (adam->step == 0) return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "step is 1-based");
+    if (adam->step == 0) return fail_who(who, "step is 1-based");
     if (adam->param_lp != nullptr && adam->lp_dtype != NAF_F16 && adam->lp_dtype != NAF_BF16)
-        return fail_in(NAF_ERR_UNSUPPORTED, who, "lp_dtype must be NAF_F16 or NAF_BF16 when param_lp is given");
+        return fail_who(who, "lp_dtype must be NAF_F16 or NAF_BF16 when param_lp is given", NAF_ERR_UNSUPPORTED);
     if (((uintptr_t)adam->param | (uintptr_t)adam->exp_avg | (uintptr_t)adam->exp_avg_sq | (uintptr_t)grad_embeddings) & 15u)
-        return fail_in(NAF_ERR_INVALID_ARGUMENT, who, "buffers must be 16-byte aligned");
+        return fail_who(who, "buffers must be 16-byte aligned");
     tail->param = adam->param; tail->m = adam->exp_avg; tail->v = adam->exp_avg_sq;
     tail->lp = adam->param_lp; tail->lp_dtype = adam->lp_dtype; tail->overflow = nullptr;
     tail->a = make_adam_args(adam->lr, adam->beta1, adam->beta2, adam->eps, adam->step, adam->grad_scale);

@@ -249,18 +249,16 @@ extern "C" int naf_sample_rays(const float *rays, const float *t_rand, float *z_
     if (n_samples < 2) return fail(NAF_ERR_INVALID_ARGUMENT, "sample_rays: n_samples must be >= 2");
     if (n_rays == 0) return NAF_OK;
     const uint64_t total = (uint64_t)n_rays * n_samples;
-    { ProfScope prof_("sample_rays_kernel", (hipStream_t)stream); hipLaunchKernelGGL(sample_rays_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, rays, t_rand,
-                       z_vals, pts, n_rays, n_samples, perturb != 0, bound, seed, ray_index_base); }
-    return check_launch("sample_rays_kernel");
+    return launch("sample_rays_kernel", sample_rays_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, rays, t_rand,
+                  z_vals, pts, n_rays, n_samples, perturb != 0, bound, seed, ray_index_base);
 }
 
 extern "C" int naf_integrate_forward(const float *sigma, const float *z_vals, const float *rays, float *acc,
                                      uint32_t n_rays, uint32_t n_samples, void *stream) {
     if (n_rays != 0 && (!sigma || !z_vals || !rays || !acc)) return fail(NAF_ERR_INVALID_ARGUMENT, "integrate_forward: null pointer");
     if (n_rays == 0) return NAF_OK;
-    { ProfScope prof_("integrate_forward_kernel", (hipStream_t)stream); hipLaunchKernelGGL(integrate_forward_kernel, dim3(grid_for(n_rays, 4)), dim3(256), 0, (hipStream_t)stream, sigma,
-                       z_vals, rays, acc, n_rays, n_samples); }
-    return check_launch("integrate_forward_kernel");
+    return launch("integrate_forward_kernel", integrate_forward_kernel, dim3(grid_for(n_rays, 4)), dim3(256), 0, (hipStream_t)stream,
+                  sigma, z_vals, rays, acc, n_rays, n_samples);
 }
 
 extern "C" int naf_integrate_backward(const float *grad_acc, const float *z_vals, const float *rays, float *grad_sigma,
@@ -268,9 +266,8 @@ extern "C" int naf_integrate_backward(const float *grad_acc, const float *z_vals
     if (n_rays != 0 && (!grad_acc || !z_vals || !rays || !grad_sigma)) return fail(NAF_ERR_INVALID_ARGUMENT, "integrate_backward: null pointer");
     if (n_rays == 0) return NAF_OK;
     const uint64_t total = (uint64_t)n_rays * n_samples;
-    { ProfScope prof_("integrate_backward_kernel", (hipStream_t)stream); hipLaunchKernelGGL(integrate_backward_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                       grad_acc, z_vals, rays, grad_sigma, n_rays, n_samples); }
-    return check_launch("integrate_backward_kernel");
+    return launch("integrate_backward_kernel", integrate_backward_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                  grad_acc, z_vals, rays, grad_sigma, n_rays, n_samples);
 }
 
 extern "C" int naf_fine_depths(const float *rays, const float *t_rand, const float *sigma, const float *u, float *z_out,
@@ -287,25 +284,24 @@ extern "C" int naf_fine_depths(const float *rays, const float *t_rand, const flo
     std::memcpy(&bits, &floor_w, 4);
     if (hipMemsetD32Async((hipDeviceptr_t)scratch, (int)bits, 1, s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "fine_depths: memset failed");
     const uint64_t total = (uint64_t)n_rays * n_samples;
-    { ProfScope prof_("fine_weight_max_kernel", s); hipLaunchKernelGGL(fine_weight_max_kernel, dim3(grid_for(total, 1024, 1024)), dim3(256), 0, s, sigma, total, n_samples, (uint32_t *)scratch); }
-    if (int rc = check_launch("fine_weight_max_kernel")) return rc;
+    if (int rc = launch("fine_weight_max_kernel", fine_weight_max_kernel, dim3(grid_for(total, 1024, 1024)), dim3(256), 0, s, sigma,
+                        total, n_samples, (uint32_t *)scratch)) return rc;
     uint32_t P = 2;
     while (P < n_samples + n_fine) P <<= 1;
     const uint32_t lds = 4u * (2u * n_samples + P) * 4u;
     if (lds > (64u << 10) &&
         hipFuncSetAttribute((const void *)fine_depths_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return fail(NAF_ERR_LAUNCH, "fine_depths: cannot raise dynamic LDS limit");
-    { ProfScope prof_("fine_depths_kernel", s); hipLaunchKernelGGL(fine_depths_kernel, dim3(grid_for(n_rays, 4)), dim3(256), lds, s, rays, t_rand, sigma, (const uint32_t *)scratch, u, z_out,
-                       weights_out, n_rays, n_samples, n_fine, P, perturb != 0, det != 0, seed, ray_index_base); }
-    return check_launch("fine_depths_kernel");
+    return launch("fine_depths_kernel", fine_depths_kernel, dim3(grid_for(n_rays, 4)), dim3(256), lds, s, rays, t_rand, sigma,
+                  (const uint32_t *)scratch, u, z_out, weights_out, n_rays, n_samples, n_fine, P, perturb != 0, det != 0, seed,
+                  ray_index_base);
 }
 
 extern "C" int naf_normalize_inputs(const float *x, uint64_t n, float size, float *out01, int32_t *flag, void *stream) {
     if (n != 0 && (!x || !flag)) return fail(NAF_ERR_INVALID_ARGUMENT, "normalize_inputs: null pointer");
     if (n == 0) return NAF_OK;
-    { ProfScope prof_("normalize_inputs_kernel", (hipStream_t)stream); hipLaunchKernelGGL(normalize_inputs_kernel, dim3(grid_for(n, 1024, 2048)), dim3(256), 0, (hipStream_t)stream, x, n,
-                       size, out01, flag); }
-    return check_launch("normalize_inputs_kernel");
+    return launch("normalize_inputs_kernel", normalize_inputs_kernel, dim3(grid_for(n, 1024, 2048)), dim3(256), 0, (hipStream_t)stream, x,
+                  n, size, out01, flag);
 }
 
 // ---- G3/G4: on-the-fly ray generation (reference src/dataset/tigre.py:402-456, 463-528) --------------------------
@@ -343,7 +339,7 @@ int naf::make_draw_job(const naf_scan_draw *draw, const float *poses, const floa
     if (draw->n_segments == 0 || draw->n_segments > NAF_MAX_DRAW_SEGMENTS || draw->rays_per_segment == 0)
         return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: n_segments must be in [1, 16] and rays_per_segment > 0");
     if (const char *what = detector_refusal(*det, n_projections, /*marched=*/false)) return fail_who("draw_scan_rays", what);
-    if (n_draws != 0 && (((uintptr_t)rays) & 15u)) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: rays must be 16-byte aligned");
+    if (n_draws != 0 && !aligned(rays, 15u)) return misaligned("draw_scan_rays", "rays", 16);
     const uint64_t total = (uint64_t)draw->n_segments * draw->rays_per_segment;
     if (total > 0xffffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: more than 2^32 - 1 draws per call");
     if ((uint64_t)first_draw + n_draws > total) return fail(NAF_ERR_INVALID_ARGUMENT, "draw_scan_rays: draw range outside n_segments * rays_per_segment");
@@ -368,9 +364,7 @@ int naf::make_draw_job(const naf_scan_draw *draw, const float *poses, const floa
 
 int naf::launch_draw(const DrawJob &job, hipStream_t stream) {
     if (job.count == 0) return NAF_OK;
-    { ProfScope prof_("draw_scan_rays_kernel", stream);
-      hipLaunchKernelGGL(draw_scan_rays_kernel, dim3(grid_for(job.count, 256)), dim3(256), 0, stream, job); }
-    return check_launch("draw_scan_rays_kernel");
+    return launch("draw_scan_rays_kernel", draw_scan_rays_kernel, dim3(grid_for(job.count, 256)), dim3(256), 0, stream, job);
 }
 
 extern "C" int naf_draw_scan_rays(const naf_scan_draw *draw, const float *poses, const float *projections, int64_t *pixels,
@@ -386,11 +380,10 @@ extern "C" int naf_generate_rays(const float *poses, const int64_t *pixels, int6
     if (!det || (n != 0 && (!poses || !rays))) return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: null pointer");
     if (const char *what = detector_refusal(*det, n_projections, /*marched=*/false)) return fail_who("generate_rays", what);
     const uint64_t n_pixels = (uint64_t)n_projections * det->det_w * det->det_h;
-    if (((uintptr_t)rays) & 15u) return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: rays must be 16-byte aligned");
+    if (!aligned(rays, 15u)) return misaligned("generate_rays", "rays", 16);
     if (!pixels && (first_pixel < 0 || (uint64_t)first_pixel + n > n_pixels))
         return fail(NAF_ERR_INVALID_ARGUMENT, "generate_rays: pixel range outside the scan");
     if (n == 0) return NAF_OK;
-    { ProfScope prof_("generate_rays_kernel", (hipStream_t)stream); hipLaunchKernelGGL(generate_rays_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, poses, pixels,
-                       first_pixel, rays, n, ray_geo(*det), n_pixels); }
-    return check_launch("generate_rays_kernel");
+    return launch("generate_rays_kernel", generate_rays_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, poses, pixels,
+                  first_pixel, rays, n, ray_geo(*det), n_pixels);
 }

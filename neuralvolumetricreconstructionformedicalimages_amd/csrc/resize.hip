@@ -355,12 +355,8 @@ extern "C" int naf_resize_volume(const float *in, const uint32_t *in_dims, float
             return fail(NAF_ERR_INVALID_ARGUMENT, "resize_volume: an extent above 2^30 is not supported");
     const ResizePlan p = resize_plan(in_dims, out_dims);
     if (p.blocks > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "resize_volume: volume too large for one call");
-    if (workspace_bytes < p.bytes) {
-        std::snprintf(msg, sizeof(msg), "resize_volume: workspace too small (%llu bytes, need %llu)",
-                      (unsigned long long)workspace_bytes, (unsigned long long)p.bytes);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (((uintptr_t)workspace) & 15u) return fail(NAF_ERR_INVALID_ARGUMENT, "resize_volume: workspace must be 16-byte aligned");
+    if (workspace_bytes < p.bytes) return workspace_too_small("resize_volume", workspace_bytes, p.bytes);
+    if (!aligned(workspace, 15u)) return misaligned("resize_volume", "workspace", 16);
     const int forced = forced_form();
     if (forced < 0) return fail(NAF_ERR_INVALID_ARGUMENT, "resize_volume: NAF_RESIZE_FORM must be tiled or direct");
     if (forced == 1 && !p.fits) return fail(NAF_ERR_UNSUPPORTED, "resize_volume: the tiled form does not fit the LDS budget at these shapes");
@@ -372,22 +368,13 @@ extern "C" int naf_resize_volume(const float *in, const uint32_t *in_dims, float
     float2 *partials = minmax ? reinterpret_cast<float2 *>(ws + p.partial_off) : nullptr;
     const Dims3 a = {{in_dims[0], in_dims[1], in_dims[2]}}, b = {{out_dims[0], out_dims[1], out_dims[2]}};
     hipStream_t s = (hipStream_t)stream;
-    { ProfScope prof_("resize_tables_kernel", s);
-      hipLaunchKernelGGL(resize_tables_kernel, dim3((uint32_t)((p.total + 255u) / 256u)), dim3(256), 0, s, a, b, w, base); }
-    int rc = check_launch("resize_tables_kernel");
+    int rc = launch("resize_tables_kernel", resize_tables_kernel, dim3((uint32_t)((p.total + 255u) / 256u)), dim3(256), 0, s, a, b, w,
+                    base);
     if (rc != NAF_OK) return rc;
-    if (tiled) {
-        ProfScope prof_("resize_tiled_kernel", s);
-        hipLaunchKernelGGL(resize_tiled_kernel, dim3((uint32_t)p.blocks), dim3(kThreads), p.lds_bytes, s, in, a, scale, shift, out, b,
-                           w, base, p.tiles[1], p.tiles[2], partials);
-    } else {
-        ProfScope prof_("resize_direct_kernel", s);
-        hipLaunchKernelGGL(resize_direct_kernel, dim3((uint32_t)p.blocks), dim3(kThreads), 0, s, in, a, scale, shift, out, b, w, base,
-                           p.tiles[1], p.tiles[2], partials);
-    }
-    rc = check_launch(tiled ? "resize_tiled_kernel" : "resize_direct_kernel");
+    rc = tiled ? launch("resize_tiled_kernel", resize_tiled_kernel, dim3((uint32_t)p.blocks), dim3(kThreads), p.lds_bytes, s, in, a, scale,
+                        shift, out, b, w, base, p.tiles[1], p.tiles[2], partials)
+               : launch("resize_direct_kernel", resize_direct_kernel, dim3((uint32_t)p.blocks), dim3(kThreads), 0, s, in, a, scale, shift, out,
+                        b, w, base, p.tiles[1], p.tiles[2], partials);
     if (rc != NAF_OK || !minmax) return rc;
-    { ProfScope prof_("resize_minmax_kernel", s);
-      hipLaunchKernelGGL(resize_minmax_kernel, dim3(1), dim3(kFoldThreads), 0, s, partials, p.blocks, minmax); }
-    return check_launch("resize_minmax_kernel");
+    return launch("resize_minmax_kernel", resize_minmax_kernel, dim3(1), dim3(kFoldThreads), 0, s, partials, p.blocks, minmax);
 }

@@ -146,11 +146,8 @@ int sart_residual_scan(const char *who, const char *kernel, const float *volume,
     const int rc = make_scan_launch(who, volume, {projections, y}, dims, dvoxel, poses, n_sub, det, step, &s, kScanTiles, view_index,
                                     n_scan_views);
     if (rc != NAF_OK) return rc;
-    { ProfScope prof_(kernel, (hipStream_t)stream);
-      hipLaunchKernelGGL(subset_residual_kernel<P>, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream,
-                         P::field(s.v, dvoxel), poses, s.g, ViewList{view_index, n_scan_views}, projections, y, r, s.tiles_x,
-                         s.tiles_per_view); }
-    return check_launch(kernel);
+    return launch(kernel, subset_residual_kernel<P>, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream,
+                  P::field(s.v, dvoxel), poses, s.g, ViewList{view_index, n_scan_views}, projections, y, r, s.tiles_x, s.tiles_per_view);
 }
 
 template <class P>
@@ -162,11 +159,9 @@ int sart_backproject_scan(const char *who, const char *kernel, const float *y, c
     const int rc = make_scan_launch(who, num, {y}, dims, dvoxel, poses, n_sub, det, step, &s, kScanTiles, view_index, n_scan_views);
     if (rc != NAF_OK) return rc;
     if (den == num) return fail_who(who, "num and den must be two volumes");
-    { ProfScope prof_(kernel, (hipStream_t)stream);
-      hipLaunchKernelGGL(subset_transpose_kernel<P>, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream,
-                         P::grid(P::field(s.v, dvoxel)), num, den, y, poses, s.g, ViewList{view_index, n_scan_views}, s.tiles_x,
-                         s.tiles_per_view); }
-    return check_launch(kernel);
+    return launch(kernel, subset_transpose_kernel<P>, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream,
+                  P::grid(P::field(s.v, dvoxel)), num, den, y, poses, s.g, ViewList{view_index, n_scan_views}, s.tiles_x,
+                  s.tiles_per_view);
 }
 
 }  // namespace
@@ -220,7 +215,6 @@ extern "C" int naf_sart_update(float *x, float *num, float *den, uint64_t n, flo
     const uint64_t work = std::max<uint64_t>(n_vec, n - 4u * n_vec);
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((work + 255u) / 256u, 2048u);
     UpdateArgs a{relax, nonneg != 0, den_is_reciprocal != 0, zero_den != 0};
-    { ProfScope prof_("sart_update_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(sart_update_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, num, den, n, head, n_vec, a); }
-    return check_launch("sart_update_kernel");
+    return launch("sart_update_kernel", sart_update_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, num, den, n, head, n_vec,
+                  a);
 }

@@ -72,7 +72,7 @@ inline int make_scan_launch(const char *who, const float *volume, std::initializ
 inline int make_ray_launch(const char *who, const float *rays, const void *other, uint64_t n_rays, uint32_t *blocks) {
     const char *what = nullptr;
     if (!rays || !other) what = "null pointer";
-    else if (((uintptr_t)rays) & 15u) what = "rays must be 16-byte aligned";
+    else if (!aligned(rays, 15u)) what = "rays must be 16-byte aligned";
     else if ((n_rays + 255u) / 256u > 0x7fffffffull) what = "too many rays for one call";
     if (what) return fail_who(who, what);
     *blocks = (uint32_t)((n_rays + 255u) / 256u);

@@ -1,51 +1,32 @@
 // ssim.hip -- 3-D SSIM of two fp32 volumes for gfx950 (naf_ssim_3d): the reference's `ssim_3d` evaluation metric
 // (src/utils/util.py:87-139 with scikit-image 0.19.3 defaults), defined in include/naf_hip.h (M1) and DESIGN.md section 11.
 //
-// Layout: one lane per output (axis 1, axis 2) column; a workgroup owns a kTileY x kTileZ tile of window starts and one chunk of
-// axis 0.  For each x slice it stages the (kTileY + 6) x (kTileZ + 6) fp32 input tile of both volumes in LDS, forms the 7-tap
-// sums of the five moments along axis 2 (row pass, fp64 into LDS) and then along axis 1 (column pass, per lane), and keeps the
-// last seven slice sums of each lane in registers: their sum is the 7 x 7 x 7 window.  A chunk starts with 6 warm-up slices.
+// Layout: the slab grid of csrc/slab_grid.h over the window starts (one lane per column of an 8 x 32 tile of them, a workgroup per
+// tile and chunk of axis 0).  For each x slice it stages the (kTileY + 6) x (kTileZ + 6) fp32 input tile of both volumes in LDS, forms
+// the 7-tap sums of the five moments along axis 2 (row pass, fp64 into LDS) and then along axis 1 (column pass, per lane), and keeps
+// the last seven slice sums of each lane in registers: their sum is the 7 x 7 x 7 window.  A chunk starts with 6 warm-up slices.
 // Nothing full-size is written; every workgroup writes one fp64 partial sum of S and a second one-workgroup kernel adds the
-// partials in a fixed order (no atomics: two calls return the same bits).
+// partials in the fixed order of csrc/block_sum.h (no atomics: two calls return the same bits).
 #include <cstdio>
 
+#include "block_sum.h"
 #include "naf_host.h"
+#include "slab_grid.h"
 
 namespace naf {
 
 namespace {
 
 constexpr uint32_t kWin = 7;                       // window edge; N_P = 343
-constexpr uint32_t kTileY = 8, kTileZ = 32;        // window starts per workgroup along axes 1 and 2 (256 lanes)
+constexpr uint32_t kTileY = kSlabTileY, kTileZ = kSlabTileZ;              // window starts per workgroup along axes 1 and 2 (256 lanes)
 constexpr uint32_t kInY = kTileY + kWin - 1, kInZ = kTileZ + kWin - 1;    // 14 x 38 staged inputs
 constexpr uint32_t kIn = kInY * kInZ;              // 532
 constexpr uint32_t kLoads = (kIn + 255u) / 256u;   // staged elements per lane and volume (3)
 constexpr uint32_t kRows = kInY * kTileZ;          // row-pass outputs (448)
-constexpr uint32_t kTargetBlocks = 2048;           // split axis 0 until the grid has about this many workgroups (8 per CU)
-constexpr uint32_t kMinChunk = 16;                 // ... but no chunk shorter than this (each has 6 warm-up slices)
+constexpr uint32_t kMinChunk = 16;                 // no chunk shorter than this (each has 6 warm-up slices)
 constexpr uint32_t kReduceThreads = 256;
 
-struct SsimGrid {
-    uint32_t tiles_y, tiles_z, chunks, chunk;      // chunk = window starts of axis 0 per workgroup
-    uint64_t blocks;
-};
-
-SsimGrid ssim_grid(uint32_t n1, uint32_t n2, uint32_t n3) {
-    SsimGrid g;
-    const uint32_t m1 = n1 - 6, m2 = n2 - 6, m3 = n3 - 6;
-    g.tiles_y = (m2 + kTileY - 1) / kTileY;
-    g.tiles_z = (m3 + kTileZ - 1) / kTileZ;
-    const uint64_t tiles = (uint64_t)g.tiles_y * g.tiles_z;
-    uint64_t want = (kTargetBlocks + tiles - 1) / tiles;
-    const uint64_t most = (m1 + kMinChunk - 1) / kMinChunk;
-    want = std::max<uint64_t>(1, std::min(want, most));
-    g.chunk = (uint32_t)((m1 + want - 1) / want);
-    g.chunks = (m1 + g.chunk - 1) / g.chunk;
-    g.blocks = tiles * g.chunks;
-    return g;
-}
-
-uint64_t ssim_workspace_bytes(const SsimGrid &g) { return (g.blocks * sizeof(double) + 255u) & ~(uint64_t)255u; }
+uint64_t ssim_workspace_bytes(const SlabGrid &g) { return (g.blocks * sizeof(double) + 255u) & ~(uint64_t)255u; }
 
 // S of one window from its five moment sums (skimage.metrics.structural_similarity, gaussian_weights=False, data_range=2).
 __device__ __forceinline__ double ssim_of(double sx, double sy, double sxx, double syy, double sxy) {
@@ -66,12 +47,10 @@ ssim_partial_kernel(const float *__restrict__ x, const float *__restrict__ y, ui
     __shared__ double red[256];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tz_tile = blockIdx.x % tiles_z, rest = blockIdx.x / tiles_z;
-    const uint32_t ty_tile = rest % tiles_y, c = rest / tiles_y;
-    const uint32_t y0 = ty_tile * kTileY, z0 = tz_tile * kTileZ;
-    const uint32_t ly = tid / kTileZ, lz = tid % kTileZ;
+    const SlabLane l = slab_lane(tiles_y, tiles_z, chunk);
+    const uint32_t y0 = l.y0, z0 = l.z0, ly = l.ly, lz = l.lz;
     const bool valid = y0 + ly < n2 - 6 && z0 + lz < n3 - 6;     // this lane's window start is interior
-    const uint32_t a_begin = c * chunk, a_end = min(a_begin + chunk, n1 - 6);
+    const uint32_t a_begin = l.a_begin, a_end = min(a_begin + chunk, n1 - 6);
     const uint32_t s_end = a_end + 6;                              // input slices [a_begin, s_end), s_end <= n1
 
     // staged element e = row * kInZ + col of the tile; elements outside the volume feed no valid window and are staged as 0
@@ -151,7 +130,8 @@ ssim_partial_kernel(const float *__restrict__ x, const float *__restrict__ y, ui
         }
     }
 
-    // fixed-order tree over the workgroup (a NaN propagates: no min / max, nothing skipped)
+    // The tree of block_sum.h, written out: inlined from there, the compiler schedules this kernel's last level differently, and the
+    // kernels here keep the machine code they were measured with.  The order of the additions is the same.
     red[tid] = acc;
     __syncthreads();
     for (uint32_t h = 128; h > 0; h >>= 1) {
@@ -165,11 +145,9 @@ __global__ void __launch_bounds__(kReduceThreads)
 ssim_reduce_kernel(const double *__restrict__ partials, uint64_t n_partials, double count, double *__restrict__ out) {
     __shared__ double red[kReduceThreads];
     const uint32_t tid = threadIdx.x;
-    double t = 0.0;
-    for (uint64_t i = tid; i < n_partials; i += kReduceThreads) t += partials[i];
-    red[tid] = t;
+    red[tid] = strided_sum<kReduceThreads>(partials, n_partials, tid);
     __syncthreads();
-    for (uint32_t h = kReduceThreads / 2; h > 0; h >>= 1) {
+    for (uint32_t h = kReduceThreads / 2; h > 0; h >>= 1) {                // as above
         if (tid < h) red[tid] += red[tid + h];
         __syncthreads();
     }
@@ -184,7 +162,7 @@ using namespace naf;
 
 extern "C" size_t naf_ssim_3d_workspace_bytes(uint32_t n1, uint32_t n2, uint32_t n3) {
     if (n1 < kWin || n2 < kWin || n3 < kWin) return 0;
-    return (size_t)ssim_workspace_bytes(ssim_grid(n1, n2, n3));
+    return (size_t)ssim_workspace_bytes(slab_grid(n1 - 6, n2 - 6, n3 - 6, kMinChunk));
 }
 
 extern "C" int naf_ssim_3d(const float *x, const float *y, uint32_t n1, uint32_t n2, uint32_t n3, double *out, void *workspace,
@@ -196,23 +174,16 @@ extern "C" int naf_ssim_3d(const float *x, const float *y, uint32_t n1, uint32_t
                       n1, n2, n3);
         return fail(NAF_ERR_INVALID_ARGUMENT, msg);
     }
-    const SsimGrid g = ssim_grid(n1, n2, n3);
+    const SlabGrid g = slab_grid(n1 - 6, n2 - 6, n3 - 6, kMinChunk);           // over the window starts
     if (g.blocks > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "ssim_3d: volume too large for one call");
     const uint64_t need = ssim_workspace_bytes(g);
-    if (workspace_bytes < need) {
-        std::snprintf(msg, sizeof(msg), "ssim_3d: workspace too small (%llu bytes, need %llu)", (unsigned long long)workspace_bytes,
-                      (unsigned long long)need);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (((uintptr_t)workspace) & 7u) return fail(NAF_ERR_INVALID_ARGUMENT, "ssim_3d: workspace must be 8-byte aligned");
+    if (workspace_bytes < need) return workspace_too_small("ssim_3d", workspace_bytes, need);
+    if (!aligned(workspace, 7u)) return misaligned("ssim_3d", "workspace", 8);
     double *partials = static_cast<double *>(workspace);
     const double count = (double)(n1 - 6) * (double)(n2 - 6) * (double)(n3 - 6);
-    { ProfScope prof_("ssim_partial_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(ssim_partial_kernel, dim3((uint32_t)g.blocks), dim3(256), 0, (hipStream_t)stream, x, y, n1, n2, n3,
-                         g.tiles_y, g.tiles_z, g.chunk, partials); }
-    const int rc = check_launch("ssim_partial_kernel");
+    const int rc = launch("ssim_partial_kernel", ssim_partial_kernel, dim3((uint32_t)g.blocks), dim3(256), 0, (hipStream_t)stream, x, y,
+                          n1, n2, n3, g.tiles_y, g.tiles_z, g.chunk, partials);
     if (rc != NAF_OK) return rc;
-    { ProfScope prof_("ssim_reduce_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(ssim_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, (hipStream_t)stream, partials, g.blocks, count, out); }
-    return check_launch("ssim_reduce_kernel");
+    return launch("ssim_reduce_kernel", ssim_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, (hipStream_t)stream, partials, g.blocks,
+                  count, out);
 }

@@ -96,12 +96,6 @@ stripe_median_kernel(const uint32_t *__restrict__ s, const uint16_t *__restrict_
     out[((uint64_t)perm[base + u] * H + v) * W + u] = stripe_unkey(median);
 }
 
-int refuse(const char *what) {
-    char msg[200];
-    std::snprintf(msg, sizeof(msg), "stripe_remove_sorting: %s", what);
-    return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-}
-
 const char *shape_error(uint32_t N, uint32_t H, uint32_t W) {
     if (N > kStripeMaxViews) return "more than 4096 views";
     if (H > kMaxExtent || W > kMaxExtent) return "view dimension above 2^24";
@@ -116,8 +110,6 @@ uint64_t workspace_bytes(uint32_t N, uint32_t W, uint64_t rows) {
     return round8(elements * sizeof(float)) + round8(elements * sizeof(uint16_t));
 }
 
-bool aligned(const void *a, uintptr_t mask) { return (((uintptr_t)a) & mask) == 0; }
-
 }  // namespace
 
 }  // namespace naf
@@ -131,19 +123,20 @@ extern "C" size_t naf_stripe_workspace_bytes(uint32_t N, uint32_t H, uint32_t W,
 
 extern "C" int naf_stripe_remove_sorting(const float *p, uint32_t N, uint32_t H, uint32_t W, uint32_t size, void *ws, size_t ws_bytes,
                                          float *out, void *stream) {
+    const char *who = "stripe_remove_sorting";
     if (N == 0 || H == 0 || W == 0) return NAF_OK;
-    if (!p || !out || !ws) return refuse("null pointer");
-    if (const char *err = shape_error(N, H, W)) return refuse(err);
-    if (size < 3u || size > kStripeMaxSize || size % 2u == 0u) return refuse("size must be odd and in [3, 63]");
-    if (size > W) return refuse("size above the number of detector columns");
-    if (!aligned(p, 3u) || !aligned(out, 3u)) return refuse("projections must be 4-byte aligned");
-    if (!aligned(ws, 7u)) return refuse("workspace must be 8-byte aligned");
+    if (!p || !out || !ws) return fail_who(who, "null pointer");
+    if (const char *err = shape_error(N, H, W)) return fail_who(who, err);
+    if (size < 3u || size > kStripeMaxSize || size % 2u == 0u) return fail_who(who, "size must be odd and in [3, 63]");
+    if (size > W) return fail_who(who, "size above the number of detector columns");
+    if (!aligned(p, 3u) || !aligned(out, 3u)) return misaligned(who, "projections", 4);
+    if (!aligned(ws, 7u)) return misaligned(who, "workspace", 8);
     const uint64_t one_row = workspace_bytes(N, W, 1);
     if (ws_bytes < one_row) {
         char msg[160];
         std::snprintf(msg, sizeof(msg), "workspace too small (%llu bytes, one detector row needs %llu)", (unsigned long long)ws_bytes,
                       (unsigned long long)one_row);
-        return refuse(msg);
+        return fail_who(who, msg);
     }
     SortPlan g;
     g.N = N, g.H = H, g.W = W;
@@ -164,14 +157,11 @@ extern "C" int naf_stripe_remove_sorting(const float *p, uint32_t N, uint32_t H,
         const uint32_t rows = (uint32_t)std::min<uint64_t>(group, H - v0);
         uint32_t *s = static_cast<uint32_t *>(ws);
         uint16_t *perm = reinterpret_cast<uint16_t *>(static_cast<char *>(ws) + round8((uint64_t)rows * N * W * sizeof(float)));
-        { ProfScope prof_("stripe_sort_kernel", st);
-          hipLaunchKernelGGL(stripe_sort_kernel, dim3(rows * g.tiles), dim3(kThreads), lds, st, bits, g, v0, s, perm); }
-        const int sorted = check_launch("stripe_sort_kernel");
+        const int sorted = launch("stripe_sort_kernel", stripe_sort_kernel, dim3(rows * g.tiles), dim3(kThreads), lds, st, bits, g, v0, s,
+                                  perm);
         if (sorted != NAF_OK) return sorted;
-        { ProfScope prof_("stripe_median_kernel", st);
-          hipLaunchKernelGGL(stripe_median_kernel, dim3(rows * N * run_tiles), dim3(kThreads), 0, st, s, perm, N, H, W, h, v0, run_tiles,
-                             out_bits); }
-        const int done = check_launch("stripe_median_kernel");
+        const int done = launch("stripe_median_kernel", stripe_median_kernel, dim3(rows * N * run_tiles), dim3(kThreads), 0, st, s, perm,
+                                N, H, W, h, v0, run_tiles, out_bits);
         if (done != NAF_OK) return done;
     }
     return NAF_OK;

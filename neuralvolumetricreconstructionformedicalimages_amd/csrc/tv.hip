@@ -2,55 +2,36 @@
 // (naf_tv_gradient, naf_tv_descent): the regulariser of the ASD-POCS baseline.  Defined in include/naf_hip.h (V2) and DESIGN.md
 // section 14; the per-voxel arithmetic is csrc/tv_device.h.
 //
-// Layout: one lane per (axis 1, axis 2) column of a kTileY x kTileZ tile; a workgroup owns the tile and one chunk of axis 0 and
-// marches through its slices.  Every slice's tile plus a halo of one voxel is staged in LDS once, four slots deep, so that the
-// slices x - 1, x and x + 1 of the 13-point stencil are there with one barrier per slice while slice x + 2 is in flight.
+// Layout: the slab grid of csrc/slab_grid.h (one lane per column of an 8 x 32 tile, a workgroup per tile and chunk of axis 0).  Every
+// slice's tile plus a halo of one voxel is staged in LDS once, four slots deep, so that the slices x - 1, x and x + 1 of the 13-point
+// stencil are there with one barrier per slice while slice x + 2 is in flight.
 //   tv_kernel<kGradient>  writes g and one fp64 partial of sum m and of sum g^2 per workgroup
 //   tv_kernel<kPartials>  the same without the store of g (descent, first pass)
-//   tv_reduce_kernel      adds the partials in a fixed order into stats[0..1] (no atomics: two calls return the same bits)
+//   tv_reduce_kernel      adds the partials in a fixed order into stats[0..1] (csrc/block_sum.h: two calls return the same bits)
 //   tv_kernel<kUpdate>    recomputes g and writes f - (step / ||g||) g to the other buffer (descent, second pass)
 // A descent step therefore reads the volume twice and writes it once; g is never materialised.
 #include <cmath>
-#include <cstdio>
 
+#include "block_sum.h"
 #include "naf_host.h"
+#include "slab_grid.h"
 #include "tv_device.h"
 
 namespace naf {
 
 namespace {
 
-constexpr uint32_t kTileY = 8, kTileZ = 32;        // voxels per workgroup along axes 1 and 2 (256 lanes)
+constexpr uint32_t kTileY = kSlabTileY, kTileZ = kSlabTileZ;              // voxels per workgroup along axes 1 and 2 (256 lanes)
 constexpr uint32_t kInY = kTileY + 2, kInZ = kTileZ + 2;                  // 10 x 34 staged values per slice
 constexpr uint32_t kIn = kInY * kInZ;              // 340
 constexpr uint32_t kLoads = (kIn + 255u) / 256u;   // staged elements per lane (2)
 constexpr uint32_t kSlots = 4;                     // slices kept in LDS
-constexpr uint32_t kTargetBlocks = 2048;           // split axis 0 until the grid has about this many workgroups (8 per CU)
-constexpr uint32_t kMinChunk = 8;                  // ... but no chunk shorter than this (each reads 2 halo slices)
+constexpr uint32_t kMinChunk = 8;                  // no chunk shorter than this (each reads 2 halo slices)
 constexpr uint32_t kReduceThreads = 256;
 
 enum TvMode { kGradient = 0, kPartials = 1, kUpdate = 2 };
 
-struct TvGrid {
-    uint32_t tiles_y, tiles_z, chunks, chunk;      // chunk = slices of axis 0 per workgroup
-    uint64_t blocks;
-};
-
-TvGrid tv_grid(uint32_t n1, uint32_t n2, uint32_t n3) {
-    TvGrid g;
-    g.tiles_y = (n2 + kTileY - 1) / kTileY;
-    g.tiles_z = (n3 + kTileZ - 1) / kTileZ;
-    const uint64_t tiles = (uint64_t)g.tiles_y * g.tiles_z;
-    uint64_t want = (kTargetBlocks + tiles - 1) / tiles;
-    const uint64_t most = (n1 + kMinChunk - 1) / kMinChunk;
-    want = std::max<uint64_t>(1, std::min(want, most));
-    g.chunk = (uint32_t)((n1 + want - 1) / want);
-    g.chunks = (n1 + g.chunk - 1) / g.chunk;
-    g.blocks = tiles * g.chunks;
-    return g;
-}
-
-uint64_t tv_workspace_bytes(const TvGrid &g) { return (g.blocks * 2u * sizeof(double) + 255u) & ~(uint64_t)255u; }
+uint64_t tv_workspace_bytes(const SlabGrid &g) { return (g.blocks * 2u * sizeof(double) + 255u) & ~(uint64_t)255u; }
 
 template <int kMode>
 __global__ void __launch_bounds__(256)
@@ -60,13 +41,11 @@ tv_kernel(const float *__restrict__ f, uint32_t n1, uint32_t n2, uint32_t n3, ui
     __shared__ double red[2][256];
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tz_tile = blockIdx.x % tiles_z, rest = blockIdx.x / tiles_z;
-    const uint32_t ty_tile = rest % tiles_y, c = rest / tiles_y;
-    const uint32_t y0 = ty_tile * kTileY, z0 = tz_tile * kTileZ;
-    const uint32_t ly = tid / kTileZ, lz = tid % kTileZ;
+    const SlabLane l = slab_lane(tiles_y, tiles_z, chunk);
+    const uint32_t y0 = l.y0, z0 = l.z0, ly = l.ly, lz = l.lz;
     const uint32_t y = y0 + ly, z = z0 + lz;
     const bool valid = y < n2 && z < n3;
-    const uint32_t a_begin = c * chunk, a_end = min(a_begin + chunk, n1);
+    const uint32_t a_begin = l.a_begin, a_end = min(a_begin + chunk, n1);
 
     // staged element e = row * kInZ + col holds voxel (y0 + row - 1, z0 + col - 1); positions outside the volume are staged as 0
     // and never used (their has_lo / has_hi flag is false)
@@ -149,17 +128,7 @@ tv_kernel(const float *__restrict__ f, uint32_t n1, uint32_t n2, uint32_t n3, ui
     }
     if (kMode == kUpdate) return;
 
-    // fixed-order tree over the workgroup (a NaN propagates: nothing skipped)
-    red[0][tid] = sum_m;
-    red[1][tid] = sum_g2;
-    __syncthreads();
-    for (uint32_t h = 128; h > 0; h >>= 1) {
-        if (tid < h) {
-            red[0][tid] += red[0][tid + h];
-            red[1][tid] += red[1][tid + h];
-        }
-        __syncthreads();
-    }
+    block_sum<256>(red, sum_m, sum_g2, tid);
     if (tid == 0) {
         partials[2u * (uint64_t)blockIdx.x] = red[0][0];
         partials[2u * (uint64_t)blockIdx.x + 1u] = red[1][0];
@@ -171,20 +140,11 @@ tv_reduce_kernel(const double *__restrict__ partials, uint64_t n_partials, doubl
     __shared__ double red[2][kReduceThreads];
     const uint32_t tid = threadIdx.x;
     double t = 0.0, u = 0.0;
-    for (uint64_t i = tid; i < n_partials; i += kReduceThreads) {
+    for (uint64_t i = tid; i < n_partials; i += kReduceThreads) {      // the two interleaved sums, each in ascending order
         t += partials[2u * i];
         u += partials[2u * i + 1u];
     }
-    red[0][tid] = t;
-    red[1][tid] = u;
-    __syncthreads();
-    for (uint32_t h = kReduceThreads / 2; h > 0; h >>= 1) {
-        if (tid < h) {
-            red[0][tid] += red[0][tid + h];
-            red[1][tid] += red[1][tid + h];
-        }
-        __syncthreads();
-    }
+    block_sum<kReduceThreads>(red, t, u, tid);
     if (tid == 0) {
         stats[0] = red[0][0];
         stats[1] = red[1][0];
@@ -193,47 +153,26 @@ tv_reduce_kernel(const double *__restrict__ partials, uint64_t n_partials, doubl
 
 // Argument checks shared by the two entry points; fills the grid.
 int tv_check(const char *who, uint32_t n1, uint32_t n2, uint32_t n3, float eps, const void *workspace, size_t workspace_bytes,
-             TvGrid *g) {
-    char msg[160];
-    if (n1 == 0 || n2 == 0 || n3 == 0) {
-        std::snprintf(msg, sizeof(msg), "%s: zero volume dimension", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (!(eps > 0.0f) || !std::isfinite(eps)) {
-        std::snprintf(msg, sizeof(msg), "%s: eps must be > 0 and finite", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    *g = tv_grid(n1, n2, n3);
-    if (g->blocks > 0x7fffffffull) {
-        std::snprintf(msg, sizeof(msg), "%s: volume too large for one call", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+             SlabGrid *g) {
+    if (n1 == 0 || n2 == 0 || n3 == 0) return fail_who(who, "zero volume dimension");
+    if (!(eps > 0.0f) || !std::isfinite(eps)) return fail_who(who, "eps must be > 0 and finite");
+    *g = slab_grid(n1, n2, n3, kMinChunk);
+    if (g->blocks > 0x7fffffffull) return fail_who(who, "volume too large for one call");
     const uint64_t need = tv_workspace_bytes(*g);
-    if (workspace_bytes < need) {
-        std::snprintf(msg, sizeof(msg), "%s: workspace too small (%llu bytes, need %llu)", who, (unsigned long long)workspace_bytes,
-                      (unsigned long long)need);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (((uintptr_t)workspace) & 7u) {
-        std::snprintf(msg, sizeof(msg), "%s: workspace must be 8-byte aligned", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (workspace_bytes < need) return workspace_too_small(who, workspace_bytes, need);
+    if (!aligned(workspace, 7u)) return misaligned(who, "workspace", 8);
     return NAF_OK;
 }
 
 template <int kMode>
-int tv_launch(const char *name, const TvGrid &g, const float *f, uint32_t n1, uint32_t n2, uint32_t n3, float eps, float step,
+int tv_launch(const char *name, const SlabGrid &g, const float *f, uint32_t n1, uint32_t n2, uint32_t n3, float eps, float step,
               float *out, double *partials, const double *stats, hipStream_t stream) {
-    { ProfScope prof_(name, stream);
-      hipLaunchKernelGGL(tv_kernel<kMode>, dim3((uint32_t)g.blocks), dim3(256), 0, stream, f, n1, n2, n3, g.tiles_y, g.tiles_z,
-                         g.chunk, eps, step, out, partials, stats); }
-    return check_launch(name);
+    return launch(name, tv_kernel<kMode>, dim3((uint32_t)g.blocks), dim3(256), 0, stream, f, n1, n2, n3, g.tiles_y, g.tiles_z, g.chunk,
+                  eps, step, out, partials, stats);
 }
 
-int tv_reduce(const TvGrid &g, const double *partials, double *stats, hipStream_t stream) {
-    { ProfScope prof_("tv_reduce_kernel", stream);
-      hipLaunchKernelGGL(tv_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, stream, partials, g.blocks, stats); }
-    return check_launch("tv_reduce_kernel");
+int tv_reduce(const SlabGrid &g, const double *partials, double *stats, hipStream_t stream) {
+    return launch("tv_reduce_kernel", tv_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, stream, partials, g.blocks, stats);
 }
 
 }  // namespace
@@ -244,14 +183,14 @@ using namespace naf;
 
 extern "C" size_t naf_tv_workspace_bytes(uint32_t n1, uint32_t n2, uint32_t n3) {
     if (n1 == 0 || n2 == 0 || n3 == 0) return 0;
-    return (size_t)tv_workspace_bytes(tv_grid(n1, n2, n3));
+    return (size_t)tv_workspace_bytes(slab_grid(n1, n2, n3, kMinChunk));
 }
 
 extern "C" int naf_tv_gradient(const float *x, uint32_t n1, uint32_t n2, uint32_t n3, float eps, float *grad, double *stats,
                                void *workspace, size_t workspace_bytes, void *stream) {
     if (!x || !grad || !stats || !workspace) return fail(NAF_ERR_INVALID_ARGUMENT, "tv_gradient: null pointer");
     if (x == grad) return fail(NAF_ERR_INVALID_ARGUMENT, "tv_gradient: grad must not be x (a voxel's neighbours read x)");
-    TvGrid g;
+    SlabGrid g;
     int rc = tv_check("tv_gradient", n1, n2, n3, eps, workspace, workspace_bytes, &g);
     if (rc != NAF_OK) return rc;
     double *partials = static_cast<double *>(workspace);
@@ -263,7 +202,7 @@ extern "C" int naf_tv_gradient(const float *x, uint32_t n1, uint32_t n2, uint32_
 extern "C" int naf_tv_descent(float *x, float *scratch, uint32_t n1, uint32_t n2, uint32_t n3, float step, uint32_t n_steps,
                               float eps, double *stats, void *workspace, size_t workspace_bytes, void *stream) {
     if (!x || !scratch || !stats || !workspace) return fail(NAF_ERR_INVALID_ARGUMENT, "tv_descent: null pointer");
-    TvGrid g;
+    SlabGrid g;
     int rc = tv_check("tv_descent", n1, n2, n3, eps, workspace, workspace_bytes, &g);
     if (rc != NAF_OK) return rc;
     if (!std::isfinite(step) || step < 0.0f) return fail(NAF_ERR_INVALID_ARGUMENT, "tv_descent: step must be >= 0 and finite");

@@ -2,9 +2,8 @@
 // of the FISTA-TV baseline.  Defined in include/naf_hip.h (V3) and DESIGN.md section 18; the per-voxel arithmetic is
 // csrc/tvprox_device.h.
 //
-// tvprox_step_kernel, one dual iteration in one launch (seven arrays read, six written).  Layout as in tv.hip: one lane per
-// (axis 1, axis 2) column of a kTileY x kTileZ tile, lanes along the contiguous axis 2; a workgroup owns the tile and one chunk of
-// axis 0 and marches through its slices.  Per slice x it
+// tvprox_step_kernel, one dual iteration in one launch (seven arrays read, six written).  Layout: the slab grid of csrc/slab_grid.h
+// (one lane per column of an 8 x 32 tile, a workgroup per tile and chunk of axis 0).  Per slice x it
 //   1. stages r_0[x], r_1[x], r_2[x] of the tile plus a halo of one voxel in LDS.  r_0[x] is what the lane fetched as r_0[x + 1]
 //      one slice earlier and kept in a register; the r_1 and r_2 planes serve a voxel and its v - e_1 / v - e_2 neighbours from
 //      one load;
@@ -15,41 +14,21 @@
 // and 2 on slice a_begin - 1 to have u[x - 1].
 // tvprox_primal_kernel is a plain map with neighbour reads, run once per prox.
 #include <cmath>
-#include <cstdio>
 
 #include "naf_host.h"
+#include "slab_grid.h"
 #include "tvprox_device.h"
 
 namespace naf {
 
 namespace {
 
-constexpr uint32_t kTileY = 8, kTileZ = 32;        // voxels per workgroup along axes 1 and 2 (256 lanes)
+constexpr uint32_t kTileY = kSlabTileY, kTileZ = kSlabTileZ;              // voxels per workgroup along axes 1 and 2 (256 lanes)
 constexpr uint32_t kInY = kTileY + 2, kInZ = kTileZ + 2;                  // 10 x 34 staged values per plane
 constexpr uint32_t kIn = kInY * kInZ;              // 340
 constexpr uint32_t kLoads = (kIn + 255u) / 256u;   // staged elements per lane (2)
-constexpr uint32_t kTargetBlocks = 2048;           // split axis 0 until the grid has about this many workgroups (8 per CU)
-constexpr uint32_t kMinChunk = 8;                  // ... but no chunk shorter than this (each recomputes one slice of u)
+constexpr uint32_t kMinChunk = 8;                  // no chunk shorter than this (each recomputes one slice of u)
 constexpr uint32_t kPrimalThreads = 256;
-
-struct ProxGrid {
-    uint32_t tiles_y, tiles_z, chunks, chunk;      // chunk = slices of axis 0 per workgroup
-    uint64_t blocks;
-};
-
-ProxGrid prox_grid(uint32_t n1, uint32_t n2, uint32_t n3) {
-    ProxGrid g;
-    g.tiles_y = (n2 + kTileY - 1) / kTileY;
-    g.tiles_z = (n3 + kTileZ - 1) / kTileZ;
-    const uint64_t tiles = (uint64_t)g.tiles_y * g.tiles_z;
-    uint64_t want = (kTargetBlocks + tiles - 1) / tiles;
-    const uint64_t most = (n1 + kMinChunk - 1) / kMinChunk;
-    want = std::max<uint64_t>(1, std::min(want, most));
-    g.chunk = (uint32_t)((n1 + want - 1) / want);
-    g.chunks = (n1 + g.chunk - 1) / g.chunk;
-    g.blocks = tiles * g.chunks;
-    return g;
-}
 
 // r and r_next are different buffers and p is only touched at the lane's own voxel, so every pointer may be __restrict__.
 __global__ void __launch_bounds__(256)
@@ -60,13 +39,11 @@ tvprox_step_kernel(const float *__restrict__ b, const float *__restrict__ r, flo
     __shared__ float us[2][kIn];                   // u[x] on the rows 0 .. kTileY and columns 0 .. kTileZ of the same layout
 
     const uint32_t tid = threadIdx.x;
-    const uint32_t tz_tile = blockIdx.x % tiles_z, rest = blockIdx.x / tiles_z;
-    const uint32_t ty_tile = rest % tiles_y, c = rest / tiles_y;
-    const uint32_t y0 = ty_tile * kTileY, z0 = tz_tile * kTileZ;
-    const uint32_t ly = tid / kTileZ, lz = tid % kTileZ;
+    const SlabLane l = slab_lane(tiles_y, tiles_z, chunk);
+    const uint32_t y0 = l.y0, z0 = l.z0, ly = l.ly, lz = l.lz;
     const uint32_t y = y0 + ly, z = z0 + lz;
     const bool valid = y < n2 && z < n3;
-    const uint32_t a_begin = c * chunk, a_end = min(a_begin + chunk, n1);
+    const uint32_t a_begin = l.a_begin, a_end = min(a_begin + chunk, n1);
     const uint32_t x_first = a_begin > 0 ? a_begin - 1u : 0u;             // the slice before the chunk gives u[x - 1]
     const uint64_t slice = (uint64_t)n2 * n3, volume = slice * n1;        // 64-bit: a 1024^3 fp32 volume is 4 GiB
 
@@ -188,21 +165,6 @@ tvprox_primal_kernel(const float *b, const float *__restrict__ p, float *x, uint
     x[at] = tvprox_primal(b[at], tvprox_adjoint(lo, hi, has_lo, has_hi), lambda, nonneg != 0);
 }
 
-int prox_check_dims(const char *who, uint32_t n1, uint32_t n2, uint32_t n3) {
-    char msg[160];
-    if (n1 == 0 || n2 == 0 || n3 == 0) {
-        std::snprintf(msg, sizeof(msg), "%s: zero volume dimension", who);
-        return fail(NAF_ERR_UNSUPPORTED, msg);
-    }
-    return NAF_OK;
-}
-
-int prox_too_large(const char *who) {
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "%s: volume too large for one call", who);
-    return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-}
-
 }  // namespace
 
 }  // namespace naf
@@ -213,34 +175,26 @@ extern "C" int naf_tv_prox_step(const float *b, const float *r, float *p, float 
                                 float lambda, float momentum, int nonneg, void *stream) {
     if (!b || !r || !p) return fail(NAF_ERR_INVALID_ARGUMENT, "tv_prox_step: null pointer");
     if (r_next == r) return fail(NAF_ERR_INVALID_ARGUMENT, "tv_prox_step: r_next must not be r (a voxel's neighbours read r)");
-    int rc = prox_check_dims("tv_prox_step", n1, n2, n3);
-    if (rc != NAF_OK) return rc;
+    if (n1 == 0 || n2 == 0 || n3 == 0) return fail_who("tv_prox_step", "zero volume dimension", NAF_ERR_UNSUPPORTED);
     if (!std::isfinite(lambda) || !(lambda > 0.0f))
         return fail(NAF_ERR_INVALID_ARGUMENT, "tv_prox_step: lambda must be > 0 and finite");
     if (!std::isfinite(momentum) || momentum < 0.0f)
         return fail(NAF_ERR_INVALID_ARGUMENT, "tv_prox_step: momentum must be >= 0 and finite");
-    const ProxGrid g = prox_grid(n1, n2, n3);
-    if (g.blocks > 0x7fffffffull) return prox_too_large("tv_prox_step");
-    hipStream_t s = (hipStream_t)stream;
-    { ProfScope prof_("tvprox_step_kernel", s);
-      hipLaunchKernelGGL(tvprox_step_kernel, dim3((uint32_t)g.blocks), dim3(256), 0, s, b, r, p, r_next, n1, n2, n3, g.tiles_y,
-                         g.tiles_z, g.chunk, lambda, tvprox_dual_step(lambda), momentum, nonneg); }
-    return check_launch("tvprox_step_kernel");
+    const SlabGrid g = slab_grid(n1, n2, n3, kMinChunk);
+    if (g.blocks > 0x7fffffffull) return fail_who("tv_prox_step", "volume too large for one call");
+    return launch("tvprox_step_kernel", tvprox_step_kernel, dim3((uint32_t)g.blocks), dim3(256), 0, (hipStream_t)stream, b, r, p, r_next,
+                  n1, n2, n3, g.tiles_y, g.tiles_z, g.chunk, lambda, tvprox_dual_step(lambda), momentum, nonneg);
 }
 
 extern "C" int naf_tv_prox_primal(const float *b, const float *p, float *x, uint32_t n1, uint32_t n2, uint32_t n3, float lambda,
                                   int nonneg, void *stream) {
     if (!b || !p || !x) return fail(NAF_ERR_INVALID_ARGUMENT, "tv_prox_primal: null pointer");
-    int rc = prox_check_dims("tv_prox_primal", n1, n2, n3);
-    if (rc != NAF_OK) return rc;
+    if (n1 == 0 || n2 == 0 || n3 == 0) return fail_who("tv_prox_primal", "zero volume dimension", NAF_ERR_UNSUPPORTED);
     if (!std::isfinite(lambda) || lambda < 0.0f)
         return fail(NAF_ERR_INVALID_ARGUMENT, "tv_prox_primal: lambda must be >= 0 and finite");
     const uint32_t tiles_z = (n3 + kPrimalThreads - 1u) / kPrimalThreads;
     const uint64_t blocks = (uint64_t)n1 * n2 * tiles_z;
-    if (blocks > 0x7fffffffull) return prox_too_large("tv_prox_primal");
-    hipStream_t s = (hipStream_t)stream;
-    { ProfScope prof_("tvprox_primal_kernel", s);
-      hipLaunchKernelGGL(tvprox_primal_kernel, dim3((uint32_t)blocks), dim3(kPrimalThreads), 0, s, b, p, x, n1, n2, n3, tiles_z,
-                         lambda, nonneg); }
-    return check_launch("tvprox_primal_kernel");
+    if (blocks > 0x7fffffffull) return fail_who("tv_prox_primal", "volume too large for one call");
+    return launch("tvprox_primal_kernel", tvprox_primal_kernel, dim3((uint32_t)blocks), dim3(kPrimalThreads), 0, (hipStream_t)stream, b, p,
+                  x, n1, n2, n3, tiles_z, lambda, nonneg);
 }

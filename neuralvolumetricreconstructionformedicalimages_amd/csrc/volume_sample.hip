@@ -9,7 +9,6 @@
 // with one instruction) rather than three 4-byte loads at a stride of 12 bytes, which would issue three instructions over the same
 // six cache lines.  The draw kernel writes its points the same way.
 #include <cmath>
-#include <cstdio>
 
 #include "naf_host.h"
 #include "volume_sample_device.h"
@@ -56,24 +55,12 @@ volume_draw_sample_kernel(const float *__restrict__ f, SampleGrid g, DrawBox box
 
 // Argument checks shared by the two entry points; fills the grid.
 int sample_check(const char *who, const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, SampleGrid *g) {
-    char msg[160];
-    if (!volume || !dvoxel) {
-        std::snprintf(msg, sizeof(msg), "%s: null pointer", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (n1 == 0 || n2 == 0 || n3 == 0) {
-        std::snprintf(msg, sizeof(msg), "%s: zero volume dimension", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
-    if (n1 > NAF_VOLUME_SAMPLE_MAX_EXTENT || n2 > NAF_VOLUME_SAMPLE_MAX_EXTENT || n3 > NAF_VOLUME_SAMPLE_MAX_EXTENT) {
-        std::snprintf(msg, sizeof(msg), "%s: volume dimension above 2^24 (an index would not be exact in fp32)", who);
-        return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-    }
+    if (!volume || !dvoxel) return fail_who(who, "null pointer");
+    if (n1 == 0 || n2 == 0 || n3 == 0) return fail_who(who, "zero volume dimension");
+    if (n1 > NAF_VOLUME_SAMPLE_MAX_EXTENT || n2 > NAF_VOLUME_SAMPLE_MAX_EXTENT || n3 > NAF_VOLUME_SAMPLE_MAX_EXTENT)
+        return fail_who(who, "volume dimension above 2^24 (an index would not be exact in fp32)");
     for (int a = 0; a < 3; ++a) {
-        if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) {
-            std::snprintf(msg, sizeof(msg), "%s: voxel size must be > 0 and finite", who);
-            return fail(NAF_ERR_INVALID_ARGUMENT, msg);
-        }
+        if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) return fail_who(who, "voxel size must be > 0 and finite");
     }
     sample_grid(n1, n2, n3, dvoxel, g);
     return NAF_OK;
@@ -92,14 +79,11 @@ extern "C" int naf_volume_sample_points(const float *volume, uint32_t n1, uint32
     const int rc = sample_check("volume_sample_points", volume, n1, n2, n3, dvoxel, &g);
     if (rc != NAF_OK) return rc;
     if (!points || !out) return fail(NAF_ERR_INVALID_ARGUMENT, "volume_sample_points: null pointer");
-    if ((((uintptr_t)volume) | ((uintptr_t)points) | ((uintptr_t)out)) & 3u)
-        return fail(NAF_ERR_INVALID_ARGUMENT, "volume_sample_points: pointers must be 4-byte aligned");
+    if (!aligned(volume, 3u) || !aligned(points, 3u) || !aligned(out, 3u)) return misaligned("volume_sample_points", "pointers", 4);
     const uint64_t blocks = (n + kSampleThreads - 1) / kSampleThreads;
     if (blocks > 0x7fffffffull) return fail(NAF_ERR_INVALID_ARGUMENT, "volume_sample_points: too many points for one call");
-    { ProfScope prof_("volume_sample_points_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(volume_sample_points_kernel, dim3((uint32_t)blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, volume, g,
-                         reinterpret_cast<const Point3 *>(points), n, out); }
-    return check_launch("volume_sample_points_kernel");
+    return launch("volume_sample_points_kernel", volume_sample_points_kernel, dim3((uint32_t)blocks), dim3(kSampleThreads), 0,
+                  (hipStream_t)stream, volume, g, reinterpret_cast<const Point3 *>(points), n, out);
 }
 
 extern "C" int naf_volume_draw_sample(const float *volume, const uint32_t *dims, const float *dvoxel, const float *lo, const float *hi,
@@ -110,8 +94,8 @@ extern "C" int naf_volume_draw_sample(const float *volume, const uint32_t *dims,
     const int rc = sample_check("volume_draw_sample", volume, dims[0], dims[1], dims[2], dvoxel, &g);
     if (rc != NAF_OK) return rc;
     if (!lo || !hi || !points_out || !targets_out) return fail(NAF_ERR_INVALID_ARGUMENT, "volume_draw_sample: null pointer");
-    if ((((uintptr_t)volume) | ((uintptr_t)points_out) | ((uintptr_t)targets_out)) & 3u)
-        return fail(NAF_ERR_INVALID_ARGUMENT, "volume_draw_sample: pointers must be 4-byte aligned");
+    if (!aligned(volume, 3u) || !aligned(points_out, 3u) || !aligned(targets_out, 3u))
+        return misaligned("volume_draw_sample", "pointers", 4);
     DrawBox box;
     for (int a = 0; a < 3; ++a) {
         if (!std::isfinite(lo[a]) || !std::isfinite(hi[a]) || !(lo[a] <= hi[a]) || !std::isfinite(hi[a] - lo[a]))
@@ -120,8 +104,6 @@ extern "C" int naf_volume_draw_sample(const float *volume, const uint32_t *dims,
         box.hi[a] = hi[a];
     }
     const uint32_t blocks = (uint32_t)(((uint64_t)n + kSampleThreads - 1) / kSampleThreads);
-    { ProfScope prof_("volume_draw_sample_kernel", (hipStream_t)stream);
-      hipLaunchKernelGGL(volume_draw_sample_kernel, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream, volume, g, box, seed, step,
-                         n, reinterpret_cast<Point3 *>(points_out), targets_out); }
-    return check_launch("volume_draw_sample_kernel");
+    return launch("volume_draw_sample_kernel", volume_draw_sample_kernel, dim3(blocks), dim3(kSampleThreads), 0, (hipStream_t)stream,
+                  volume, g, box, seed, step, n, reinterpret_cast<Point3 *>(points_out), targets_out);
 }
