@@ -161,14 +161,12 @@ static int launch_encode(const Src &src, const void *table, const int32_t *offse
     auto kern = encode_kernel<TT, FT, C, Src, 0u>;
     if constexpr (kCanWindow) { if (window) kern = encode_kernel<TT, FT, C, Src, 2u>; }
     const uint32_t kPts = window ? 2u : encode_points_per_thread(C);
-    if ((flags & NAF_CFG_PER_LEVEL_LAUNCHES) != 0u && chunk == 0u) {
+    if ((flags & NAF_CFG_PER_LEVEL_LAUNCHES) != 0u && chunk == 0u) {      // a level's launch is timed under its own name; a failed one ends the loop
         static const char *const names[32] = NAF_LEVEL_NAMES("encode_kernel_L");
-        for (uint32_t l = lv_begin; l < lv_end; ++l) {
-            ProfScope prof_(level_name(names, l), s);
-            hipLaunchKernelGGL(kern, dim3(hash_grid_x((B + kPts - 1u) / kPts), 1), dim3(256), 0, s, src,
-                               (const typename TT::store_t *)table, offsets, (typename FT::store_t *)feat, B, H, l, 0u, 1u, L, 0u, 0u, blc ? 1u : 0u);
-        }
-        return check_launch("encode_kernel");
+        for (uint32_t l = lv_begin; l < lv_end; ++l)
+            if (int rc = launch_as(level_name(names, l), "encode_kernel", kern, dim3(hash_grid_x((B + kPts - 1u) / kPts), 1), dim3(256), 0, s, src,
+                                   (const typename TT::store_t *)table, offsets, (typename FT::store_t *)feat, B, H, l, 0u, 1u, L, 0u, 0u, blc ? 1u : 0u)) return rc;
+        return NAF_OK;
     }
     const uint32_t gx = hash_grid_x((B + kPts - 1u) / kPts);
     const bool interleaved = (flags & NAF_CFG_LEVELS_INTERLEAVED) != 0u && gx <= 65535u;
@@ -185,9 +183,8 @@ static int launch_encode(const Src &src, const void *table, const int32_t *offse
     const bool grouped = !interleaved && log2g != 0u && (nl >= 8u || nl != L);
     const uint32_t order = interleaved ? 1u : grouped ? 4u + log2g : 0u;
     const dim3 grid = interleaved ? dim3(nl, gx) : grouped ? dim3((nl * gx + 7u) / 8u * 8u) : dim3(gx, nl);
-    { ProfScope prof_("encode_kernel", s); hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, src,
-                       (const typename TT::store_t *)table, offsets, (typename FT::store_t *)feat, B, H, lv_begin, order, nl, L, gx, chunk, blc ? 1u : 0u); }
-    return check_launch("encode_kernel");
+    return launch("encode_kernel", kern, grid, dim3(256), 0, s, src,
+                  (const typename TT::store_t *)table, offsets, (typename FT::store_t *)feat, B, H, lv_begin, order, nl, L, gx, chunk, blc ? 1u : 0u);
 }
 
 }  // namespace naf

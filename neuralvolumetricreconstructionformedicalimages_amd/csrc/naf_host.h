@@ -48,13 +48,20 @@ class ProfScope {
     hipStream_t stream_;
 };
 
-// One launch: times `kernel` under `name` when profiling is on, launches it, and reports a failed launch under the same name.  A site
-// that picks one of several instantiations under one name calls this once per branch.
+// One launch under two names: times `kernel` under `timed` when profiling is on (the aggregate name bench.py's per-kernel table reads:
+// mlp_forward_kernel for every forward instantiation, a level's own name on the per-level diagnostic path), launches it, and reports a
+// failed launch under `name`, the kernel's own.
 template <typename K, typename... Args>
-static int launch(const char *name, K kernel, dim3 grid, dim3 block, uint32_t lds_bytes, hipStream_t stream, Args... args) {
-    { ProfScope prof_(name, stream);
+static int launch_as(const char *timed, const char *name, K kernel, dim3 grid, dim3 block, uint32_t lds_bytes, hipStream_t stream, Args... args) {
+    { ProfScope prof_(timed, stream);
       hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...); }
     return check_launch(name);
+}
+// One launch, timed and reported under the same name.  A site that picks one of several instantiations under one name calls this once
+// per branch, or picks the kernel first.
+template <typename K, typename... Args>
+static int launch(const char *name, K kernel, dim3 grid, dim3 block, uint32_t lds_bytes, hipStream_t stream, Args... args) {
+    return launch_as(name, name, kernel, grid, block, lds_bytes, stream, args...);
 }
 
 }  // namespace naf

@@ -22,7 +22,7 @@
 //   mlp16_kernels.h    2b, 3b, 3c, 5: the 16-point bf16 kernels, mlp16_train_kernel, mlp_grad_reduce_kernel
 //   fused_forward.h    2c: fused_forward_kernel
 //   levels_gather.h    levels_gather_kernel (level-parallel training)
-//   render_step.h      the host drivers: workspace, launches, the bodies of the entry points
+//   render_step.h      the host drivers: workspace, launches (each through naf_host.h's launch / launch_as), the bodies of the entry points
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -291,7 +291,7 @@ extern "C" int naf_levels_scatter(const float *rays, const float *t_rand, const 
     if (int rc = check_ray_call("levels_scatter", cfg, t_rand, n_rays, !rays || !grad_blocks || !offsets || !grad_embeddings || !workspace, kEmptyOk, &lv,
                                 &n_ranks)) return rc;
     if (n_rays == 0) return NAF_OK;
-    const size_t esz = cfg->mlp_precision == NAF_F32 ? 4 : 2;
+    const size_t esz = feature_elem_bytes(cfg);
     if (block_stride_bytes < (size_t)(level_end - level_begin) * (n_rays / n_ranks) * cfg->n_samples * cfg->C * esz || block_stride_bytes % esz != 0)
         return fail(NAF_ERR_INVALID_ARGUMENT, "levels_scatter: block stride smaller than a rank's block");
     AdamTail tail;
@@ -339,7 +339,7 @@ extern "C" int naf_field_forward_grid(const double *start, const double *stop, c
     src.bound = cfg->bound;
     // The grid is walked in ranges of its traversal order that fit the caller's workspace (every point is evaluated on its own,
     // so the ranges give the same bits as one call): a 1024^3 query needs 64 GiB of features at once, or any smaller buffer.
-    const size_t per_point = forward_workspace_bytes(cfg, 1u << 20) > 256 ? (size_t)cfg->L * cfg->C * (cfg->mlp_precision == NAF_F32 ? 4u : 2u) : 0u;
+    const size_t per_point = forward_workspace_bytes(cfg, 1u << 20) > 256 ? (size_t)cfg->L * cfg->C * feature_elem_bytes(cfg) : 0u;
     uint64_t chunk = total;
     if (per_point != 0u) {
         if (workspace_bytes < 512u + 1024u * per_point) return fail(NAF_ERR_INVALID_ARGUMENT, "field_forward_grid: workspace too small (see naf_forward_workspace_bytes)");

@@ -1,6 +1,7 @@
 // render_step.h -- the host drivers of the fused step: the workspace layout (carve), the cfg check, the launches of the encoder, the
 // MLP kernels and the table scatter (run_*), and the bodies of the entry points (*_impl).  The launch decisions are mlp_step_plan.h's
-// (MLP kernels) and scatter_host.h's (binned scatter); the structs below name a call's buffers once, in the entry point, so that
+// (MLP kernels) and scatter_host.h's (binned scatter), every launch itself is naf_host.h's launch() / launch_as(): profile name,
+// launch, check.  The structs below name a call's buffers once, in the entry point, so that
 // nothing here passes them by position.  Included from render_fused.hip only: FxRecords is no template, so it instantiates its
 // kernels in every translation unit that declares it (scatter_host.h).
 #pragma once
@@ -80,9 +81,14 @@ struct Workspace {
     size_t bytes;
 };
 
+// the features are held in the MLP's operand precision (P::feat_t); a feature tensor [L, n_points, C] is rounded up to 256 bytes
+static size_t feature_elem_bytes(const naf_render_cfg *cfg) { return cfg->mlp_precision == NAF_F32 ? 4 : 2; }
+static size_t feature_bytes(const naf_render_cfg *cfg, uint64_t n_points) {
+    return ((size_t)n_points * cfg->L * cfg->C * feature_elem_bytes(cfg) + 255) & ~(size_t)255;
+}
+
 static Workspace carve(void *base, const naf_render_cfg *cfg, uint64_t n_points) {
-    const size_t esz = cfg->mlp_precision == NAF_F32 ? 4 : 2;
-    const size_t feat_bytes = ((size_t)n_points * cfg->L * cfg->C * esz + 255) & ~(size_t)255;
+    const size_t feat_bytes = feature_bytes(cfg, n_points);
     const size_t slab_bytes = (size_t)std::max(kBackwardBlocks, kBackwardBlocks16) * kSlabStride * 4;
     const size_t n_rays_max = (size_t)(n_points / std::max<uint32_t>(cfg->n_samples, 1u)) + 1;
     Workspace w;
@@ -148,20 +154,16 @@ static int run_mlp_forward(const void *feat, const float *mlp, const SrcRays &sr
     if constexpr (std::is_same<P, PrecBF16>::value && C == 2) {
         // (depth buffers of the four waves, which also stage the weights in the prologue: Mlp16Shared::build_staged)
         const uint32_t lds16 = ((Mlp16Shared::kBytes + 15u) & ~15u) + std::max<uint32_t>(4u * kMaxSamplesLds * 4u, Mlp16Shared::kStageFloats * 4u);
-        if (kRays && forward16_splits(n_items, src.S, o.sigma != nullptr || o.depth != nullptr, cfg->flags)) {
-            ProfScope prof_("mlp_forward_kernel", s);
-            hipLaunchKernelGGL(mlp16_forward_split_kernel, dim3(forward16_split_grid(n_items)), dim3(256), lds16, s,
-                               (const uint16_t *)feat, mlp, src, o.out, n_items, B, cfg->last_activation);
-            return check_launch("mlp16_forward_split_kernel");
-        }
-        { ProfScope prof_("mlp_forward_kernel", s); hipLaunchKernelGGL((mlp16_forward_kernel<kRays>), dim3(forward_grid(n_items, kRays, 16u)), dim3(256), lds16, s,
-                           (const uint16_t *)feat, mlp, src, o.out, o.sigma, o.depth, n_items, B, cfg->last_activation, o.omap); }
-        return check_launch("mlp16_forward_kernel");
+        // (every forward instantiation is timed as mlp_forward_kernel, the row bench.py reads; a failed launch names the kernel itself)
+        if (kRays && forward16_splits(n_items, src.S, o.sigma != nullptr || o.depth != nullptr, cfg->flags))
+            return launch_as("mlp_forward_kernel", "mlp16_forward_split_kernel", mlp16_forward_split_kernel, dim3(forward16_split_grid(n_items)), dim3(256), lds16, s,
+                             (const uint16_t *)feat, mlp, src, o.out, n_items, B, cfg->last_activation);
+        return launch_as("mlp_forward_kernel", "mlp16_forward_kernel", mlp16_forward_kernel<kRays>, dim3(forward_grid(n_items, kRays, 16u)), dim3(256), lds16, s,
+                         (const uint16_t *)feat, mlp, src, o.out, o.sigma, o.depth, n_items, B, cfg->last_activation, o.omap);
     }
     // (no `else`: the 32-point kernels stay instantiated for bf16, C = 2 as well, though nothing launches them there)
-    { ProfScope prof_("mlp_forward_kernel", s); hipLaunchKernelGGL((mlp_forward_kernel<P, C, kRays>), dim3(forward_grid(n_items, kRays, 32u)), dim3(256), forward_lds_bytes<P>(), s,
-                       (const typename P::feat_t::store_t *)feat, mlp, src, o.out, o.sigma, o.depth, n_items, B, cfg->last_activation, o.omap); }
-    return check_launch("mlp_forward_kernel");
+    return launch("mlp_forward_kernel", mlp_forward_kernel<P, C, kRays>, dim3(forward_grid(n_items, kRays, 32u)), dim3(256), forward_lds_bytes<P>(), s,
+                  (const typename P::feat_t::store_t *)feat, mlp, src, o.out, o.sigma, o.depth, n_items, B, cfg->last_activation, o.omap);
 }
 
 // ---- MLP backward ---------------------------------------------------------------------------------------------------------------------
@@ -182,18 +184,16 @@ struct MlpBackwardJob {
     uint32_t *gmax_bits; float *grad_mlp, *loss_out; const MlpAdam *madam; StepExtras ex;
 };
 
-// The end of every MLP backward launch: check it, record the event, then reduce its n_slabs slabs (mlp_grad_reduce_kernel) -- or
-// leave the reduction's description where the scatter picks it up (`ex.deferred`).
-static int finish_mlp_backward(const char *kernel, const MlpBackwardJob &j, uint32_t n_slabs, hipStream_t s) {
-    if (int rc = check_launch(kernel)) return rc;
+// The end of every MLP backward launch (`launched`: what it returned): record the event, then reduce its n_slabs slabs
+// (mlp_grad_reduce_kernel) -- or leave the reduction's description where the scatter picks it up (`ex.deferred`).
+static int finish_mlp_backward(int launched, const MlpBackwardJob &j, uint32_t n_slabs, hipStream_t s) {
+    if (launched != NAF_OK) return launched;
     if (j.ex.after_backward != nullptr && hipEventRecord(j.ex.after_backward, s) != hipSuccess) return fail(NAF_ERR_LAUNCH, "mlp backward: cannot record the event");
     const MlpAdam none{nullptr, nullptr, nullptr, AdamArgs{}};
     const SlabReduce sr{j.slabs, n_slabs, j.grad_mlp, j.loss_out, j.loss.target == nullptr ? kLossNone : j.ex.loss_assign ? kLossAssign : kLossAdd,
                         j.madam != nullptr ? *j.madam : none, j.gmax_bits};
     if (j.ex.deferred != nullptr) { *j.ex.deferred = sr; return NAF_OK; }
-    ProfScope prof_("mlp_grad_reduce_kernel", s);
-    hipLaunchKernelGGL(mlp_grad_reduce_kernel, dim3(kSlabReduceBlocks), dim3(kReduceParams * kReduceGroups), 0, s, sr);
-    return check_launch("mlp_grad_reduce_kernel");
+    return launch("mlp_grad_reduce_kernel", mlp_grad_reduce_kernel, dim3(kSlabReduceBlocks), dim3(kReduceParams * kReduceGroups), 0, s, sr);
 }
 
 template <typename P, uint32_t C>
@@ -208,21 +208,22 @@ static int run_mlp_backward(const MlpBackwardJob &j, const SrcRays &src, uint32_
             auto kern = nw == 4u ? mlp16_train_kernel<4u> : mlp16_train_kernel<12u>;
             const uint32_t lds = sh16 + nw * (3u * kImg16 + kMaxSamplesLds * 4u);
             if (int rc = raise_lds_limit(kern, lds, "mlp16_train_kernel: cannot raise dynamic LDS limit")) return rc;
-            { ProfScope prof_("mlp_train_kernel", s); hipLaunchKernelGGL(kern, dim3(mlp_train_grid(n_rays, parts, nw)), dim3(64u * nw), lds, s, (const uint16_t *)j.feat, j.mlp, src,
-                               j.loss, j.ex.acc_out, (uint16_t *)j.dfeat, j.slabs, n_rays, B, cfg->last_activation, parts, n_slabs, j.ex.clear_words); }
-            return finish_mlp_backward("mlp16_train_kernel", j, n_slabs, s);
+            // (the 16-point kernels are timed under the aggregate names bench.py reads, mlp_train_kernel and mlp_backward_kernel)
+            const int rc = launch_as("mlp_train_kernel", "mlp16_train_kernel", kern, dim3(mlp_train_grid(n_rays, parts, nw)), dim3(64u * nw), lds, s, (const uint16_t *)j.feat, j.mlp,
+                                     src, j.loss, j.ex.acc_out, (uint16_t *)j.dfeat, j.slabs, n_rays, B, cfg->last_activation, parts, n_slabs, j.ex.clear_words);
+            return finish_mlp_backward(rc, j, n_slabs, s);
         }
         const uint32_t lds16 = sh16 + std::max<uint32_t>(4u * 3u * 1024u + 4u * kMaxSamplesLds * 4u, (kMlpParams + 2u) * 4u);
-        { ProfScope prof_("mlp_backward_kernel", s); hipLaunchKernelGGL(mlp16_backward_kernel, dim3(n_slabs), dim3(256), lds16, s, (const uint16_t *)j.feat, j.mlp, src,
-                           j.grad_acc, j.loss, (uint16_t *)j.dfeat, j.slabs, n_rays, B, cfg->last_activation, parts, j.ex.clear_words); }
-        return finish_mlp_backward("mlp16_backward_kernel", j, n_slabs, s);
+        const int rc = launch_as("mlp_backward_kernel", "mlp16_backward_kernel", mlp16_backward_kernel, dim3(n_slabs), dim3(256), lds16, s, (const uint16_t *)j.feat, j.mlp, src,
+                                 j.grad_acc, j.loss, (uint16_t *)j.dfeat, j.slabs, n_rays, B, cfg->last_activation, parts, j.ex.clear_words);
+        return finish_mlp_backward(rc, j, n_slabs, s);
     }
     auto kern = mlp_backward_kernel<P, C>;                   // (no `else`: see run_mlp_forward)
     const uint32_t lds = backward_lds_bytes<P>(), n_slabs = backward_slabs(n_rays);
     if (int rc = raise_lds_limit(kern, lds, "mlp_backward_kernel: cannot raise dynamic LDS limit")) return rc;      // fp32 images need > 64 KiB
-    { ProfScope prof_("mlp_backward_kernel", s); hipLaunchKernelGGL(kern, dim3(n_slabs), dim3(256), lds, s, (const typename P::feat_t::store_t *)j.feat, j.mlp, src, j.grad_acc, j.loss,
-                       (typename P::feat_t::store_t *)j.dfeat, j.slabs, n_rays, B, cfg->last_activation, j.ex.clear_words); }
-    return finish_mlp_backward("mlp_backward_kernel", j, n_slabs, s);
+    const int rc = launch("mlp_backward_kernel", kern, dim3(n_slabs), dim3(256), lds, s, (const typename P::feat_t::store_t *)j.feat, j.mlp, src, j.grad_acc, j.loss,
+                          (typename P::feat_t::store_t *)j.dfeat, j.slabs, n_rays, B, cfg->last_activation, j.ex.clear_words);
+    return finish_mlp_backward(rc, j, n_slabs, s);
 }
 
 // ---- table scatter --------------------------------------------------------------------------------------------------------------------
@@ -272,13 +273,13 @@ struct FxRecords {
         return (3u * (1u << plan.log2_nb) + 4u) * 4u + (plan.slots + 1u) * (uint32_t)sizeof(PairFx) + side_list_capacity(plan.slots) * 12u;
     }
     template <typename K>
-    void launch_bin(K bin, dim3 grid, uint32_t threads, uint32_t lds, hipStream_t s, const BinPass &p) const {
+    int launch_bin(const char *timed, K bin, dim3 grid, uint32_t threads, uint32_t lds, hipStream_t s, const BinPass &p) const {
         DrawJob dj{};
         if (next_draw != nullptr && next_draw->count != 0u) { dj = *next_draw; next_draw->count = 0u; }
         grid.x += (dj.count + threads - 1u) / threads;                    // the draw's spare workgroups
         const GradBlocks gb = from_blocks != nullptr ? *from_blocks : GradBlocks{};
-        hipLaunchKernelGGL(bin, grid, dim3(threads), lds, s, src, (const uint16_t *)dfeat, p.offsets, p.grad_table, (PairFx *)p.w.regions,
-                           p.w.counts, p.w.overflow, B, p.H, p.l0, p.nl, p.plan, p.job, dj, gb);
+        return launch_as(timed, "scatter_bin_kernel", bin, grid, dim3(threads), lds, s, src, (const uint16_t *)dfeat, p.offsets, p.grad_table, (PairFx *)p.w.regions,
+                         p.w.counts, p.w.overflow, B, p.H, p.l0, p.nl, p.plan, p.job, dj, gb);
     }
 };
 
@@ -301,31 +302,23 @@ static int run_hash_backward_levels(const ScatterJob &j, uint32_t lv_begin, uint
     const Workspace &w = j.w;
     if (j.from_blocks != nullptr && !(w.binned && scatter_v2(cfg))) return fail(NAF_ERR_LAUNCH, "hash backward: only the 8-byte-record scatter reads gradient blocks in place");
     if (w.binned) {
-        if (scatter_v2(cfg)) {
-            FxRecords fam{j.src, j.dfeat, j.B, j.next_draw, j.from_blocks};
-            return launch_binned_scatter(fam, cfg, w.plan, w.bin, j.offsets, j.grad_table, lv_begin, lv_end, j.buckets, j.s, j.adam, j.slab_job);
-        }
+        auto scatter = [&](auto fam) { return launch_binned_scatter(fam, cfg, w.plan, w.bin, j.offsets, j.grad_table, lv_begin, lv_end, j.buckets, j.s, j.adam, j.slab_job); };
+        if (scatter_v2(cfg)) return scatter(FxRecords{j.src, j.dfeat, j.B, j.next_draw, j.from_blocks});
         // fp32 records in parity mode, bf16 ones packed in pairs otherwise; the features are [L, B, C]: strides (B, 1)
-        if (cfg->mlp_precision == NAF_F32) {
-            PairRecords<FT, C, SrcRays, PairF32<C>, 16u, true> fam{j.src, j.dfeat, j.B, j.B, 1u};
-            return launch_binned_scatter(fam, cfg, w.plan, w.bin, j.offsets, j.grad_table, lv_begin, lv_end, j.buckets, j.s, j.adam, j.slab_job);
-        }
-        PairRecords<FT, C, SrcRays, PairBF16<C>, 16u, true> fam{j.src, j.dfeat, j.B, j.B, 1u};
-        return launch_binned_scatter(fam, cfg, w.plan, w.bin, j.offsets, j.grad_table, lv_begin, lv_end, j.buckets, j.s, j.adam, j.slab_job);
+        if (cfg->mlp_precision == NAF_F32) return scatter(PairRecords<FT, C, SrcRays, PairF32<C>, 16u, true>{j.src, j.dfeat, j.B, j.B, 1u});
+        return scatter(PairRecords<FT, C, SrcRays, PairBF16<C>, 16u, true>{j.src, j.dfeat, j.B, j.B, 1u});
     }
     if (j.adam != nullptr) return fail(NAF_ERR_LAUNCH, "hash backward: the Adam tail needs the binned scatter");
-    if (per_level_launches(cfg)) {
+    const auto kern = hash_backward_kernel<FT, 3, C, SrcRays>;
+    if (per_level_launches(cfg)) {                           // a level's launch is timed under its own name; a failed one ends the loop
         static const char *const names[32] = NAF_LEVEL_NAMES("hash_backward_kernel_L");
-        for (uint32_t l = lv_begin; l < lv_end; ++l) {
-            ProfScope prof_(level_name(names, l), j.s);
-            hipLaunchKernelGGL((hash_backward_kernel<FT, 3, C, SrcRays>), dim3(hash_grid_x(j.B), 1), dim3(256), 0, j.s, j.src,
-                               (const typename FT::store_t *)j.dfeat, j.offsets, j.grad_table, j.B, cfg->L, cfg->H, false, l);
-        }
-        return check_launch("hash_backward_kernel");
+        for (uint32_t l = lv_begin; l < lv_end; ++l)
+            if (int rc = launch_as(level_name(names, l), "hash_backward_kernel", kern, dim3(hash_grid_x(j.B), 1), dim3(256), 0, j.s, j.src,
+                                   (const typename FT::store_t *)j.dfeat, j.offsets, j.grad_table, j.B, cfg->L, cfg->H, false, l)) return rc;
+        return NAF_OK;
     }
-    { ProfScope prof_("hash_backward_kernel", j.s); hipLaunchKernelGGL((hash_backward_kernel<FT, 3, C, SrcRays>), dim3(hash_grid_x(j.B), lv_end - lv_begin), dim3(256), 0, j.s, j.src,
-                       (const typename FT::store_t *)j.dfeat, j.offsets, j.grad_table, j.B, cfg->L, cfg->H, false, lv_begin); }
-    return check_launch("hash_backward_kernel");
+    return launch("hash_backward_kernel", kern, dim3(hash_grid_x(j.B), lv_end - lv_begin), dim3(256), 0, j.s, j.src,
+                  (const typename FT::store_t *)j.dfeat, j.offsets, j.grad_table, j.B, cfg->L, cfg->H, false, lv_begin);
 }
 
 // All levels, in the order of `buckets` when given (data-parallel training: each bucket's event is recorded on the stream as
@@ -356,10 +349,6 @@ static int run_hash_backward(const ScatterJob &j) {
 static bool forward_fused(const naf_render_cfg *cfg) {
     return (cfg->flags & NAF_CFG_FORWARD_FUSED) != 0u && cfg->mlp_precision == NAF_BF16 && cfg->C == 2u && cfg->L == kFusedLevels;
 }
-static size_t feature_bytes(const naf_render_cfg *cfg, uint64_t n_points) {
-    const size_t esz = cfg->mlp_precision == NAF_F32 ? 4 : 2;
-    return ((size_t)n_points * cfg->L * cfg->C * esz + 255) & ~(size_t)255;
-}
 static size_t forward_workspace_bytes(const naf_render_cfg *cfg, uint64_t n_points) {
     if (forward_fused(cfg) && (cfg->flags & NAF_CFG_FUSED_STORE_FEATURES) == 0u) return 256;
     return feature_bytes(cfg, n_points) + 256;
@@ -371,9 +360,8 @@ static int launch_fused_forward(const Src &src, const Field &f, const ForwardOut
     constexpr bool kRays = std::is_same<Src, SrcRays>::value;
     const uint32_t lds = ((Mlp16Shared::kBytes + 15u) & ~15u) + kFusedLevels * (uint32_t)sizeof(LevelRec) + (kRays ? 4u * kMaxSamplesLds * 4u : 0u);
     uint16_t *fout = (cfg->flags & NAF_CFG_FUSED_STORE_FEATURES) != 0u ? (uint16_t *)feat : nullptr;
-    { ProfScope prof_("fused_forward_kernel", s); hipLaunchKernelGGL((fused_forward_kernel<TT, Src>), dim3(forward_grid(n_items, kRays, 16u)), dim3(256), lds, s, src,
-                       (const typename TT::store_t *)f.emb, f.offsets, f.mlp, o.out, o.sigma, o.depth, fout, n_items, B, cfg->H, cfg->last_activation, o.omap); }
-    return check_launch("fused_forward_kernel");
+    return launch("fused_forward_kernel", fused_forward_kernel<TT, Src>, dim3(forward_grid(n_items, kRays, 16u)), dim3(256), lds, s, src,
+                  (const typename TT::store_t *)f.emb, f.offsets, f.mlp, o.out, o.sigma, o.depth, fout, n_items, B, cfg->H, cfg->last_activation, o.omap);
 }
 template <typename Src>
 static int run_fused_forward(const Src &src, const Field &f, const ForwardOut &o, void *feat, uint32_t n_items, uint32_t B, const naf_render_cfg *cfg,
@@ -521,12 +509,9 @@ static int levels_scatter_impl(const RayBatch &b, const LevelBlocks &in, const i
     const uint32_t units = vec ? run / (uint32_t)(16u / sizeof(T)) : run;
     // ~512 workgroups in all: each ends with ONE atomic on the same word, and same-address atomics retire ~12 ns apart
     const uint32_t gx = std::max<uint32_t>(1u, std::min<uint32_t>((units + 1023u) / 1024u, std::max<uint32_t>(1u, 512u / (n_ranks * nl))));
-    {
-        ProfScope prof_("levels_gather_kernel", s);
-        auto kern = vec ? levels_gather_kernel<T, true> : levels_gather_kernel<T, false>;
-        hipLaunchKernelGGL(kern, dim3(gx, n_ranks * nl), dim3(256), 0, s, (const unsigned char *)in.blocks, in.stride, (T *)w.dfeat, n_ranks, nl, run, lv_begin, gmax);
-    }
-    if (int rc = check_launch("levels_gather_kernel")) return rc;
+    auto kern = vec ? levels_gather_kernel<T, true> : levels_gather_kernel<T, false>;
+    if (int rc = launch("levels_gather_kernel", kern, dim3(gx, n_ranks * nl), dim3(256), 0, s, (const unsigned char *)in.blocks, in.stride, (T *)w.dfeat, n_ranks, nl, run,
+                        lv_begin, gmax)) return rc;
     return run_hash_backward_levels<P, C>(sj, lv_begin, lv_end);
 }
 

@@ -113,7 +113,7 @@ struct BinPass {
 //   kLvMany, kLvFew               levels per bin workgroup when tiles are plentiful / scarce
 //   bin_kernel(plan, big, many)   the pass-1 instantiation; reduce_kernel(adam): the pass-2 one
 //   bin_lds(plan)                 pass 1's dynamic LDS bytes
-//   launch_bin(k, grid, threads, lds, s, pass)   a pass-1 launch, with the family's own arguments
+//   launch_bin(timed, k, grid, threads, lds, s, pass)   a pass-1 launch timed as `timed`, with the family's own arguments; launch_as()'s result
 // `slab_job` (training steps): the deferred slab reduction, run by spare workgroups of the first pass-1 launch (StepExtras).
 // `buckets` (data parallel): each bucket's event is recorded as soon as its rows are final.
 template <typename F>
@@ -142,23 +142,22 @@ static int launch_binned_scatter(F &fam, const naf_render_cfg *cfg, const BinPla
     SlabReduce job{};
     if (slab_job != nullptr) job = *slab_job;
     // pass 1 over the levels [l0, l0 + nl): their records fill the region buffer from level slot 0
+    // (both passes are timed under a level's own name on the per-level diagnostic path; a failed launch names the kernel)
     auto launch_bin = [&](uint32_t l0, uint32_t nl) -> int {
-        ProfScope prof_(per_level ? level_name(bin_names, l0) : "scatter_bin_kernel", s);
         const uint32_t spare = job.slabs != nullptr ? kSlabReduceBlocks : 0u;
-        fam.launch_bin(bin, dim3(plan.n_tiles + spare, (nl + LV - 1u) / LV), threads, bin_lds, s, BinPass{offsets, grad_table, w, cfg->H, l0, nl, plan, job});
+        const int rc = fam.launch_bin(per_level ? level_name(bin_names, l0) : "scatter_bin_kernel", bin, dim3(plan.n_tiles + spare, (nl + LV - 1u) / LV), threads, bin_lds, s,
+                                      BinPass{offsets, grad_table, w, cfg->H, l0, nl, plan, job});
         job = SlabReduce{};
-        return check_launch("scatter_bin_kernel");
+        return rc;
     };
     // pass 2 over the level slots [ly0, ly0 + nl) of a bin pass that started at level l0
     auto launch_reduce = [&](uint32_t l0, uint32_t ly0, uint32_t nl) -> int {
-        ProfScope prof_(per_level ? level_name(red_names, l0 + ly0) : "scatter_reduce_kernel", s);
         // keep >= ~1024 reducer workgroups in flight: with one or two levels per pass split each bucket's tiles.
         // (A reducer workgroup owns a CU's LDS, so 256 run at a time: 512 or more unsplit ones already come in full rounds.)
         const uint32_t n_split = reducer_split(NB, nl);
         if (adam != nullptr && n_split != 1u) return fail(NAF_ERR_LAUNCH, "binned scatter: the Adam tail needs unsplit reducer launches");
-        hipLaunchKernelGGL(red, dim3(NB, nl, n_split), dim3(1024), red_lds, s, (const typename F::Rec *)w.regions, w.counts, offsets,
-                           grad_table, w.gmax, l0, ly0, cfg->H, plan, tail);
-        return check_launch("scatter_reduce_kernel");
+        return launch_as(per_level ? level_name(red_names, l0 + ly0) : "scatter_reduce_kernel", "scatter_reduce_kernel", red, dim3(NB, nl, n_split), dim3(1024), red_lds, s,
+                         (const typename F::Rec *)w.regions, w.counts, offsets, grad_table, w.gmax, l0, ly0, cfg->H, plan, tail);
     };
     if (buckets != nullptr && !per_level && plan.levels_per_pass >= cfg->L && lv_begin == 0u && lv_end == cfg->L) {
         // data parallel, and the records of all levels fit one pass: bin ONCE (the sample position is evaluated once per
@@ -211,9 +210,9 @@ struct PairRecords {
     }
     uint32_t bin_lds(const BinPlan &plan) const { return (2u * (1u << plan.log2_nb) + 4u) * 4u + plan.slots * (uint32_t)sizeof(Rec); }
     template <typename K>
-    void launch_bin(K bin, dim3 grid, uint32_t threads, uint32_t lds, hipStream_t s, const BinPass &p) const {
-        hipLaunchKernelGGL(bin, grid, dim3(threads), lds, s, src, (const typename FT::store_t *)grad, p.offsets, p.grad_table, (Rec *)p.w.regions,
-                           p.w.counts, p.w.overflow, B, p.H, p.l0, p.nl, p.plan, p.job, sl, sb);
+    int launch_bin(const char *timed, K bin, dim3 grid, uint32_t threads, uint32_t lds, hipStream_t s, const BinPass &p) const {
+        return launch_as(timed, "scatter_bin_kernel", bin, grid, dim3(threads), lds, s, src, (const typename FT::store_t *)grad, p.offsets, p.grad_table, (Rec *)p.w.regions,
+                         p.w.counts, p.w.overflow, B, p.H, p.l0, p.nl, p.plan, p.job, sl, sb);
     }
 };
 
