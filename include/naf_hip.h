@@ -909,6 +909,37 @@ int naf_stripe_remove_sorting(const float *p, uint32_t N, uint32_t H, uint32_t W
 int naf_frames_condition(const void *raw, int raw_dtype, const float *dark, const float *flat, const uint8_t *bad, uint32_t N, uint32_t H,
                          uint32_t W, uint32_t size, float dif, float t_min, uint32_t flags, float *out, uint32_t *counts, void *stream);
 
+/* A4  sinogram in-painting for metal artefact reduction: the pixels of a metal trace replaced, in every detector row of every view, by
+ * linear interpolation between their nearest valid neighbours (LI-MAR, Kalender et al. 1987), optionally on the sinogram divided by
+ * a prior's (NMAR, Meyer et al. 2010), in one launch (metal.py).  DESIGN.md section 32; the bitmap search and the per-pixel
+ * arithmetic are csrc/inpaint_device.h.
+ *   p, out  f32 [N, H, W] C-contiguous: N views, H detector rows (v), W detector columns (u)
+ *   mask    u8 [N, H, W]: non-zero marks a pixel of the trace
+ *   prior   f32 [N, H, W] or NULL: the forward projection of a prior volume;  eps  f32 > 0, finite (read only with a prior)
+ *   counts  u32 [N, 2] (+=) or NULL
+ * Per view i, row v and column u, every operation one IEEE fp32 operation in the order written, the divisions correctly rounded:
+ *   1. g[u] = prior ? fmaxf(prior[i,v,u], eps) : 1,   q[u] = prior ? p[i,v,u] / g[u] : p[i,v,u]
+ *   2. a pixel that is not masked: out gets the bits of p
+ *   3. a masked pixel: L is the largest column below u of the same row and view that is not masked, R the smallest above u.
+ *        both exist:    w = (float)(u - L) / (float)(R - L),  d = q[R] - q[L],  val = q[L] + w d
+ *        only L (or R): val = q[L] (or q[R])
+ *        out = prior ? val g[u] : val
+ *        neither (the whole row is masked): out gets the bits of p
+ *   4. counts[i, 0] += the pixels of view i that were replaced, counts[i, 1] += the masked pixels left as they were: summed within a
+ *      workgroup and added with one integer atomic each, so equal inputs give equal counts.  The caller zeroes them.
+ * Non-finite values are not special: they propagate as the arithmetic says.  Every output is a pure function of the inputs: equal
+ * inputs give equal bits, the bits of a float32 numpy restatement (tests/_inpaint_oracle.py).
+ * `out` may be p itself: a pixel that is not masked is only ever re-stored with its own bits, and a masked pixel is never read as a
+ * neighbour (L and R are not masked, and q is read at L, R and u only), so no lane reads what another lane stores.  In place the
+ * kernel skips the stores of the pixels it does not replace.  Any other overlap of `out` with p, mask or prior is refused.
+ * Refused before any launch (NAF_ERR_INVALID_ARGUMENT): a null p, mask or out; W above NAF_INPAINT_MAX_W (the row's bitmap is held in
+ * LDS); H above 2^24; N H above 2^31 - 1 (one workgroup per row); p, prior, out or counts not 4-byte aligned; a partial overlap; with a
+ * prior, eps not finite or not above zero.  N H W == 0 returns NAF_OK without examining anything else.  Element offsets are 64-bit.
+ * The call takes the stream, allocates nothing and never synchronises. */
+#define NAF_INPAINT_MAX_W 16384u
+int naf_inpaint_rows(const float *p, const uint8_t *mask, const float *prior, float eps, uint32_t N, uint32_t H, uint32_t W, float *out,
+                     uint32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

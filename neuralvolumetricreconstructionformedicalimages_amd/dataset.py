@@ -172,10 +172,13 @@ class TIGREDataset(Dataset):
 
 
 def synthetic_scan(n_voxel=64, n_train=50, n_val=8, mode="cone", tilt_angle=0, seed=0, device="cpu", full_proj=False,
-                   geometry=None, train_angles=None):
+                   geometry=None, train_angles=None, metal=None, p_max=None):
     """A complete in-memory scan with the pickle schema, from the analytic phantom (no data ships with the reference).
     Train angles: linspace(0, pi, n+1)[:-1] (generateData.py:175) unless `train_angles` (radians) is given; val angles:
-    sorted U(0, pi) with seed 1.  `geometry` overrides the default scanner dict (e.g. the 256 x 356 laminography detector)."""
+    sorted U(0, pi) with seed 1.  `geometry` overrides the default scanner dict (e.g. the 256 x 356 laminography detector).
+    `metal=(count, radius, rho)` plants that many metal spheres in the phantom (`add_metal`, drawn with `seed`; radius in metres)
+    and `p_max` ends the detector's dynamic range there (`saturate`); both are stored as `data["metal"]`.  Without them the scan
+    is what it has always been."""
     from . import phantom
     from .geometry import angle2pose  # noqa: F401  (documented dependency)
 
@@ -188,6 +191,9 @@ def synthetic_scan(n_voxel=64, n_train=50, n_val=8, mode="cone", tilt_angle=0, s
     if tilt_angle:                                       # flat sample for laminography
         table["c"][:, 2] *= 0.3
         table["a"][:, 2] *= 0.3
+    if metal is not None:
+        count, radius, rho = metal
+        table = add_metal(table, count, radius, rho, seed)
     rng = np.random.RandomState(1)
     splits = {"train": np.linspace(0, np.pi, n_train + 1)[:-1] if train_angles is None else np.asarray(train_angles, dtype=np.float64),
               "val": np.sort(rng.uniform(0, np.pi, n_val))}
@@ -199,7 +205,11 @@ def synthetic_scan(n_voxel=64, n_train=50, n_val=8, mode="cone", tilt_angle=0, s
             projs = torch.stack([phantom.line_integrals(gen.rays_for_projection(i), table).reshape(H, W) for i in range(len(angles))])
         else:                                             # CPU construction for tests: the oracle-free torch formula
             projs = torch.stack([phantom.line_integrals(_rays_cpu(geo, a), table).reshape(H, W) for a in angles])
+        if p_max is not None:
+            projs = saturate(projs.cpu(), p_max)
         data[name] = {"angles": angles, "projections": projs.cpu().numpy()}
+    if metal is not None or p_max is not None:
+        data["metal"] = {"spheres": None if metal is None else tuple(metal), "p_max": p_max, "seed": seed}
     data["numTrain"], data["numVal"] = n_train, n_val
     data["image"] = phantom.volume(geo, table, device=dev).cpu().numpy()
     if full_proj:
@@ -303,6 +313,40 @@ def add_stripes(projs, fraction, sigma, generator):
     gain = np.where(defective, np.maximum(1.0 + float(sigma) * rng.standard_normal(p.shape[1:]), 0.1), 1.0)
     out = (-np.log(np.exp(-p) * gain[None])).astype(np.float32)
     return torch.from_numpy(out) if as_tensor else out
+
+
+def add_metal(table, count, radius, rho, generator):
+    """A copy of a `phantom.ellipsoid_table` with `count` spheres of radius `radius` (metres) and density `rho` appended: fillings
+    or implants.  Their centres are drawn uniformly in the body ellipsoid (the table's first row) shrunk by `radius`, so every sphere
+    lies inside the body.  `generator` is a numpy Generator or an int seed for one; equal seeds give equal bits.  Host side; `table`
+    is left as it is.  The metal alone is the last `count` rows of the result."""
+    count, radius, rho = int(count), float(radius), float(rho)
+    room = np.asarray(table["a"][0], dtype=np.float64) - radius
+    if count < 1 or not radius > 0.0 or not rho > 0.0 or not room.min() > 0.0:
+        raise ValueError(f"add_metal: count must be >= 1, rho above zero and radius above zero and below the body's semi-axes "
+                         f"{tuple(table['a'][0])}, got {count}, {radius}, {rho}")
+    rng = generator if isinstance(generator, np.random.Generator) else np.random.default_rng(generator)
+    direction = rng.standard_normal((count, 3))
+    direction /= np.linalg.norm(direction, axis=1, keepdims=True)
+    inside = direction * np.cbrt(rng.random((count, 1))) * room[None]                     # uniform in the shrunk ellipsoid's own frame
+    body_R = np.asarray(table["R"][0], dtype=np.float64)                                   # world -> frame, so its transpose leads back
+    centres = np.asarray(table["c"][0], dtype=np.float64)[None] + inside @ body_R
+    return {"c": np.concatenate([np.asarray(table["c"], dtype=np.float64), centres]),
+            "a": np.concatenate([np.asarray(table["a"], dtype=np.float64), np.full((count, 3), radius)]),
+            "R": np.concatenate([np.asarray(table["R"], dtype=np.float64), np.broadcast_to(np.eye(3), (count, 3, 3))]),
+            "rho": np.concatenate([np.asarray(table["rho"], dtype=np.float64), np.full(count, rho)])}
+
+
+def saturate(projs, p_max):
+    """min(p, p_max) on line integrals `projs` (numpy array or tensor): the end of the detector's dynamic range, below which no
+    count is told from none.  A linear, monochromatic metal is consistent data and draws no streaks; a trace that is cut off does.
+    Returns float32 of the kind given; `projs` is left as it is."""
+    p_max = float(p_max)
+    if not p_max > 0.0 or not np.isfinite(p_max):
+        raise ValueError(f"saturate: p_max must be finite and above zero, got {p_max}")
+    if isinstance(projs, torch.Tensor):
+        return projs.float().clamp(max=p_max)
+    return np.minimum(np.asarray(projs, dtype=np.float32), np.float32(p_max))
 
 
 def _host_array(a, who, name, ndim):

@@ -108,6 +108,9 @@ pass) and takes w_i = gap_i, for scans of pi .. 2 pi.  A 
 
 The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
 arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart`, `fista_tv` and `cgls`, are HIP kernels.
+
+`reduce_metal` / `reduce_metal_operators` are no solver but a repair of the projections in front of one: the trace of the metal
+voxels of a first reconstruction is in-painted along the detector rows (`metal.inpaint_rows`).
 """
 from __future__ import annotations
 
@@ -819,3 +822,88 @@ def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call
 
     _, AT = _scan_operators(geo, angles, views_per_call, deterministic, projections.device)
     return fdk_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=nonneg, short_scan=short_scan)
+
+
+METAL_METHODS = ("li", "nmar")
+NMAR_EPS_FRACTION = 1e-3                # eps of the normalised in-painting, as a fraction of the prior sinogram's maximum
+
+
+def _check_metal(method, air, bone, grow):
+    if method not in METAL_METHODS:
+        raise ValueError(f"reduce_metal: method must be one of {METAL_METHODS}, got {method!r}")
+    if method == "nmar":
+        if air is None or bone is None:
+            raise ValueError("reduce_metal: method 'nmar' needs air and bone, the thresholds of its prior")
+        if not float(air) < float(bone):
+            raise ValueError(f"reduce_metal: air must be below bone, got {air} and {bone}")
+    if isinstance(grow, bool) or not isinstance(grow, int) or grow < 0:
+        raise ValueError(f"reduce_metal: grow must be an int >= 0, got {grow!r}")
+
+
+def reduce_metal_operators(A, inpaint, dilate, b, initial, threshold, method="li", air=None, bone=None, grow=1):
+    """Metal artefact reduction by sinogram in-painting (metal.py) as array code over callables, on arrays of
+    `b`'s kind ([N, H, W]; torch tensors on any device, numpy arrays).
+
+        A(x)                         volume -> projections [N, H, W], float32
+        inpaint(b, mask, prior, eps) -> (b with the masked pixels in-painted along their rows, counts [N, 2]); prior and eps are
+                                     None for `method="li"`
+        dilate(mask, grow)           a mask [N, H, W] grown by `grow` pixels along both detector axes -> uint8
+
+        metal = initial > threshold                               the metal voxels of a first reconstruction
+        trace = dilate(A(metal as float32) > 0, grow)             the pixels whose ray meets one
+        "nmar":  prior = A(metal.prior_volume(initial, metal, air, bone));   eps = 1e-3 max(prior)
+        corrected, counts = inpaint(b, trace, prior, eps)
+
+    Returns (corrected, info) with info = {"metal": bool volume, "trace": uint8 [N, H, W], "counts": [N, 2], "initial": initial,
+    "prior": the prior sinogram or None, "eps": eps or None}.  A prior sinogram with no positive value (air and bone leave nothing)
+    is refused: it would normalise by eps everywhere."""
+    from .metal import prior_volume
+    _check_metal(method, air, bone, grow)
+    xp, _ = _namespace(b)
+    metal = initial > threshold
+    trace = dilate(A(metal.float() if xp.__name__ == "torch" else metal.astype(xp.float32)) > 0, grow)
+    prior, eps = None, None
+    if method == "nmar":
+        prior = A(prior_volume(initial, metal, air, bone))
+        eps = NMAR_EPS_FRACTION * float(prior.max())
+        if not eps > 0.0 or not math.isfinite(eps):
+            raise ValueError(f"reduce_metal: the prior's sinogram has no finite positive maximum ({eps / NMAR_EPS_FRACTION}): nothing "
+                             "of the first reconstruction lies at or above `air`")
+    corrected, counts = inpaint(b, trace, prior, eps)
+    return corrected, {"metal": metal, "trace": trace, "counts": counts, "initial": initial, "prior": prior, "eps": eps}
+
+
+def reduce_metal(projections, geo, angles, threshold, method="li", air=None, bone=None, grow=1, initial=None, kind="interpolated",
+                 views_per_call=None):
+    """Metal artefact reduction of `projections` [N, H, W] (float32, on the GPU) taken with `geo` at `angles` -> (corrected [N, H, W],
+    info): the iteration of `reduce_metal_operators` over `projector.project_scan` (of `kind`), `metal.inpaint_rows` and
+    `metal.dilate`.  `method="li"` interpolates the sinogram itself, `"nmar"` the sinogram normalised by that of a prior volume with
+    the thresholds `air` and `bone` (required then).  `threshold` separates metal in the first reconstruction `initial`
+    (float32, geo.nVoxel, on the GPU); `initial=None` takes `fdk(projections, geo, angles)`, so a tilted scan is refused where `fdk`
+    refuses it: pass a SIRT or CGLS volume as `initial` there.  `grow` widens the trace by that many detector pixels.  `projections`
+    is left as it is."""
+    import torch
+
+    from . import _abi, metal, projector
+    who = "reduce_metal"
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError(f"{who}: projections must be a CUDA/HIP tensor (no CPU path)")
+    _check_metal(method, air, bone, grow)
+    projector.check_kind(kind, who)
+    scan = projector.Scan(geo, angles, projections.device)
+    shape = (scan.N, scan.H, scan.W)
+    if projections.dtype != torch.float32 or tuple(projections.shape) != shape or not projections.is_contiguous():
+        raise ValueError(f"{who}: projections must be contiguous float32 {shape}, got {projections.dtype} {tuple(projections.shape)}")
+    if initial is None:
+        initial = fdk(projections, geo, angles, views_per_call=views_per_call)
+    else:
+        _abi.check_volume(initial, who, "initial")
+        projector.check_geometry(initial, geo)
+
+    def A(x):
+        return projector.project_scan(x.contiguous(), geo, angles, views_per_call=views_per_call, kind=kind, scan=scan)
+
+    def inpaint(b, mask, prior, eps):
+        return metal.inpaint_rows(b, mask, prior=prior, eps=eps, counts=True)
+
+    return reduce_metal_operators(A, inpaint, metal.dilate, projections, initial, threshold, method=method, air=air, bone=bone, grow=grow)
