@@ -575,8 +575,8 @@ int naf_backproject_scan_gather(const float *values, const uint32_t *view_index,
  *   [-h_a + i_a * dvoxel_a, -h_a + (i_a + 1) * dvoxel_a] per axis,  h_a = fp32(n_a * dvoxel_a / 2) as in P1,
  * the value is volume[i, j, k] inside it and zero outside the volume.  volume, dvoxel, dims, rays, poses and the detector `det`
  * are P1's; there is no sample step (TIGRE's geo.accuracy plays no part).
- * A ray (o, d, near, far) is clipped exactly as P1 clips it: the same float32 slab test intersected with [near, far] in the same
- * order, p0 = fma(t0, d, o), s_end = t1 - t0.  The result is
+ * A ray (o, d, near, far) is clipped by the function that clips P1's (clip_ray of csrc/voxel_grid.h): the float32 slab test
+ * intersected with [near, far], p0 = fma(t0, d, o), s_end = t1 - t0.  The result is
  *     sum over voxels of  volume[voxel] * (length of the clipped segment inside that voxel):  exact chord lengths.
  *   an empty span returns 0;  a non-finite p0 or s_end returns NaN;  a ray lying exactly in a voxel plane has measure zero and is
  *   attributed to one of the two neighbours (the upper one; the last voxel on the face +h_a).
@@ -780,7 +780,7 @@ int naf_cgls_direction_step(float *x, float *p, const float *s, uint64_t n, uint
  *           get_voxels grid (tigre.py:388-400), the box |p_a| <= h_a = fp32(n_a * dvoxel[a] / 2) centred at the origin, as in P1
  *   dvoxel  HOST f32 [3] voxel size in metres (> 0, finite);  dims  HOST u32 [3] = n1, n2, n3
  * Value at p: trilinear between voxel centres, clamp-to-edge EVERYWHERE (a point outside the box returns the value of the nearest
- * point of the centre hull; P1 returns zero there because it never samples outside).  The cell is P1's and P2's:
+ * point of the centre hull; P1 returns zero there because it never samples outside).  The cell is P1's and P2's (voxel_cell of csrc/voxel_grid.h):
  *   u_a = (p_a + h_a) * fp32(1 / dvoxel_a) - 1/2, one add, one multiply, one subtract; clamped on the float to [0, n_a - 1];
  *   i_a = min(floor(u_a), n_a - 2), w_a = u_a - i_a (exact); an axis of one voxel is constant: its w_a is 0, it has no upper corner.
  * The eight corners are blended by seven interpolations fma(w, b, fma(-w, a, a)), axis 2 first, then axis 1, then axis 0.  A weight

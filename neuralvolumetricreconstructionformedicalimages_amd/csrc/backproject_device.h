@@ -10,7 +10,7 @@ namespace naf {
 // Adds scale * acc[c] to the eight corners of the cell at `q`; corners that got no weight (a constant axis, a sample on a voxel
 // centre) are skipped.  Corner c = 4 cx + 2 cy + cz.
 __device__ __forceinline__ void flush_cell(float *__restrict__ q, const ProjVolume &v, float scale, const float acc[8]) {
-    const uint64_t sx = v.next[0], sy = v.next[1], sz = v.next[2];
+    const uint64_t sx = v.grid.next[0], sy = v.grid.next[1], sz = v.grid.next[2];
     const uint64_t off[8] = {0, sz, sy, sy + sz, sx, sx + sz, sx + sy, sx + sy + sz};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -51,7 +51,7 @@ __device__ __forceinline__ void scatter_ray(const ProjVolume &v, float4 a, float
     for (uint32_t k = 0; k < s.n; ++k) {
         float p[3], w[3];
         span_point(s, k, p);
-        const uint64_t base = trilinear_cell(v, p[0], p[1], p[2], w);
+        const uint64_t base = trilinear_cell(v, p, w);
 #ifdef NAF_BACKPROJECT_PER_SAMPLE
         const bool moved = true;
 #else

@@ -75,7 +75,7 @@ gather_spans_kernel(ProjVolume v, const float *__restrict__ poses, RayGeo g, Gat
 // blockIdx.x = (bx * bricks_y + by) * blocks_z + bz: voxels [4 bx, 4 bx + 4) x [4 by, 4 by + 4) x [16 bz, 16 bz + 16).
 template <bool kTable, bool kDen>
 __global__ void __launch_bounds__(256)
-backproject_gather_kernel(ProjVolume v, GatherGrid grid, float *__restrict__ num, float *__restrict__ den,
+backproject_gather_kernel(ProjVolume v, float *__restrict__ num, float *__restrict__ den,
                           const float *__restrict__ values, const float *__restrict__ poses, RayGeo g, GatherViews list,
                           const GatherSpan *__restrict__ spans, uint32_t bricks_y, uint32_t blocks_z) {
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -84,10 +84,10 @@ backproject_gather_kernel(ProjVolume v, GatherGrid grid, float *__restrict__ num
     b /= blocks_z;
     const uint32_t by = b % bricks_y, bx = b / bricks_y;
     const uint32_t i[3] = {bx * 4u + (lane >> 4), by * 4u + ((lane >> 2) & 3u), (bz * 4u + wave) * 4u + (lane & 3u)};
-    if (i[0] >= v.n[0] || i[1] >= v.n[1] || i[2] >= v.n[2]) return;
-    const uint64_t voxel = (uint64_t)i[0] * v.stride[0] + (uint64_t)i[1] * v.stride[1] + i[2];
+    if (i[0] >= v.grid.n[0] || i[1] >= v.grid.n[1] || i[2] >= v.grid.n[2]) return;
+    const uint64_t voxel = (uint64_t)i[0] * v.grid.stride[0] + (uint64_t)i[1] * v.grid.stride[1] + i[2];
     float lo[3], hi[3];
-    gather_support(grid, i, lo, hi);
+    gather_support(v.grid, i, lo, hi);
     const GatherDetector det{g.W, g.H, g.du, g.dv, g.ou, g.ov, g.DSD, g.parallel};
     const uint64_t per_view = (uint64_t)g.W * g.H;
     float acc = num[voxel], dacc = kDen ? den[voxel] : 0.0f;
@@ -124,8 +124,8 @@ backproject_gather_kernel(ProjVolume v, GatherGrid grid, float *__restrict__ num
                 for (uint32_t k = k_lo; k <= k_hi; ++k) {
                     float p[3], w[3];
                     span_point(span, k, p);
-                    const uint64_t cell = trilinear_cell(v, p[0], p[1], p[2], w);
-                    sw += gather_corner_weight(voxel, cell, v.next, w);
+                    const uint64_t cell = trilinear_cell(v, p, w);
+                    sw += gather_corner_weight(voxel, cell, v.grid.next, w);
                 }
                 if (sw == 0.0f) continue;
                 s_num += (values[(uint64_t)(list.first + j) * per_view + pixel] * s.weight) * sw;
@@ -167,12 +167,6 @@ extern "C" int naf_backproject_scan_gather(const float *values, const uint32_t *
     else if (!aligned(workspace, 7u)) what = "workspace must be 8-byte aligned";
     else if (workspace && workspace_bytes < per_view * NAF_GATHER_SPAN_BYTES) what = "workspace too small for the spans of one view";
     if (what) return fail_who(who, what);
-    GatherGrid grid;
-    for (int a = 0; a < 3; ++a) {
-        grid.n[a] = v.n[a];
-        grid.half[a] = v.half[a];
-        grid.d[a] = dvoxel[a];
-    }
     GatherSpan *spans = static_cast<GatherSpan *>(workspace);
     // With a table the views go in groups that fit the workspace, each group a pre-pass and a gather; a voxel adds its views in
     // launch order either way, so the grouping does not change a bit.
@@ -189,7 +183,7 @@ extern "C" int naf_backproject_scan_gather(const float *values, const uint32_t *
         }
         auto kernel = workspace ? (den ? backproject_gather_kernel<true, true> : backproject_gather_kernel<true, false>)
                                 : (den ? backproject_gather_kernel<false, true> : backproject_gather_kernel<false, false>);
-        const int rk = launch("backproject_gather_kernel", kernel, grid_dim, dim3(256), 0, (hipStream_t)stream, v, grid, volume, den, values,
+        const int rk = launch("backproject_gather_kernel", kernel, grid_dim, dim3(256), 0, (hipStream_t)stream, v, volume, den, values,
                               poses, g, list, (const GatherSpan *)spans, (uint32_t)bricks_y, (uint32_t)blocks_z);
         if (rk != NAF_OK) return rk;
     }

@@ -3,22 +3,16 @@
 // a sample's trilinear cell gives the voxel.  The weights themselves come from project_device.h (ray_span, span_point,
 // trilinear_cell), the code the forward projector and the scatter run; this header only decides where to look, so all it has to be
 // is a SUPERSET of the (ray, sample) pairs to which the scatter gives the voxel a non-zero weight.
-// It includes nothing of HIP, so a host compiler reads it too: tools/gather_host_check.cpp runs these very functions on the CPU
-// under AddressSanitizer / UBSan against a float64 enumeration.
+// The grid is voxel_grid.h's VoxelGrid, the one the scatter's ProjVolume holds.  It includes nothing of HIP, so a host compiler reads
+// it too: tools/gather_host_check.cpp runs these very functions on the CPU under AddressSanitizer / UBSan against a float64 enumeration.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
 
-#include "host_device.h"
+#include "voxel_grid.h"
 
 namespace naf {
-
-struct GatherGrid {
-    uint32_t n[3];
-    float half[3];                   // ProjVolume's: fp32(n_a * dvoxel_a / 2)
-    float d[3];                      // dvoxel
-};
 
 struct GatherDetector {              // the fields of RayGeo that place a pixel
     uint32_t W, H;
@@ -39,7 +33,7 @@ constexpr float kGatherEps = 1.0f / 524288.0f;
 // u_a = (p_a + h_a) / d_a - 1/2 lies in (i_a - 1, i_a + 1), that is p_a in (c_a - d_a, c_a + d_a) around the voxel centre c_a.
 // Clamp-to-edge gives an edge voxel the whole outer half cell, so the box reaches the volume's face there (an axis of one voxel: both
 // faces).  Widened by kGatherEps (h_a + d_a): the fp32 error of c_a, of the kernel's u_a and of the sample position.
-NAF_HD void gather_support(const GatherGrid &g, const uint32_t i[3], float lo[3], float hi[3]) {
+NAF_HD void gather_support(const VoxelGrid &g, const uint32_t i[3], float lo[3], float hi[3]) {
     for (int a = 0; a < 3; ++a) {
         const float m = kGatherEps * (g.half[a] + g.d[a]);
         const float below = ((float)i[a] - 0.5f) * g.d[a] - g.half[a], above = ((float)i[a] + 1.5f) * g.d[a] - g.half[a];

@@ -9,6 +9,8 @@
 
 #include <type_traits>
 
+#include "mix32.h"
+
 namespace naf {
 
 constexpr uint32_t kPrime1 = 19349663u;
@@ -360,12 +362,6 @@ __device__ __forceinline__ float dpp_row_shr(float v) { return __uint_as_float(d
 // ---- counter-based jitter (used when the caller passes no t_rand) --------------------------------
 // Two rounds of the "lowbias32" integer finaliser over (seed, global ray index, sample); 24 bits -> [0,1).
 // 32-bit only on purpose: it is re-evaluated by every kernel that needs the sample position.
-__device__ __host__ __forceinline__ uint32_t mix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x7feb352du;
-    h ^= h >> 15; h *= 0x846ca68bu;
-    h ^= h >> 16;
-    return h;
-}
 __device__ __host__ __forceinline__ float jitter(uint64_t seed, uint32_t ray, uint32_t sample) {
     uint32_t h = mix32((uint32_t)seed ^ (ray * 0x9e3779b1u));
     h = mix32(h ^ (uint32_t)(seed >> 32) ^ (sample * 0x85ebca77u) ^ 0x27d4eb2fu);

@@ -1,41 +1,27 @@
 // project_device.h -- the pieces of the projection definition (include/naf_hip.h P1) that the forward
 // projector, its transpose (both projector.hip) and the OS-SART subset kernels (sart.hip) must share to the bit: the
-// volume's grid, the clipped segment of a ray with its sample count, the sample positions, the trilinear cell with its three
-// weights, and the forward's sum over the samples.
+// volume, the clipped segment of a ray with its sample count, the sample positions, and the forward's sum over the samples.  The
+// grid, the clip itself and the trilinear cell are voxel_grid.h's, which the Siddon pair and the volume sampler read too.
 #pragma once
 
 #include <cmath>
 #include <cstdio>
 
 #include "naf_host.h"
+#include "voxel_grid.h"
 
 namespace naf {
 
 struct ProjVolume {
     const float *__restrict__ data;  // [n1, n2, n3] fp32, axis 0 = x, C-contiguous (the forward's input; unused by the transpose)
-    uint32_t n[3];
-    uint32_t imax[3];                // max(n_a - 2, 0): the largest lower corner
-    uint64_t stride[3];              // n2 * n3, n3, 1
-    uint64_t next[3];                // stride of the upper corner: 0 when n_a == 1 (constant axis)
-    float half[3];                   // sVoxel / 2
-    float inv_d[3];                  // 1 / dVoxel
+    VoxelGrid grid;
     float step;                      // target sample spacing in metres (accuracy * min dVoxel)
 };
 
-// Trilinear cell of p, clamp-to-edge: offset of the lower corner (64-bit: a 1024^3 volume is 4 GiB) and the weights w_a of the
-// upper corners.  Only called for points inside the box (midpoints of the clipped segment); the clamp keeps every p in bounds.
-__device__ __forceinline__ uint64_t trilinear_cell(const ProjVolume &v, float px, float py, float pz, float w[3]) {
-    const float p[3] = {px, py, pz};
-    uint64_t base = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        float u = (p[a] + v.half[a]) * v.inv_d[a] - 0.5f;
-        u = fminf(fmaxf(u, 0.0f), (float)(v.n[a] - 1u));
-        const uint32_t i = min((uint32_t)u, v.imax[a]);      // u >= 0: truncation is floor
-        w[a] = u - (float)i;
-        base += (uint64_t)i * v.stride[a];
-    }
-    return base;
+// voxel_cell of p.  Only called for points inside the box (midpoints of the clipped segment); the clamp keeps every p in bounds.
+__device__ __forceinline__ uint64_t trilinear_cell(const ProjVolume &v, const float p[3], float w[3]) {
+    float u[3];                      // dropped on purpose (the sampler's NaN hand-on needs it); gone once inlined
+    return voxel_cell(v.grid, p, w, u);
 }
 
 // The part of a ray inside the box and [near, far], cut into n midpoint-rule samples.  t0, t1 and n are the quantities a float32
@@ -52,19 +38,8 @@ enum SpanKind { kSpanEmpty = 0, kSpanOk = 1, kSpanUnbounded = 2 };   // unbounde
 
 __device__ __forceinline__ SpanKind ray_span(const ProjVolume &v, float4 a, float4 b, RaySpan &s) {
     const float o[3] = {a.x, a.y, a.z}, d[3] = {a.w, b.x, b.y};
-    float t0 = b.z, t1 = b.w;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (d[k] == 0.0f) {
-            if (o[k] < -v.half[k] || o[k] > v.half[k]) t1 = -INFINITY;    // parallel to the slab and outside it
-            continue;
-        }
-        const float ta = (-v.half[k] - o[k]) / d[k], tb = (v.half[k] - o[k]) / d[k];
-        const float lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
-        t0 = lo > t0 ? lo : t0;
-        t1 = hi < t1 ? hi : t1;
-    }
-    if (!(t1 > t0)) return kSpanEmpty;
+    float t0, t1;
+    if (!clip_ray(v.grid, o, d, b.z, b.w, t0, t1)) return kSpanEmpty;
     const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     const float len = (t1 - t0) * dn;
     const float nf = fmaxf(1.0f, ceilf(len / v.step));
@@ -73,17 +48,13 @@ __device__ __forceinline__ SpanKind ray_span(const ProjVolume &v, float4 a, floa
     s.seg = (t1 - t0) / nf;
     s.len = len;
     s.weight = len / nf;
-    // Sample k sits at p0 + s_k d with p0 = o + t0 d and s_k = (k + 1/2) seg, each a single-rounding fma: a cone ray's origin is
-    // ~1 m from the volume, and o + t d with an fp32 t ~ 1 would place every sample ~6e-8 m (6e-5 of a 1 mm voxel) off its spot.
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        s.d[k] = d[k];
-        s.p0[k] = fmaf(t0, d[k], o[k]);
-    }
+    for (int k = 0; k < 3; ++k) s.d[k] = d[k];
+    clip_entry(t0, o, d, s.p0);
     return kSpanOk;
 }
 
-// Position of sample k, from k and not by increments.
+// Position of sample k, from k and not by increments: p0 + s_k d with s_k = (k + 1/2) seg, a single-rounding fma like p0 itself.
 __device__ __forceinline__ void span_point(const RaySpan &s, uint32_t k, float p[3]) {
     const float t = ((float)k + 0.5f) * s.seg;
 #pragma unroll
@@ -91,10 +62,10 @@ __device__ __forceinline__ void span_point(const RaySpan &s, uint32_t k, float p
 }
 
 // Value of the volume at p: trilinear, clamp-to-edge.  Only called for points inside the box (midpoints of the clipped segment).
-__device__ __forceinline__ float sample_volume(const ProjVolume &v, float px, float py, float pz) {
+__device__ __forceinline__ float sample_volume(const ProjVolume &v, const float p[3]) {
     float w[3];
-    const float *__restrict__ q = v.data + trilinear_cell(v, px, py, pz, w);
-    const uint64_t sx = v.next[0], sy = v.next[1], sz = v.next[2];
+    const float *__restrict__ q = v.data + trilinear_cell(v, p, w);
+    const uint64_t sx = v.grid.next[0], sy = v.grid.next[1], sz = v.grid.next[2];
     const float c000 = q[0], c001 = q[sz], c010 = q[sy], c011 = q[sy + sz];
     const float c100 = q[sx], c101 = q[sx + sz], c110 = q[sx + sy], c111 = q[sx + sy + sz];
     const float c00 = c000 + w[2] * (c001 - c000), c01 = c010 + w[2] * (c011 - c010);
@@ -111,7 +82,7 @@ __device__ __forceinline__ float span_sum(const ProjVolume &v, const RaySpan &s)
     for (uint32_t k = 0; k < s.n; ++k) {
         float p[3];
         span_point(s, k, p);
-        acc += sample_volume(v, p[0], p[1], p[2]);
+        acc += sample_volume(v, p);
     }
     return acc;
 }
@@ -122,19 +93,11 @@ inline int make_volume(const char *who, const float *volume, uint32_t n1, uint32
     if (!volume || !dvoxel) return fail_who(who, "null pointer");
     if (n1 == 0 || n2 == 0 || n3 == 0) return fail_who(who, "zero volume dimension");
     if (!(step > 0.0f) || !std::isfinite(step)) return fail_who(who, "step must be > 0");
-    const uint32_t n[3] = {n1, n2, n3};
     for (int a = 0; a < 3; ++a) {
         if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) return fail_who(who, "voxel size must be > 0");
-        v->n[a] = n[a];
-        v->imax[a] = n[a] >= 2u ? n[a] - 2u : 0u;
-        v->half[a] = (float)((double)n[a] * (double)dvoxel[a] / 2.0);
-        v->inv_d[a] = 1.0f / dvoxel[a];
     }
     v->data = volume;
-    v->stride[0] = (uint64_t)n2 * n3;
-    v->stride[1] = n3;
-    v->stride[2] = 1;
-    for (int a = 0; a < 3; ++a) v->next[a] = n[a] > 1u ? v->stride[a] : 0u;
+    v->grid = voxel_grid(n1, n2, n3, dvoxel);
     v->step = step;
     return NAF_OK;
 }

@@ -75,7 +75,7 @@ int project_rays(const char *who, const char *kernel, const float *volume, uint3
     int rc = make_volume(who, volume, n1, n2, n3, dvoxel, step, &v);
     if (rc == NAF_OK) rc = make_ray_launch(who, rays, out, n_rays, &blocks);
     if (rc != NAF_OK) return rc;
-    return launch(kernel, rays_forward_kernel<P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P::field(v, dvoxel), rays, out, n_rays);
+    return launch(kernel, rays_forward_kernel<P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P::field(v), rays, out, n_rays);
 }
 
 template <class P>
@@ -86,7 +86,7 @@ int project_scan(const char *who, const char *kernel, const float *volume, const
     const int rc = make_scan_launch(who, volume, {out}, dims, dvoxel, poses, n_projections, det, step, &s, P::kForwardLayout);
     if (rc != NAF_OK) return rc;
     return launch(kernel, scan_forward_kernel<P>, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream,
-                  P::field(s.v, dvoxel), poses, s.g, out, s.tiles_x, s.tiles_per_view);
+                  P::field(s.v), poses, s.g, out, s.tiles_x, s.tiles_per_view);
 }
 
 template <class P>
@@ -98,7 +98,7 @@ int backproject_rays(const char *who, const char *kernel, const float *values, c
     int rc = make_volume(who, volume, n1, n2, n3, dvoxel, step, &v);
     if (rc == NAF_OK) rc = make_ray_launch(who, rays, values, n_rays, &blocks);
     if (rc != NAF_OK) return rc;
-    return launch(kernel, rays_transpose_kernel<P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P::grid(P::field(v, dvoxel)), volume,
+    return launch(kernel, rays_transpose_kernel<P>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P::grid(P::field(v)), volume,
                   values, rays, n_rays);
 }
 
@@ -110,7 +110,7 @@ int backproject_scan(const char *who, const char *kernel, const float *projectio
     const int rc = make_scan_launch(who, volume, {projections}, dims, dvoxel, poses, n_projections, det, step, &s);
     if (rc != NAF_OK) return rc;
     return launch(kernel, scan_transpose_kernel<P>, dim3(s.tiles_per_view * n_projections), dim3(256), 0, (hipStream_t)stream,
-                  P::grid(P::field(s.v, dvoxel)), volume, projections, poses, s.g, s.tiles_x, s.tiles_per_view);
+                  P::grid(P::field(s.v)), volume, projections, poses, s.g, s.tiles_x, s.tiles_per_view);
 }
 
 }  // namespace

@@ -3,10 +3,10 @@
 //   InterpolatedPair  P1 / P2 / P4: trilinear samples at a step (project_device.h, backproject_device.h)
 //   SiddonPair        P6 / P7 / P8: exact chord lengths per voxel (siddon_device.h, which includes nothing of HIP)
 // A pair says what its kernels take (`Field` to read a volume, `Grid` beside the volumes a transpose adds into), how the host makes
-// that from a checked ProjVolume, its forward line integral, its OS-SART residual, its transpose walk with the two deposits, and the
-// layout of its forward scan kernel.  The host checks are make_volume's and make_scan_launch's for both: the Siddon entry points
-// have no sample step and pass 1, which any valid call passes.  The Siddon pair has no residual(): its residual kernel is written
-// out in sart.hip.  The shapes here (integral takes the two float4, the rest a Ray made in the kernel, Residual is {y, res}) are the
+// that from a checked ProjVolume (whose VoxelGrid both pairs read), its forward line integral, its OS-SART residual, its transpose
+// walk with the two deposits, and the layout of its forward scan kernel.  The host checks are make_volume's and make_scan_launch's
+// for both: the Siddon entry points have no sample step and pass 1.  The Siddon pair has no residual(): its residual kernel is
+// written out in sart.hip.  The shapes here (integral takes the two float4, the rest a Ray made in the kernel, Residual is {y, res}) are the
 // ones that compile to the hand-written kernels' machine code; check with tools/compare_kernel_asm.py
 // before changing them.
 #pragma once
@@ -37,7 +37,7 @@ struct InterpolatedPair {
         float4 a, b;                 // (o, d.x) and (d.y, d.z, near, far)
     };
 
-    static Field field(const ProjVolume &v, const float *) { return v; }
+    static Field field(const ProjVolume &v) { return v; }
     static const Grid &grid(const Field &f) { return f; }
     __device__ static __forceinline__ Ray ray(float4 a, float4 b) { return Ray{a, b}; }
 
@@ -96,18 +96,38 @@ struct SiddonDepositPair {
 };
 
 struct SiddonPair {
+    // What a Siddon kernel is handed of a VoxelGrid: the fields its walk reads, side by side, which it fetches from the argument
+    // segment with one scalar load less than out of a whole VoxelGrid.  grid() is the VoxelGrid again: imax
+    // and next, which no walk reads, come from the one place that defines them and fold away.
+    struct Grid {
+        uint32_t n[3];
+        uint64_t stride[3];
+        float half[3], d[3], inv_d[3];
+
+        template <class From, class To>
+        __host__ __device__ static __forceinline__ void copy(const From &f, To &t) {
+            NAF_UNROLL
+            for (int a = 0; a < 3; ++a)
+                t.n[a] = f.n[a], t.stride[a] = f.stride[a], t.half[a] = f.half[a], t.d[a] = f.d[a], t.inv_d[a] = f.inv_d[a];
+        }
+        __host__ __device__ __forceinline__ VoxelGrid grid() const {
+            VoxelGrid g;
+            copy(*this, g);
+            voxel_grid_corners(g);
+            return g;
+        }
+    };
     struct Field {
-        SiddonGrid grid;
+        Grid grid;
         const float *volume;
     };
-    using Grid = SiddonGrid;
     using ValueDeposit = SiddonDepositValue;
     using PairDeposit = SiddonDepositPair;
     static constexpr ScanLayout kForwardLayout = kScanTiles;
 
-    static Field field(const ProjVolume &v, const float *dvoxel) {
+    static Field field(const ProjVolume &v) {
         Field f;
-        siddon_grid(v.n[0], v.n[1], v.n[2], dvoxel, &f.grid);
+        Grid::copy(v.grid, f.grid);
         f.volume = v.data;
         return f;
     }
@@ -121,7 +141,7 @@ struct SiddonPair {
     __device__ static __forceinline__ float integral(const Field &f, float4 a, float4 b) {
         const float *volume = f.volume;
         SiddonIntegral sum;
-        const SiddonKind kind = siddon_forward(f.grid, ray(a, b), [volume](uint64_t offset) { return volume[offset]; }, sum);
+        const SiddonKind kind = siddon_forward(f.grid.grid(), ray(a, b), [volume](uint64_t offset) { return volume[offset]; }, sum);
         if (kind == kSiddonEmpty) return 0.0f;
         if (kind == kSiddonNotFinite) return __builtin_nanf("");
         return sum.acc;
@@ -129,7 +149,7 @@ struct SiddonPair {
 
     template <class Deposit>
     __device__ static __forceinline__ void transpose(const Grid &grid, const Ray &ray, const Deposit &deposit) {
-        siddon_transpose(grid, ray, deposit);
+        siddon_transpose(grid.grid(), ray, deposit);
     }
 };
 

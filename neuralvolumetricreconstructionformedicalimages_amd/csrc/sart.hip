@@ -60,7 +60,7 @@ subset_residual_kernel<SiddonPair>(SiddonPair::Field field, const float *__restr
         const float *volume = field.volume;
         SiddonIntegralAndRow sum;
         const SiddonKind kind =
-            siddon_forward(field.grid, SiddonPair::ray(ray[0], ray[1]), [volume](uint64_t offset) { return volume[offset]; }, sum);
+            siddon_forward(field.grid.grid(), SiddonPair::ray(ray[0], ray[1]), [volume](uint64_t offset) { return volume[offset]; }, sum);
         if (kind == kSiddonEmpty) {
             res = b;
             weighted = 0.0f;
@@ -147,7 +147,7 @@ int sart_residual_scan(const char *who, const char *kernel, const float *volume,
                                     n_scan_views);
     if (rc != NAF_OK) return rc;
     return launch(kernel, subset_residual_kernel<P>, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream,
-                  P::field(s.v, dvoxel), poses, s.g, ViewList{view_index, n_scan_views}, projections, y, r, s.tiles_x, s.tiles_per_view);
+                  P::field(s.v), poses, s.g, ViewList{view_index, n_scan_views}, projections, y, r, s.tiles_x, s.tiles_per_view);
 }
 
 template <class P>
@@ -160,7 +160,7 @@ int sart_backproject_scan(const char *who, const char *kernel, const float *y, c
     if (rc != NAF_OK) return rc;
     if (den == num) return fail_who(who, "num and den must be two volumes");
     return launch(kernel, subset_transpose_kernel<P>, dim3(s.tiles_per_view * n_sub), dim3(256), 0, (hipStream_t)stream,
-                  P::grid(P::field(s.v, dvoxel)), num, den, y, poses, s.g, ViewList{view_index, n_scan_views}, s.tiles_x,
+                  P::grid(P::field(s.v)), num, den, y, poses, s.g, ViewList{view_index, n_scan_views}, s.tiles_x,
                   s.tiles_per_view);
 }
 

@@ -17,37 +17,15 @@
 #include <cmath>
 #include <cstdint>
 
-#include "host_device.h"
+#include "voxel_grid.h"
 
 namespace naf {
 
 constexpr uint32_t kSiddonGroup = 4;   // steps whose loads are issued together, before the first of them is used
 
-struct SiddonGrid {
-    uint32_t n[3];
-    uint64_t stride[3];                // n2 * n3, n3, 1
-    float half[3];                     // fp32(n_a * dvoxel_a / 2), P1's h_a
-    float dvox[3];                     // dvoxel_a
-    float inv_d[3];                    // 1 / dvoxel_a
-};
-
-// Host: the grid of a [n1, n2, n3] volume; the same h_a and 1 / dvoxel_a as P1's make_volume.  Arguments are checked by the caller.
-inline void siddon_grid(uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, SiddonGrid *g) {
-    const uint32_t n[3] = {n1, n2, n3};
-    for (int a = 0; a < 3; ++a) {
-        g->n[a] = n[a];
-        g->half[a] = (float)((double)n[a] * (double)dvoxel[a] / 2.0);
-        g->dvox[a] = dvoxel[a];
-        g->inv_d[a] = 1.0f / dvoxel[a];
-    }
-    g->stride[0] = (uint64_t)n2 * n3;
-    g->stride[1] = n3;
-    g->stride[2] = 1;
-}
-
-// The clipped segment of a ray: P1's ray_span without the sample count -- the same float32 operations in the same order.
+// The clipped segment of a ray: clip_ray's and clip_entry's, and what the walk needs of it.
 struct SiddonSpan {
-    float p0[3], d[3];                 // p0 = fma(t0, d, o)
+    float p0[3], d[3];                 // p0 = clip_entry(t0, o, d)
     float s_end;                       // t1 - t0
     float dn;                          // |d|
 };
@@ -56,27 +34,16 @@ enum SiddonKind { kSiddonEmpty = 0, kSiddonOk = 1, kSiddonNotFinite = 2 };
 
 NAF_HD bool siddon_finite(float x) { return (x - x) == 0.0f; }   // false for NaN and +-infinity
 
-NAF_HD SiddonKind siddon_span(const SiddonGrid &g, const float o[3], const float d[3], float near, float far, SiddonSpan &s) {
-    float t0 = near, t1 = far;
-    NAF_UNROLL
-    for (int k = 0; k < 3; ++k) {
-        if (d[k] == 0.0f) {
-            if (o[k] < -g.half[k] || o[k] > g.half[k]) t1 = -INFINITY;    // parallel to the slab and outside it
-            continue;
-        }
-        const float ta = (-g.half[k] - o[k]) / d[k], tb = (g.half[k] - o[k]) / d[k];
-        const float lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;
-        t0 = lo > t0 ? lo : t0;
-        t1 = hi < t1 ? hi : t1;
-    }
-    if (!(t1 > t0)) return kSiddonEmpty;
+NAF_HD SiddonKind siddon_span(const VoxelGrid &g, const float o[3], const float d[3], float near, float far, SiddonSpan &s) {
+    float t0, t1;
+    if (!clip_ray(g, o, d, near, far, t0, t1)) return kSiddonEmpty;
     s.dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     s.s_end = t1 - t0;
     bool finite = siddon_finite(s.s_end);
+    clip_entry(t0, o, d, s.p0);
     NAF_UNROLL
     for (int k = 0; k < 3; ++k) {
         s.d[k] = d[k];
-        s.p0[k] = fmaf(t0, d[k], o[k]);
         finite = finite && siddon_finite(s.p0[k]);
     }
     return finite ? kSiddonOk : kSiddonNotFinite;
@@ -84,15 +51,15 @@ NAF_HD SiddonKind siddon_span(const SiddonGrid &g, const float o[3], const float
 
 // Voxel index of coordinate p on axis a, clamped to [0, n_a - 1].  The clamp is made on the float (fmaxf / fminf drop a NaN), so the
 // conversion to an integer is defined for every input.
-NAF_HD int32_t siddon_index(const SiddonGrid &g, int a, float p) {
+NAF_HD int32_t siddon_index(const VoxelGrid &g, int a, float p) {
     float u = floorf((p + g.half[a]) * g.inv_d[a]);
     u = fminf(fmaxf(u, 0.0f), (float)(g.n[a] - 1u));
     return (int32_t)u;
 }
 
 // Parameter s (from p0) at which the ray crosses plane m of axis a: from m itself, never by increments.
-NAF_HD float siddon_crossing(const SiddonGrid &g, const SiddonSpan &r, int a, int32_t m) {
-    return (fmaf((float)m, g.dvox[a], -g.half[a]) - r.p0[a]) / r.d[a];
+NAF_HD float siddon_crossing(const VoxelGrid &g, const SiddonSpan &r, int a, int32_t m) {
+    return (fmaf((float)m, g.d[a], -g.half[a]) - r.p0[a]) / r.d[a];
 }
 
 // State of a walk: the current voxel (as a 64-bit element offset), the crossings left per axis and each axis' next crossing.
@@ -106,7 +73,7 @@ struct SiddonWalk {
 };
 
 // Returns the number of steps: rem_x + rem_y + rem_z + 1.
-NAF_HD uint32_t siddon_begin(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w) {
+NAF_HD uint32_t siddon_begin(const VoxelGrid &g, const SiddonSpan &r, SiddonWalk &w) {
     uint32_t steps = 1;
     w.offset = 0;
     w.s_prev = 0.0f;
@@ -127,7 +94,7 @@ NAF_HD uint32_t siddon_begin(const SiddonGrid &g, const SiddonSpan &r, SiddonWal
 
 // One step: the offset of the current voxel and the length (in s) of the segment inside it, then the move across the nearest plane.
 // With no crossing left the segment runs to s_end, and every later step is a zero-length segment of the same voxel.
-NAF_HD void siddon_step(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w, uint64_t &offset, float &ds) {
+NAF_HD void siddon_step(const VoxelGrid &g, const SiddonSpan &r, SiddonWalk &w, uint64_t &offset, float &ds) {
     const float dx = r.d[0], dy = r.d[1], dz = r.d[2];
     const bool ax = w.rem[0] > 0u, ay = w.rem[1] > 0u, az = w.rem[2] > 0u;
     // the smallest of the next crossings; an exhausted axis counts as +infinity: it is never chosen (integer tests gate every choice)
@@ -149,7 +116,7 @@ NAF_HD void siddon_step(const SiddonGrid &g, const SiddonSpan &r, SiddonWalk &w,
     }
     float num[3];
     NAF_UNROLL
-    for (int a = 0; a < 3; ++a) num[a] = fmaf((float)(w.idx[a] + (w.dir[a] > 0 ? 1 : 0)), g.dvox[a], -g.half[a]) - r.p0[a];
+    for (int a = 0; a < 3; ++a) num[a] = fmaf((float)(w.idx[a] + (w.dir[a] > 0 ? 1 : 0)), g.d[a], -g.half[a]) - r.p0[a];
     const float c = (px ? num[0] : (py ? num[1] : num[2])) / (px ? dx : (py ? dy : dz));   // siddon_crossing of the picked axis
     NAF_UNROLL
     for (int a = 0; a < 3; ++a) w.next[a] = pick[a] ? c : w.next[a];
@@ -180,7 +147,7 @@ struct SiddonIntegralAndRow {
 // the first of them is used: the indices depend on one another, the loads do not.  Returns the span's kind; `sum` is left as it was
 // unless that is kSiddonOk, and what an empty or a non-finite span yields is the caller's to say.
 template <class Load, class Sum>
-NAF_HD SiddonKind siddon_forward(const SiddonGrid &g, const SiddonRay &ray, Load load, Sum &sum) {
+NAF_HD SiddonKind siddon_forward(const VoxelGrid &g, const SiddonRay &ray, Load load, Sum &sum) {
     SiddonSpan r;
     const SiddonKind kind = siddon_span(g, ray.o, ray.d, ray.near, ray.far, r);
     if (kind != kSiddonOk) return kind;
@@ -226,7 +193,7 @@ NAF_HD SiddonKind siddon_forward(const SiddonGrid &g, const SiddonRay &ray, Load
 // voxel's fixed point) send nothing, and neither does an empty span, a non-finite one, or a deposit that says up front
 // (deposit.wanted()) that it has nothing to add.  A group is stepped first and sent after: nothing here waits for what `deposit` does.
 template <class Deposit>
-NAF_HD void siddon_transpose(const SiddonGrid &g, const SiddonRay &ray, const Deposit &deposit) {
+NAF_HD void siddon_transpose(const VoxelGrid &g, const SiddonRay &ray, const Deposit &deposit) {
     if (!deposit.wanted()) return;
     SiddonSpan r;
     if (siddon_span(g, ray.o, ray.d, ray.near, ray.far, r) != kSiddonOk) return;

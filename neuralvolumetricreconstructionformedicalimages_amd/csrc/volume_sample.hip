@@ -28,7 +28,7 @@ struct DrawBox {
 };
 
 __global__ void __launch_bounds__(kSampleThreads)
-volume_sample_points_kernel(const float *__restrict__ f, SampleGrid g, const Point3 *__restrict__ points, uint64_t n,
+volume_sample_points_kernel(const float *__restrict__ f, VoxelGrid g, const Point3 *__restrict__ points, uint64_t n,
                             float *__restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * kSampleThreads + threadIdx.x;
     if (i >= n) return;
@@ -38,7 +38,7 @@ volume_sample_points_kernel(const float *__restrict__ f, SampleGrid g, const Poi
 }
 
 __global__ void __launch_bounds__(kSampleThreads)
-volume_draw_sample_kernel(const float *__restrict__ f, SampleGrid g, DrawBox box, uint64_t seed, uint32_t step, uint32_t n,
+volume_draw_sample_kernel(const float *__restrict__ f, VoxelGrid g, DrawBox box, uint64_t seed, uint32_t step, uint32_t n,
                           Point3 *__restrict__ points_out, float *__restrict__ targets_out) {
     const uint32_t i = blockIdx.x * kSampleThreads + threadIdx.x;
     if (i >= n) return;
@@ -54,7 +54,7 @@ volume_draw_sample_kernel(const float *__restrict__ f, SampleGrid g, DrawBox box
 }
 
 // Argument checks shared by the two entry points; fills the grid.
-int sample_check(const char *who, const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, SampleGrid *g) {
+int sample_check(const char *who, const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, VoxelGrid *g) {
     if (!volume || !dvoxel) return fail_who(who, "null pointer");
     if (n1 == 0 || n2 == 0 || n3 == 0) return fail_who(who, "zero volume dimension");
     if (n1 > NAF_VOLUME_SAMPLE_MAX_EXTENT || n2 > NAF_VOLUME_SAMPLE_MAX_EXTENT || n3 > NAF_VOLUME_SAMPLE_MAX_EXTENT)
@@ -62,7 +62,7 @@ int sample_check(const char *who, const float *volume, uint32_t n1, uint32_t n2,
     for (int a = 0; a < 3; ++a) {
         if (!(dvoxel[a] > 0.0f) || !std::isfinite(dvoxel[a])) return fail_who(who, "voxel size must be > 0 and finite");
     }
-    sample_grid(n1, n2, n3, dvoxel, g);
+    *g = voxel_grid(n1, n2, n3, dvoxel);
     return NAF_OK;
 }
 
@@ -75,7 +75,7 @@ using namespace naf;
 extern "C" int naf_volume_sample_points(const float *volume, uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel,
                                         const float *points, uint64_t n, float *out, void *stream) {
     if (n == 0) return NAF_OK;
-    SampleGrid g;
+    VoxelGrid g;
     const int rc = sample_check("volume_sample_points", volume, n1, n2, n3, dvoxel, &g);
     if (rc != NAF_OK) return rc;
     if (!points || !out) return fail(NAF_ERR_INVALID_ARGUMENT, "volume_sample_points: null pointer");
@@ -90,7 +90,7 @@ extern "C" int naf_volume_draw_sample(const float *volume, const uint32_t *dims,
                                       uint64_t seed, uint32_t step, uint32_t n, float *points_out, float *targets_out, void *stream) {
     if (n == 0) return NAF_OK;
     if (!dims) return fail(NAF_ERR_INVALID_ARGUMENT, "volume_draw_sample: null pointer");
-    SampleGrid g;
+    VoxelGrid g;
     const int rc = sample_check("volume_draw_sample", volume, dims[0], dims[1], dims[2], dvoxel, &g);
     if (rc != NAF_OK) return rc;
     if (!lo || !hi || !points_out || !targets_out) return fail(NAF_ERR_INVALID_ARGUMENT, "volume_draw_sample: null pointer");

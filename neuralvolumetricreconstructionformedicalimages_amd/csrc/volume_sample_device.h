@@ -5,16 +5,10 @@
 // operation in the order written (the library and the host check are built with -ffp-contract=off); every fused multiply-add is
 // asked for by name.
 //
-// Order of operations, per axis a (h_a = fp32(n_a d_a / 2) and r_a = fp32(1 / d_a) are formed on the host, as P1 forms them):
-//   t  = p_a + h_a                       one add
-//   u' = t * r_a                         one multiply
-//   u' = u' - 0.5                        one subtract
-//   u  = min(max(u', 0), n_a - 1)        on the float, before any conversion: fmaxf / fminf return the other operand for a NaN, so a
-//                                        NaN becomes 0 and +-inf the nearer edge; no index can leave the volume whatever p holds
-//   i  = min((uint32)u, max(n_a - 2, 0)) u >= 0: the truncation is the floor
-//   w  = u - (float)i                    exact (u and i are less than 2 apart and below 2^24); a NaN p_a gives w = NaN instead
-// The eight corners c_xyz = f[i_0 + x, i_1 + y, i_2 + z] (an axis of one voxel has no upper corner: its x is dropped and its w is 0)
-// are loaded before the first of them is used, then seven interpolations lerp(a, b, w) = fma(w, b, fma(-w, a, a)), two fmas each
+// The cell and its weights are voxel_grid.h's (voxel_cell: u = (p_a + h_a) r_a - 1/2, clamped on the float before any conversion,
+// so no index can leave the volume whatever p holds); a NaN u gives w = NaN instead.  The eight corners c_xyz = f[i_0 + x, i_1 + y,
+// i_2 + z] (an axis of one voxel has no upper corner: its x is dropped and its w is 0) are loaded before the first of them is used,
+// then seven interpolations lerp(a, b, w) = fma(w, b, fma(-w, a, a)), two fmas each
 // (a - w a, then + w b: w = 0 returns a's bits and w = 1 returns b's, which a + w (b - a) does not):
 //   along axis 2:  c_00 = lerp(c_000, c_001, w_2), c_01 = lerp(c_010, c_011, w_2), c_10 = lerp(c_100, c_101, w_2), c_11 = lerp(c_110, c_111, w_2)
 //   along axis 1:  c_0 = lerp(c_00, c_01, w_1), c_1 = lerp(c_10, c_11, w_1)
@@ -25,56 +19,25 @@
 #include <cmath>
 #include <cstdint>
 
-#include "host_device.h"
+#include "mix32.h"
+#include "voxel_grid.h"
 
 namespace naf {
 
-struct SampleGrid {
-    uint32_t n[3];
-    uint32_t imax[3];                  // max(n_a - 2, 0): the largest lower corner
-    uint64_t stride[3];                // n2 * n3, n3, 1
-    uint64_t next[3];                  // stride of the upper corner: 0 when n_a == 1 (constant axis)
-    float half[3];                     // fp32(n_a * dvoxel_a / 2), P1's h_a
-    float inv_d[3];                    // fp32(1 / dvoxel_a)
-};
-
-// Host: the grid of a [n1, n2, n3] volume; the same h_a and 1 / dvoxel_a as P1's make_volume and P6's siddon_grid.  Arguments are
-// checked by the caller.
-inline void sample_grid(uint32_t n1, uint32_t n2, uint32_t n3, const float *dvoxel, SampleGrid *g) {
-    const uint32_t n[3] = {n1, n2, n3};
-    for (int a = 0; a < 3; ++a) {
-        g->n[a] = n[a];
-        g->imax[a] = n[a] >= 2u ? n[a] - 2u : 0u;
-        g->half[a] = (float)((double)n[a] * (double)dvoxel[a] / 2.0);
-        g->inv_d[a] = 1.0f / dvoxel[a];
-    }
-    g->stride[0] = (uint64_t)n2 * n3;
-    g->stride[1] = n3;
-    g->stride[2] = 1;
-    for (int a = 0; a < 3; ++a) g->next[a] = n[a] > 1u ? g->stride[a] : 0u;
-}
-
-// The cell of p: the 64-bit element offset of its lower corner and the three weights of the upper corners.
-NAF_HD uint64_t sample_cell(const SampleGrid &g, const float p[3], float w[3]) {
-    uint64_t base = 0;
+// voxel_cell of p with V4's contract for a NaN: a coordinate whose u is NaN gets that NaN as its weight.  It never chose an index:
+// voxel_cell clamped it to 0 first.
+NAF_HD uint64_t sample_cell(const VoxelGrid &g, const float p[3], float w[3]) {
+    float u[3];
+    const uint64_t base = voxel_cell(g, p, w, u);
     NAF_UNROLL
-    for (int a = 0; a < 3; ++a) {
-        float u = p[a] + g.half[a];
-        u = u * g.inv_d[a];
-        u = u - 0.5f;
-        const float c = fminf(fmaxf(u, 0.0f), (float)(g.n[a] - 1u));   // a NaN leaves fmaxf as 0
-        const uint32_t t = (uint32_t)c;                                 // 0 <= c <= n_a - 1 < 2^32: defined, and it is the floor
-        const uint32_t i = t < g.imax[a] ? t : g.imax[a];
-        w[a] = u != u ? u : c - (float)i;                               // the NaN is handed on; it never chose an index
-        base += (uint64_t)i * g.stride[a];
-    }
+    for (int a = 0; a < 3; ++a) w[a] = u[a] != u[a] ? u[a] : w[a];
     return base;
 }
 
 NAF_HD float sample_lerp(float a, float b, float w) { return fmaf(w, b, fmaf(-w, a, a)); }
 
 // The eight corners of the cell at `base`, all loaded before the first is used (c[4 x + 2 y + z]).
-NAF_HD void sample_corners(const float *f, const SampleGrid &g, uint64_t base, float c[8]) {
+NAF_HD void sample_corners(const float *f, const VoxelGrid &g, uint64_t base, float c[8]) {
     const float *q = f + base;
     const uint64_t sx = g.next[0], sy = g.next[1], sz = g.next[2];
     c[0] = q[0];
@@ -95,7 +58,7 @@ NAF_HD float sample_blend(const float c[8], const float w[3]) {
 }
 
 // Value of the volume at p: trilinear, clamp-to-edge; NaN when a coordinate of p is NaN.
-NAF_HD float sample_point(const float *f, const SampleGrid &g, const float p[3]) {
+NAF_HD float sample_point(const float *f, const VoxelGrid &g, const float p[3]) {
     float w[3], c[8];
     const uint64_t base = sample_cell(g, p, w);
     sample_corners(f, g, base, c);
@@ -103,20 +66,12 @@ NAF_HD float sample_point(const float *f, const SampleGrid &g, const float p[3])
 }
 
 // ---- the draw: point i of step `step` under `seed`, uniform in the box [lo, hi] -----------------------------------------------------
-// The integer finaliser of csrc/naf_device.h's mix32 ("lowbias32"), restated here because that header needs HIP.
-NAF_HD uint32_t sample_mix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x7feb352du;
-    h ^= h >> 15; h *= 0x846ca68bu;
-    h ^= h >> 16;
-    return h;
-}
-
 // 32 random bits of (seed, step, i, axis): three rounds of the finaliser, each keyed by the next word.  No state: equal arguments
 // give equal bits.  All arithmetic is uint32 with wrap-around.
 NAF_HD uint32_t sample_hash(uint64_t seed, uint32_t step, uint32_t i, uint32_t axis) {
-    uint32_t h = sample_mix32((uint32_t)seed ^ (i * 0x9e3779b1u));
-    h = sample_mix32(h ^ (uint32_t)(seed >> 32) ^ (step * 0x85ebca77u) ^ 0x27d4eb2fu);
-    return sample_mix32(h ^ ((axis + 1u) * 0xc2b2ae3du));
+    uint32_t h = mix32((uint32_t)seed ^ (i * 0x9e3779b1u));
+    h = mix32(h ^ (uint32_t)(seed >> 32) ^ (step * 0x85ebca77u) ^ 0x27d4eb2fu);
+    return mix32(h ^ ((axis + 1u) * 0xc2b2ae3du));
 }
 
 // 32 bits -> [0, 1): the top 24 bits times 2^-24 (both exact in fp32).

@@ -3,7 +3,7 @@ section 17) and of the scatter's enumeration it has to cover -- not a test modul
 
 `support`, `footprint`, `pixel_range` and `k_range` repeat the header's float32 operations in its order (numpy float32 arrays:
 every operation rounds once), vectorised over voxels and rays.  `spans` and `scatter_triples` restate what the scatter does with a
-ray in float32 (ray_span, span_point, trilinear_cell of csrc/project_device.h); the fused multiply-adds are formed in float64 and
+ray in float32 (ray_span, span_point, trilinear_cell of csrc/project_device.h over clip_ray and voxel_cell of csrc/voxel_grid.h); the fused multiply-adds are formed in float64 and
 rounded once, which differs from a true fma by a double rounding at worst."""
 import numpy as np
 

@@ -25,7 +25,7 @@ def _fma32(a, b, c):
 
 
 def spans(rays, dims, dvoxel):
-    """rays [n, 8] -> float32 p0 [n, 3], d [n, 3], s_end [n], |d| [n] and kind [n] in the kernel's order (siddon_span)."""
+    """rays [n, 8] -> float32 p0 [n, 3], d [n, 3], s_end [n], |d| [n] and kind [n] in the kernel's order (siddon_span over clip_ray of csrc/voxel_grid.h)."""
     r = np.asarray(rays, dtype=f32)
     o, d = r[:, 0:3], r[:, 3:6]
     t0, t1 = r[:, 6].copy(), r[:, 7].copy()

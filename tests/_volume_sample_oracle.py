@@ -17,7 +17,7 @@ C_BOUND = 60.0
 
 
 def half_extent(dims, dvoxel):
-    """h_a = fp32(n_a * d_a / 2) from the float32 voxel size, as make_volume, siddon_grid and sample_grid form it."""
+    """h_a = fp32(n_a * d_a / 2) from the float32 voxel size, as voxel_grid of csrc/voxel_grid.h forms it."""
     d = np.asarray(dvoxel, dtype=np.float32).astype(np.float64)
     return (np.asarray(dims, dtype=np.float64) * d / 2.0).astype(np.float32)
 

@@ -65,7 +65,7 @@ def test_gathered_column_equals_the_dense_matrix(name):
 
 
 def test_k_range_with_a_zero_direction_component():
-    """d[k] == 0 exactly, as ray_span treats it: inside the slab the axis does not constrain t, outside there is no sample."""
+    """d[k] == 0 exactly, as clip_ray (ray_span) treats it: inside the slab the axis does not constrain t, outside there is no sample."""
     f32 = np.float32
     lo, hi = np.array([-1, -1, -1], dtype=f32), np.array([1, 1, 1], dtype=f32)
     d = np.array([1, 0, 0], dtype=f32)

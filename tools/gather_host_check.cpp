@@ -38,8 +38,7 @@ bool read_file(const char *path, std::vector<T> &v) {
 
 int main(int argc, char **argv) {
     if (argc != 14) return usage(argv[0], "n1 n2 n3 W H n_views parallel grid det poses spans triples out");
-    naf::GatherGrid grid;
-    for (int a = 0; a < 3; ++a) grid.n[a] = (uint32_t)std::atoi(argv[1 + a]);
+    const uint32_t n1 = (uint32_t)std::atoi(argv[1]), n2 = (uint32_t)std::atoi(argv[2]), n3 = (uint32_t)std::atoi(argv[3]);
     const uint32_t W = (uint32_t)std::atoi(argv[4]), H = (uint32_t)std::atoi(argv[5]), N = (uint32_t)std::atoi(argv[6]);
     const int parallel = std::atoi(argv[7]);
     std::vector<float> g, d, poses, spans;
@@ -47,13 +46,12 @@ int main(int argc, char **argv) {
     if (!read_file(argv[8], g) || !read_file(argv[9], d) || !read_file(argv[10], poses) || !read_file(argv[11], spans) ||
         !read_file(argv[12], triples))
         return kIoFailure;
-    const size_t per_view = (size_t)W * H, n_voxels = (size_t)grid.n[0] * grid.n[1] * grid.n[2];
+    const size_t per_view = (size_t)W * H, n_voxels = (size_t)n1 * n2 * n3;
     if (g.size() != 6 || d.size() != 5 || poses.size() != (size_t)N * 12 || spans.size() != per_view * N * 9 || triples.size() % 3)
         return kIoFailure;
-    for (int a = 0; a < 3; ++a) {
-        grid.half[a] = g.at(a);
-        grid.d[a] = g.at(3 + a);
-    }
+    const naf::VoxelGrid grid = naf::voxel_grid(n1, n2, n3, &g.at(3));
+    for (int a = 0; a < 3; ++a)
+        if (grid.half[a] != g.at(a)) return kBadArguments;                                   // the driver's h_a is the library's
     const naf::GatherDetector det{W, H, d.at(0), d.at(1), d.at(2), d.at(3), d.at(4), parallel};
     // candidate k-range of every (ray, voxel): [lo, hi] inclusive, hi < lo when the pair is not visited
     std::vector<int32_t> k_lo(per_view * N * n_voxels, 0), k_hi(per_view * N * n_voxels, -1);

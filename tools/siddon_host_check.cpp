@@ -51,7 +51,7 @@ size_t differences(const std::vector<Term> &a, const std::vector<Term> &b) {
 }
 
 // The restatement: every step of the ray, ungrouped, for the padded trip count.  Nothing for a span that is not ok.
-naf::SiddonKind restate(const naf::SiddonGrid &grid, const naf::SiddonRay &ray, std::vector<Term> &steps) {
+naf::SiddonKind restate(const naf::VoxelGrid &grid, const naf::SiddonRay &ray, std::vector<Term> &steps) {
     steps.clear();
     naf::SiddonSpan span;
     const naf::SiddonKind kind = naf::siddon_span(grid, ray.o, ray.d, ray.near, ray.far, span);
@@ -109,8 +109,7 @@ int main(int argc, char **argv) {
         !read_all(argv[10], rays.get(), n_rays * 8) || !read_all(argv[11], values.get(), n_rays))
         return kIoFailure;
     for (size_t i = 0; i < n_vox; ++i) ones[i] = 1.0f;
-    naf::SiddonGrid grid;
-    naf::siddon_grid(n1, n2, n3, dvoxel, &grid);
+    const naf::VoxelGrid grid = naf::voxel_grid(n1, n2, n3, dvoxel);
     const float *data = volume.get(), *one = ones.get();
     size_t value_total = 0, num_total = 0, den_total = 0, mismatches = 0;
     std::vector<Term> steps, positive, none, called;

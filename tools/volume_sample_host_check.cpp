@@ -50,13 +50,12 @@ double sample_f64(const std::vector<float> &f, const uint32_t n[3], const float 
 }
 
 int offsets() {
-    // 2048^3 = 2^33 voxels: the offset of a cell near the far corner needs 34 bits.  Only sample_cell runs: nothing is loaded.
+    // 2048^3 = 2^33 voxels: the offset of a cell near the far corner needs 34 bits.  Only sample_cell (voxel_cell) runs: nothing is loaded.
     int wrong = 0;
     const uint32_t dims[2][3] = {{2048, 2048, 2048}, {70000, 300, 400}};
     for (const auto &n : dims) {
         const float d[3] = {0.001f, 0.001f, 0.001f};
-        naf::SampleGrid g;
-        naf::sample_grid(n[0], n[1], n[2], d, &g);
+        const naf::VoxelGrid g = naf::voxel_grid(n[0], n[1], n[2], d);
         for (int k = 0; k < 64; ++k) {
             uint32_t i[3];
             float p[3], w[3];
@@ -87,8 +86,7 @@ int main(int argc, char **argv) {
     if (n[0] == 0 || n[1] == 0 || n[2] == 0 || !(d[0] > 0.0f) || !(d[1] > 0.0f) || !(d[2] > 0.0f)) return kBadArguments;
     std::vector<float> f((size_t)n[0] * n[1] * n[2]);                   // exactly the volume: nothing to spare behind it
     if (!read_all(argv[samp ? 9 : 17], f)) return kIoFailure;
-    naf::SampleGrid g;
-    naf::sample_grid(n[0], n[1], n[2], d, &g);
+    const naf::VoxelGrid g = naf::voxel_grid(n[0], n[1], n[2], d);
     std::vector<float> pts(3 * count), out(count);
 
     if (samp) {
