@@ -940,6 +940,45 @@ int naf_frames_condition(const void *raw, int raw_dtype, const float *dark, cons
 int naf_inpaint_rows(const float *p, const uint8_t *mask, const float *prior, float eps, uint32_t N, uint32_t H, uint32_t W, float *out,
                      uint32_t *counts, void *stream);
 
+/* A5  centre-of-rotation search (tomopy's find_center; Donath et al., J. Opt. Soc. Am. A 23, 2006): one slice back-projected from
+ * filtered detector rows for K candidate offsets of the detector's column axis in one launch, and the two scores of every such slice
+ * (center.py, reconstruct.find_center).  DESIGN.md section 34; the per-pixel arithmetic is csrc/center_device.h.
+ *   q      f32 [S, N, W] C-contiguous: S slices, N views, W detector columns; filtered and FDK-weighted on the nominal geometry
+ *          (naf_filter_rows).  Nothing is filtered here.
+ *   trig   f32 [N, 2] = (cos a_i, sin a_i)
+ *   cand   f32 [K]: candidate offsets in metres, added to ou
+ *   f      f32 [S, K, n, n]: f[s, k, ix, iy] at x = (ix - (n - 1) / 2) dx + ox, y = (iy - (n - 1) / 2) dy + oy
+ * The column axis is Rz(a) e_y and the source stands at DSO (cos a, sin a).  Per pixel and view, every operation one IEEE fp32
+ * operation in the order written:
+ *   t = y cos a - x sin a;   parallel: u* = t, w = 1;   cone: s = x cos a + y sin a, U = DSO - s, u* = DSD t / U, w = (DSO / U)^2
+ *   base = (u* - ou) (1 / du) + (W / 2 - 0.5);   k = base - cand[k] / du
+ *   f += w (q[floor k] + (k - floor k) (q[floor k + 1] - q[floor k]))   where 0 <= floor k <= W - 2, else nothing
+ * Views are added in index order: equal inputs give equal bits.  No atomics.
+ * Refused before any launch (NAF_ERR_INVALID_ARGUMENT): a null pointer; N < 1; W not in 1 .. NAF_CENTER_MAX_W; K not in 1 ..
+ * NAF_CENTER_MAX_K; n above NAF_CENTER_MAX_SIZE; parallel not 0 or 1; a non-finite scalar; du, dx or dy not above zero; for a cone
+ * beam DSO or DSD not above zero, or a slice whose corners reach the source's orbit; a pointer that is not 4-byte aligned; more
+ * than 2^31 - 1 workgroups.  S n == 0 returns NAF_OK without examining anything else.
+ *
+ * naf_center_metrics: per slice s and candidate k, over the pixels within r (metres) of the slice's centre (the test is fp64:
+ * ((ix - (n - 1) / 2) dx)^2 + ((iy - (n - 1) / 2) dy)^2 <= r^2),
+ *   out[s, k, 0] = sum -min(f, 0)                                                     (negativity)
+ *   out[s, k, 1] = sum |f[ix + 1, iy] - f[ix, iy]| + |f[ix, iy + 1] - f[ix, iy]|      (sharpness; both ends inside the circle)
+ * f64 [S, K, 2], summed in fp64 in a fixed order (per-workgroup partials in `workspace`, then one pass in index order): equal
+ * inputs give equal bits.  No atomics.  workspace: at least naf_center_metrics_workspace_bytes(S, K, n) bytes, 8-byte aligned.
+ * Refused: a null pointer; n above NAF_CENTER_MAX_SIZE; dx, dy not finite or not above zero; r not finite or below zero; f not
+ * 4-byte, out or workspace not 8-byte aligned; a workspace that is too small.  S K == 0 returns NAF_OK.
+ * Both calls take the stream, allocate nothing and never synchronise. */
+#define NAF_CENTER_MAX_W 16384u
+#define NAF_CENTER_MAX_K 64u
+#define NAF_CENTER_MAX_SIZE 4096u
+#define NAF_CENTER_GROUP 8u
+int naf_center_slices(const float *q, const float *trig, const float *cand, uint32_t S, uint32_t N, uint32_t W, uint32_t K, uint32_t n,
+                      int parallel, float DSO, float DSD, float du, float ou, float dx, float dy, float ox, float oy, float *f,
+                      void *stream);
+size_t naf_center_metrics_workspace_bytes(uint32_t S, uint32_t K, uint32_t n);
+int naf_center_metrics(const float *f, uint32_t S, uint32_t K, uint32_t n, float dx, float dy, float r, double *out, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

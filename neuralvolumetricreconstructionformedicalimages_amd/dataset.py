@@ -217,6 +217,19 @@ def synthetic_scan(n_voxel=64, n_train=50, n_val=8, mode="cone", tilt_angle=0, s
     return data
 
 
+def plant_center_offset(geometry, offset_px, **kwargs):
+    """`synthetic_scan(geometry=..., **kwargs)` with a wrong centre of rotation planted: the projections are made with
+    `offDetector[0]` increased by `offset_px` detector pixels while the returned dict states the nominal `offDetector` of `geometry`
+    (the scanner dict, millimetres).  The defect is stored as `data["center_planted"]`; `reconstruct.find_center` finds it."""
+    nominal = [float(v) for v in geometry["offDetector"]]
+    true = dict(geometry)
+    true["offDetector"] = [nominal[0] + float(offset_px) * float(geometry["dDetector"][0]), *nominal[1:]]
+    data = synthetic_scan(geometry=true, **kwargs)
+    data["offDetector"] = list(geometry["offDetector"])
+    data["center_planted"] = {"offset_px": float(offset_px), "offDetector": true["offDetector"]}
+    return data
+
+
 def _rays_cpu(geo, angle):
     """Host construction of one projection's rays (only used to synthesise data without a GPU)."""
     from .geometry import angle2pose

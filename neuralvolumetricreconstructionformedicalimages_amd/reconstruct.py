@@ -110,7 +110,9 @@ The solvers are plain array code over callables and run on whatever arrays those
 arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart`, `fista_tv` and `cgls`, are HIP kernels.
 
 `reduce_metal` / `reduce_metal_operators` are no solver but a repair of the projections in front of one: the trace of the metal
-voxels of a first reconstruction is in-painted along the detector rows (`metal.inpaint_rows`).
+voxels of a first reconstruction is in-painted along the detector rows (`metal.inpaint_rows`).  `find_center` /
+`find_center_operators` are none either: they find the offset of the detector's column axis that the scan's `offDetector[0]` lacks
+(`center.slices`, `center.metrics`), and `recenter` writes it into a scan.
 """
 from __future__ import annotations
 
@@ -907,3 +909,190 @@ def reduce_metal(projections, geo, angles, threshold, method="li", air=None, bon
         return metal.inpaint_rows(b, mask, prior=prior, eps=eps, counts=True)
 
     return reduce_metal_operators(A, inpaint, metal.dilate, projections, initial, threshold, method=method, air=air, bone=bone, grow=grow)
+
+
+CENTER_METRICS = ("negativity", "sharpness")
+# Cone scans that cover less than a full turn, by what the float64 rehearsal of DESIGN.md section 34 recovers: the key is
+# `short_scan`, the value whether a planted 1.5 px offset came back within one candidate step at 64^3 (180 degrees in 50 views
+# without weights: 2.5; with Parker's weights: 1.5 at 180 degrees, 1.0 at 220).
+CENTER_CONE_SHORT_SCAN = {None: False, "parker": True}
+
+
+def center_metric(angles):
+    """The score `find_center` takes by default: "negativity" (its minimum) for a scan that covers less than a full turn less half a
+    view step, where a wrong centre draws negative tuning forks, and "sharpness" (its maximum) for a full turn, where it doubles
+    edges instead."""
+    from . import filter as F
+    import numpy as np
+    theta = F.covered_range(angles)
+    return "negativity" if theta < 2.0 * np.pi - 0.5 * theta / max(len(angles), 1) else "sharpness"
+
+
+def parabola_vertex(x, y):
+    """The abscissa of the vertex of the parabola through three points with equally spaced abscissae x[0] < x[1] < x[2]; x[1] where
+    the points lie on a line."""
+    curve = float(y[0]) - 2.0 * float(y[1]) + float(y[2])
+    if curve == 0.0 or not math.isfinite(curve):
+        return float(x[1])
+    return float(x[1]) + 0.5 * (float(y[0]) - float(y[2])) / curve * (float(x[2]) - float(x[1]))
+
+
+def _check_center(geo, angles, metric, rows, short_scan):
+    from . import center
+    from . import filter as F
+    center.scalars(geo)                                            # mode, tilt, square slice
+    if short_scan not in SHORT_SCAN:
+        raise ValueError(f"find_center: short_scan must be one of {SHORT_SCAN}, got {short_scan!r}")
+    if metric is not None and metric not in CENTER_METRICS:
+        raise ValueError(f"find_center: metric must be one of {CENTER_METRICS} or None, got {metric!r}")
+    if geo.mode == "cone":
+        if rows is not None:
+            raise ValueError("find_center: a cone beam is searched in its mid-plane only, rows must be None")
+        if center_metric(angles) == "negativity" and not CENTER_CONE_SHORT_SCAN[short_scan]:
+            raise ValueError(f"find_center: a cone scan that covers {math.degrees(F.covered_range(angles)):.1f} degrees, less than a full "
+                             f"turn, with short_scan={short_scan!r} is not supported: the float64 rehearsal does not recover a planted "
+                             "offset there (DESIGN.md section 34)")
+    elif rows is not None:
+        H = int(geo.nDetector[1])
+        rows = [int(r) for r in rows]
+        if not rows or any(r < 0 or r >= H for r in rows):
+            raise ValueError(f"find_center: rows must be a non-empty list of detector rows below {H}, got {rows}")
+    return rows
+
+
+def center_rows(geo):
+    """The detector rows a parallel-beam search takes by default: the central quarter, at most 8, evenly spread."""
+    H = int(geo.nDetector[1])
+    count = max(1, min(8, H // 4))
+    first = (H - count) // 2
+    return list(range(first, first + count))
+
+
+def find_center_operators(filter_rows, slices, metrics, b, geo, angles, candidates, metric, rows, filter="ram-lak", short_scan=None):
+    """The centre-of-rotation search (center.py) as array code over callables, on arrays of `b`'s kind
+    ([N, H, W]; torch tensors on any device, numpy arrays).
+
+        filter_rows(b, taps, pre, post, view_scale[, col])   the row filter of `fdk_operators`, here on the rows that are used only
+        slices(q, offsets)      filtered rows [S, N, W], K candidate offsets in metres -> slices [S, K, n, n]
+        metrics(f)              slices -> [S, K, 2] = (negativity, sharpness)
+
+        cone:      q = the filtered row at v = 0 (`center.midplane_rows`), S = 1;   `rows` must be None
+        parallel:  q = the filtered rows `rows` (None: `center_rows`), one slice each
+        scores[k] = sum over the slices of the `metric` ("negativity" or "sharpness") of candidate k
+
+    `candidates` are in pixels of the detector.  Returns scores [K], an array of the kind `metrics` returns.  A tilted scan is
+    refused where `fdk_weights` refuses it, a cone scan under a full turn by `CENTER_CONE_SHORT_SCAN`."""
+    import numpy as np
+
+    from . import center
+    rows = _check_center(geo, angles, metric, rows, short_scan)
+    if metric not in CENTER_METRICS:
+        raise ValueError(f"find_center: metric must be one of {CENTER_METRICS}, got {metric!r}")
+    if len(b.shape) != 3 or int(b.shape[0]) != len(angles):
+        raise ValueError(f"find_center: projections must be [N, H, W] with one view per angle, got {tuple(b.shape)} for {len(angles)} angles")
+    cand = np.asarray(candidates, dtype=np.float64).reshape(-1)
+    if not 1 <= cand.size <= center.MAX_K:
+        raise ValueError(f"find_center: 1 .. {center.MAX_K} candidates are needed, got {cand.size}")
+    weights = fdk_weights(geo, angles, filter) if short_scan is None else fdk_short_scan_weights(geo, angles, filter)
+    taps, pre, post, rest = weights[0], weights[1], weights[2], weights[3:]
+    xp, _ = _namespace(b)
+    blend = None
+    if geo.mode == "cone":
+        r0, r1, blend = center.midplane_rows(geo)
+        rows = [r0, r1]
+    elif rows is None:
+        rows = center_rows(geo)
+    sub = b[:, rows]
+    pre = None if pre is None else np.ascontiguousarray(pre[rows])
+    post = None if post is None else np.ascontiguousarray(post[rows])
+    filtered = filter_rows(sub, taps, pre, post, *rest)
+    if blend is None:
+        q = xp.swapaxes(filtered, 0, 1)
+    else:
+        q = ((1.0 - blend) * filtered[:, 0] + blend * filtered[:, 1])[None]
+    score = metrics(slices(q, cand * float(geo.dDetector[0])))
+    return score[:, :, CENTER_METRICS.index(metric)].sum(0)
+
+
+def pick_center(candidates, scores, metric, refine=True):
+    """The best candidate of a score curve (host arrays): the minimum of "negativity", the maximum of "sharpness" ->
+    (offset_px, best index, edge).  `edge`: the best is the first or the last candidate, so the true centre may lie outside the
+    grid; nothing is refined then.  Otherwise `refine` takes the vertex of the parabola through the best candidate and its two
+    neighbours, kept within half a step of the best."""
+    import numpy as np
+    cand, s = np.asarray(candidates, dtype=np.float64), np.asarray(scores, dtype=np.float64)
+    if cand.shape != s.shape or cand.ndim != 1 or cand.size < 1:
+        raise ValueError(f"find_center: one score per candidate is needed, got {s.shape} for {cand.shape}")
+    if not np.all(np.isfinite(s)):
+        raise ValueError("find_center: a score is not finite")
+    best = int(np.argmin(s) if metric == "negativity" else np.argmax(s))
+    edge = cand.size > 1 and best in (0, cand.size - 1)
+    offset = float(cand[best])
+    if refine and not edge and cand.size >= 3:
+        half = 0.5 * (cand[best + 1] - cand[best])
+        vertex = parabola_vertex(cand[best - 1:best + 2], s[best - 1:best + 2])
+        offset = float(min(max(vertex, cand[best] - half), cand[best] + half))
+    return offset, best, bool(edge)
+
+
+def find_center(projections, geo, angles, max_shift=8, step=0.5, metric=None, rows=None, filter="ram-lak", short_scan=None, refine=True):
+    """The offset of the detector's column axis that `geo.offDetector[0]` lacks, from `projections` [N, H, W] (float32, on the GPU)
+    taken with `geo` at `angles`: one slice per candidate in +-`max_shift` pixels at `step` (`center.candidates`, at most 64) is
+    back-projected from rows filtered once (`center.slices`), scored (`center.metrics`) and the best taken.  Returns a dict:
+    `offset_px`, `offset` (metres: add it to `geo.offDetector[0]`, or call `recenter`), `best_px` (the best candidate on the grid),
+    `candidates` (pixels), `scores`, `metric` and `edge`.
+
+    metric   "negativity" (minimum), "sharpness" (maximum) or None: `center_metric(angles)`
+    rows     parallel beam: the detector rows taken as slices (None: `center_rows`); a cone beam is searched in its mid-plane and
+             `rows` must be None
+    refine   the vertex of the parabola through the best candidate and its neighbours; one host read of K doubles either way
+    `edge` is True when the best candidate is the first or the last: a warning is issued and nothing is refined.  A tilted scan is
+    refused, and so is a cone scan that covers less than a full turn (`CENTER_CONE_SHORT_SCAN`)."""
+    import warnings
+
+    import torch
+
+    from . import center
+    from . import filter as F
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError("find_center: projections must be a CUDA/HIP tensor (no CPU path)")
+    if projections.dtype != torch.float32:
+        raise TypeError(f"find_center: projections must be float32, got {projections.dtype}")
+    cand = center.candidates(max_shift, step)
+    _check_center(geo, angles, metric, rows, short_scan)
+    metric = center_metric(angles) if metric is None else metric
+    radius = center.mask_radius(geo, max_shift)
+
+    def on_device(a):
+        return None if a is None else torch.tensor(a, device=projections.device)
+
+    def filter_rows(b, taps, pre, post, view_scale, col=None):
+        return F.filter_rows(b.contiguous(), on_device(taps), on_device(pre), on_device(post), on_device(view_scale), on_device(col))
+
+    def slices(q, offsets):
+        return center.slices(q.contiguous(), geo, angles, offsets)
+
+    def scores_of(f):
+        return center.metrics(f, geo, radius)
+
+    scores = find_center_operators(filter_rows, slices, scores_of, projections, geo, angles, cand, metric, rows, filter=filter,
+                                   short_scan=short_scan).cpu().numpy()
+    offset_px, best, edge = pick_center(cand, scores, metric, refine=refine)
+    if edge:
+        warnings.warn(f"find_center: the best candidate ({cand[best]:+.2f} px) is at the edge of the search range; widen max_shift")
+    return {"offset_px": offset_px, "offset": offset_px * float(geo.dDetector[0]), "best_px": float(cand[best]), "candidates": cand,
+            "scores": scores, "metric": metric, "edge": edge}
+
+
+def recenter(data, offset_m):
+    """A shallow copy of a scan dict (the pickle schema, lengths in millimetres) with `offset_m` METRES added to `offDetector[0]`,
+    and `center_offset`, the sum of all such corrections in millimetres, beside it.  `data` is left as it is."""
+    offset_mm = float(offset_m) * 1000.0
+    if not math.isfinite(offset_mm):
+        raise ValueError(f"recenter: the offset must be finite, got {offset_m}")
+    out = dict(data)
+    off = [float(v) for v in data["offDetector"]]
+    off[0] += offset_mm
+    out["offDetector"] = off
+    out["center_offset"] = float(data.get("center_offset", 0.0)) + offset_mm
+    return out
