@@ -979,6 +979,32 @@ size_t naf_center_metrics_workspace_bytes(uint32_t S, uint32_t K, uint32_t n);
 int naf_center_metrics(const float *f, uint32_t S, uint32_t K, uint32_t n, float dx, float dy, float r, double *out, void *workspace,
                        size_t workspace_bytes, void *stream);
 
+/* naf_center_slices_tilted: the same search for a tilted-axis (laminographic) parallel beam, where a candidate is an offset of the
+ * detector's column axis and a tilt, and a slice is a height z (center.slices_tilted, reconstruct.find_center_tilted).
+ * DESIGN.md section 35; the per-pixel arithmetic is csrc/center_tilted_device.h.  The scores are naf_center_metrics.
+ *   q      f32 [N, H, W] C-contiguous on the device: whole filtered views (naf_filter_rows on the nominal geometry)
+ *   trig   f32 [N, 2] = (cos a_i, sin a_i), on the device
+ *   cand_host  f32 [K, 3] = (c_k / du, sin tau_k, cos tau_k) in HOST memory, the one array here that is: c_k the offset added
+ *          to ou, in detector pixels; read before the call returns and passed to the kernel by value, so that a candidate can be
+ *          refused without a device read
+ *   z      f32 [S] on the device: the slices' heights in metres
+ *   f      f32 [S, K, n, n] on the device, pixel centres as in naf_center_slices
+ * The conventions are geometry.angle2pose's for mode "parallel": column axis (-sin a, cos a, 0), row axis (sin tau cos a,
+ * sin tau sin a, -cos tau).  Per pixel, view and candidate, every operation one IEEE fp32 operation in the order written:
+ *   t = y cos a - x sin a;   s = x cos a + y sin a;   base = (t - ou) (1 / du) + (W / 2 - 0.5);   k = base - cand_host[k][0]
+ *   v = sin tau_k s - cos tau_k z;   r = (v - ov) (1 / dv) + (H / 2 - 0.5)
+ *   acc += bilinear(q_i; r, k): linear along the columns in rows floor r and floor r + 1, then between them, where
+ *          0 <= floor k <= W - 2 and 0 <= floor r <= H - 2, else nothing
+ *   f = cos tau_k acc
+ * Views are added in index order: equal inputs give equal bits.  No atomics.
+ * Refused before any launch (NAF_ERR_INVALID_ARGUMENT): a null pointer; S < 1; N < 1; H not in 2 .. 2^24; W not in 2 ..
+ * NAF_CENTER_MAX_W; K not in 1 .. NAF_CENTER_MAX_K; n above NAF_CENTER_MAX_SIZE; a non-finite scalar or candidate; du, dv, dx or dy
+ * not above zero; a candidate whose sin^2 + cos^2 is further than 1e-3 from 1; a pointer that is not 4-byte aligned; more than
+ * 2^31 - 1 workgroups.  n == 0 returns NAF_OK after these checks.  Takes the stream, allocates nothing and never synchronises. */
+int naf_center_slices_tilted(const float *q, const float *trig, const float *cand_host, const float *z, uint32_t S, uint32_t N, uint32_t H,
+                             uint32_t W, uint32_t K, uint32_t n, float du, float dv, float ou, float ov, float dx, float dy, float ox,
+                             float oy, float *f, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,4 +6,4 @@ __version__ = "0.1.0"
 
 from .volume import prepare_volume, resize_volume  # noqa: E402,F401
 from .reconstruct import (align_operators, align_projections, asd_pocs, asd_pocs_operators, cgls, cgls_operators, fdk, fdk_operators, fista_tv, fista_tv_operators, os_sart,  # noqa: E402,F401
-                          os_sart_operators, reduce_metal, reduce_metal_operators, sirt, sirt_operators, subset_order)  # noqa: E402,F401
+                          lamino_fbp, lamino_fbp_operators, os_sart_operators, reduce_metal, reduce_metal_operators, sirt, sirt_operators, subset_order)  # noqa: E402,F401

@@ -185,6 +185,8 @@ SIGNATURES = {
     "naf_center_slices": (_i32, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "naf_center_metrics_workspace_bytes": (ctypes.c_size_t, [_u32, _u32, _u32]),
     "naf_center_metrics": (_i32, [_vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, ctypes.c_size_t, _vp]),
+    "naf_center_slices_tilted": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+                                        _vp, _vp]),
 }
 
 

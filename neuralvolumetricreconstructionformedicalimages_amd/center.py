@@ -8,6 +8,11 @@ once on the nominal geometry), score each slice (`metrics`) and add the best can
 (`reconstruct.find_center`, `reconstruct.recenter`).  Filtered rows are float32 [S, N, W] on the GPU, slices float32 [S, K, n, n],
 `f[s, k, ix, iy]` on the x and y voxel centres of the volume.  There is no CPU fallback, like the rest of the hot path; the float64
 restatement the tests compare with is tests/_center_oracle.py.
+
+A tilted-axis (laminographic) parallel-beam scan has two such numbers, the projected rotation axis and the tilt, and a pixel's
+detector row moves with the view: `tilted_scalars`, `tilted_mask_radius` and `slices_tilted` (`naf_center_slices_tilted`, DESIGN.md
+section 35) are the same search on whole filtered views [N, H, W], a candidate being an (offset, tilt) pair and a slice a height z;
+`metrics` scores both kinds.  Their restatement is tests/_lamino_oracle.py.
 """
 from __future__ import annotations
 
@@ -145,6 +150,116 @@ def slices(q, geo, angles, candidates, out=None):
     return out
 
 
+def tilted_scalars(geo):
+    """What `naf_center_slices_tilted` takes of a tilted-axis (laminographic) geometry, as a dict of Python numbers: tilt (degrees),
+    du, dv, ou, ov, W, H, n, dx, dy, ox, oy.  ValueError unless the beam is parallel, the tilt strictly between 0 and 90 degrees and
+    the slice square.  `scalars` keeps refusing such a scan: the untilted kernel has no row axis."""
+    if geo.mode != "parallel":
+        raise ValueError(f"center (tilted): mode must be 'parallel', got {geo.mode!r}: cone-beam laminography is not supported")
+    tilt = float(geo.tilt_angle)
+    if not 0.0 < tilt < 90.0:
+        raise ValueError(f"center (tilted): tilt_angle must lie strictly between 0 and 90 degrees, got {geo.tilt_angle}; an untilted scan "
+                         "is searched by find_center")
+    n1, n2 = int(geo.nVoxel[0]), int(geo.nVoxel[1])
+    if n1 != n2:
+        raise ValueError(f"center (tilted): the slice must be square, got nVoxel {n1} x {n2}")
+    return {"tilt": tilt, "du": float(geo.dDetector[0]), "dv": float(geo.dDetector[1]), "ou": float(geo.offDetector[0]),
+            "ov": float(geo.offDetector[1]), "W": int(geo.nDetector[0]), "H": int(geo.nDetector[1]), "n": n1,
+            "dx": float(geo.dVoxel[0]), "dy": float(geo.dVoxel[1]), "ox": float(geo.offOrigin[0]), "oy": float(geo.offOrigin[1])}
+
+
+def _tilts(g, tilts, K, who):
+    """One tilt in degrees per candidate, float64 [K]: the scan's own where `tilts` is None."""
+    if tilts is None:
+        return np.full(K, g["tilt"], dtype=np.float64)
+    t = np.asarray(tilts, dtype=np.float64).reshape(-1)
+    if t.size != K or not np.all(np.isfinite(t)) or not np.all((t > 0.0) & (t < 90.0)):
+        raise ValueError(f"{who}: tilts must be {K} finite values strictly between 0 and 90 degrees, one per candidate")
+    return t
+
+
+def tilted_candidates(candidates, tilts):
+    """The candidate table of `naf_center_slices_tilted`: (c_k / du in pixels, sin tau_k, cos tau_k), formed in float64 and rounded
+    once -> float32 numpy [K, 3].  `candidates` in pixels, `tilts` in degrees."""
+    c = np.asarray(candidates, dtype=np.float64).reshape(-1)
+    t = np.radians(np.asarray(tilts, dtype=np.float64).reshape(-1))
+    return np.stack([c, np.sin(t), np.cos(t)], -1).astype(np.float32)
+
+
+def tilted_mask_radius(geo, max_shift, tilts=None, z=(0.0,)):
+    """The largest radius (metres) about the slice's origin at which every pixel of every slice height in `z` (metres) projects
+    between the centres of the first and the last detector column AND row, in every view, for every candidate within +-`max_shift`
+    pixels and every tilt in `tilts` (degrees; None: the scan's own), capped by the circle inscribed in the pixel centres of the
+    slice.  ValueError if nothing is left."""
+    g = tilted_scalars(geo)
+    t = np.radians(_tilts(g, tilts, 1 if tilts is None else np.asarray(tilts).size, "center.tilted_mask_radius"))
+    zs = np.abs(np.asarray(z, dtype=np.float64).reshape(-1))
+    if zs.size < 1 or not np.all(np.isfinite(zs)):
+        raise ValueError("center.tilted_mask_radius: z must be a non-empty list of finite heights")
+    reach_u = (g["W"] / 2 - 0.5) * g["du"] - abs(g["ou"]) - abs(float(max_shift)) * g["du"]
+    reach_v = (g["H"] / 2 - 0.5) * g["dv"] - abs(g["ov"])
+    rho_v = float(np.min((reach_v - np.cos(t) * zs.max()) / np.sin(t)))         # |sin tau s - cos tau z| <= sin tau rho + cos tau |z|
+    r = min(min(reach_u, rho_v) - math.hypot(g["ox"], g["oy"]), 0.5 * (g["n"] - 1) * min(g["dx"], g["dy"]))
+    if not r > 0.0:
+        raise ValueError(f"center.tilted_mask_radius: no pixel of the slice stays on the detector for shifts of +-{max_shift} pixels, "
+                         f"the tilts and the heights given")
+    return r
+
+
+def slices_tilted(q, geo, angles, candidates, tilts=None, z=(0.0,), out=None):
+    """`naf_center_slices_tilted`: the slices at the heights `z` (metres, S of them) of a tilted-axis parallel-beam scan,
+    back-projected from whole filtered views `q` (float32 [N, H, W] on the GPU) for every candidate -> float32 [S, K, n, n].
+    `candidates` are offsets in METRES added to `geo.offDetector[0]` (at most 64), `tilts` one tilt in degrees per candidate (None:
+    the scan's own for all of them), `angles` one per view.  Each slice carries its candidate's Jacobian cos(tilt); the weights of
+    `reconstruct.lamino_fbp_weights` are expected in `q` with the nominal tilt's cosine taken out (`find_center_tilted` does that)."""
+    import ctypes
+
+    import torch
+
+    from . import _abi
+    who = "center.slices_tilted"
+    g = tilted_scalars(geo)
+    cand = np.asarray(candidates, dtype=np.float64).reshape(-1)
+    if not 1 <= cand.size <= MAX_K or not np.all(np.isfinite(cand)):
+        raise ValueError(f"{who}: 1 .. {MAX_K} finite candidates are needed, got {cand.size}")
+    table = np.ascontiguousarray(tilted_candidates(cand / g["du"], _tilts(g, tilts, cand.size, who)))
+    heights = np.asarray(z, dtype=np.float64).reshape(-1)
+    if heights.size < 1 or not np.all(np.isfinite(heights)):
+        raise ValueError(f"{who}: z must be a non-empty list of finite heights, got {z!r}")
+    tr = trig(angles)
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        raise ValueError(f"{who}: q must be a float32 tensor [N, H, W]")
+    N, H, W = (int(v) for v in q.shape)
+    if N != tr.shape[0] or N < 1 or W != g["W"] or H != g["H"]:
+        raise ValueError(f"{who}: q must be [{tr.shape[0]}, {g['H']}, {g['W']}] with one view per angle, got {tuple(q.shape)}")
+    if W > MAX_W or W < 2 or H < 2 or g["n"] > MAX_SIZE:
+        raise ValueError(f"{who}: 2 .. {MAX_W} detector columns, at least 2 rows and at most {MAX_SIZE} pixels along a side, got "
+                         f"{W}, {H} and {g['n']}")
+    _check(q, (N, H, W), None, who, "q")
+    S, K, n = heights.size, cand.size, g["n"]
+    if out is None:
+        out = torch.empty((S, K, n, n), dtype=torch.float32, device=q.device)
+    else:
+        _check(out, (S, K, n, n), q, who, "out")
+    if n == 0:
+        return out
+    trig_d = torch.tensor(tr, device=q.device)
+    z_d = torch.tensor(heights.astype(np.float32), device=q.device)
+    with torch.cuda.device(q.device):
+        _abi.check(_abi.lib().naf_center_slices_tilted(_abi.ptr(q), _abi.ptr(trig_d), table.ctypes.data_as(ctypes.c_void_p), _abi.ptr(z_d),
+                                                       S, N, H, W, K, n, g["du"], g["dv"], g["ou"], g["ov"], g["dx"], g["dy"], g["ox"],
+                                                       g["oy"], _abi.ptr(out), _abi.stream_ptr()), "center_slices_tilted")
+    return out
+
+
+def slice_grid(geo):
+    """What `metrics` reads of a geometry, tilted or not: n, dx, dy of the square slice.  ValueError for a slice that is not square."""
+    n1, n2 = int(geo.nVoxel[0]), int(geo.nVoxel[1])
+    if n1 != n2:
+        raise ValueError(f"center: the slice must be square, got nVoxel {n1} x {n2}")
+    return {"n": n1, "dx": float(geo.dVoxel[0]), "dy": float(geo.dVoxel[1])}
+
+
 def metrics_workspace(S, K, n, device):
     """The workspace of `metrics` for slices [S, K, n, n]: a float64 tensor on `device`."""
     import torch
@@ -163,7 +278,7 @@ def metrics(f, geo, radius, workspace=None):
 
     from . import _abi
     who = "center.metrics"
-    g = scalars(geo)
+    g = slice_grid(geo)
     radius = float(radius)
     if not math.isfinite(radius) or radius < 0.0:
         raise ValueError(f"{who}: radius must be finite and not below zero, got {radius}")

@@ -230,6 +230,22 @@ def plant_center_offset(geometry, offset_px, **kwargs):
     return data
 
 
+def plant_tilt_error(geometry, error_deg, **kwargs):
+    """`synthetic_scan(geometry=..., **kwargs)` of a tilted-axis scan with a wrong tilt planted: the projections are made with
+    `tilt_angle` increased by `error_deg` degrees while the returned dict states the nominal `tilt_angle` of `geometry`.  The defect
+    is stored as `data["tilt_planted"]`.  No search for it is shipped: sharpness on the slice z = 0 ran to the edge of its grid in
+    every rehearsal, and this is how a better score would be rehearsed."""
+    nominal = float(geometry.get("tilt_angle", 0))
+    if not nominal:
+        raise ValueError("plant_tilt_error: the scan has no tilt_angle to be wrong about")
+    true = dict(geometry)
+    true["tilt_angle"] = nominal + float(error_deg)
+    data = synthetic_scan(geometry=true, **kwargs)
+    data["tilt_angle"] = geometry["tilt_angle"]
+    data["tilt_planted"] = {"error_deg": float(error_deg), "tilt_angle": true["tilt_angle"]}
+    return data
+
+
 def _rays_cpu(geo, angle):
     """Host construction of one projection's rays (only used to synthesise data without a GPU)."""
     from .geometry import angle2pose

@@ -110,10 +110,14 @@ def fit_volume(net, volume, geo, n_steps, n_points=DEFAULT_POINTS, lr=1e-3, seed
     return losses
 
 
+ANALYTIC_SOURCES = ("fdk", "lamino-fbp")      # reconstruct.fdk / reconstruct.lamino_fbp of the training projections
+
+
 # ---- the training YAML's keys --------------------------------------------------------------------------------------------------------
 def init_volume_config(train_cfg, world_size=1):
-    """Parse `train.init_volume` (absent / None: no warm start; "fdk"; or a path to a .npy of shape nVoxel), `train.init_steps`
-    (default 500) and `train.init_points` (default 2^16) -> None, or {"source": "fdk" | path, "steps": int, "points": int}.
+    """Parse `train.init_volume` (absent / None: no warm start; "fdk"; "lamino-fbp" for a tilted-axis scan; or a path to a .npy of
+    shape nVoxel), `train.init_steps` (default 500) and `train.init_points` (default 2^16) -> None, or
+    {"source": "fdk" | "lamino-fbp" | path, "steps": int, "points": int}.
     Raises ValueError on an unknown value and on a world size above 1; touches no device and no process group."""
     source = train_cfg.get("init_volume")
     if source is None:
@@ -121,8 +125,8 @@ def init_volume_config(train_cfg, world_size=1):
     if not isinstance(source, (str, os.PathLike)):
         raise ValueError(f"train.init_volume must be 'fdk' or a path to a .npy volume, got {source!r}")
     source = os.fspath(source)
-    if source != "fdk" and not source.endswith(".npy"):
-        raise ValueError(f"train.init_volume must be 'fdk' or a path to a .npy volume, got {source!r}")
+    if source not in ANALYTIC_SOURCES and not source.endswith(".npy"):
+        raise ValueError(f"train.init_volume must be 'fdk' or a path to a .npy volume ('lamino-fbp' for a tilted-axis scan), got {source!r}")
     if int(world_size) > 1:
         # the fit's table gradient is summed with fp32 atomics below 2^13 points and in a per-process order above: ranks that each
         # fitted their own copy would start training from tables that differ, and the data-parallel step assumes replicas
@@ -144,16 +148,24 @@ def check_init_geometry(init, geo):
             raise ValueError(f"train.init_volume: 'fdk' needs a scan that reconstruct.fdk accepts (cone or parallel beam, no tilt), got "
                              f"mode {geo.mode!r} with tilt_angle {geo.tilt_angle}; fdk refuses a tilted (laminographic) scan")
         return
+    if init["source"] == "lamino-fbp":
+        if geo.mode != "parallel" or not 0.0 < float(geo.tilt_angle) < 90.0:
+            raise ValueError(f"train.init_volume: 'lamino-fbp' needs a scan that reconstruct.lamino_fbp accepts (a parallel beam tilted "
+                             f"strictly between 0 and 90 degrees), got mode {geo.mode!r} with tilt_angle {geo.tilt_angle}")
+        return
     shape = np.load(init["source"], mmap_mode="r").shape
     if tuple(shape) != _extent(geo.nVoxel):
         raise ValueError(f"train.init_volume: {init['source']} has shape {tuple(shape)} but the scan's nVoxel is {_extent(geo.nVoxel)}")
 
 
 def init_volume_tensor(init, geo, projections, angles, device):
-    """The volume `init` names, as a CUDA float32 tensor of shape nVoxel: reconstruct.fdk of the training projections clamped at 0,
-    or the .npy file."""
+    """The volume `init` names, as a CUDA float32 tensor of shape nVoxel: reconstruct.fdk (or reconstruct.lamino_fbp, whose
+    refusals apply: a full turn of views) of the training projections clamped at 0, or the .npy file."""
     import torch
     if init["source"] == "fdk":
         from . import reconstruct
         return reconstruct.fdk(projections, geo, angles, nonneg=True).contiguous()
+    if init["source"] == "lamino-fbp":
+        from . import reconstruct
+        return reconstruct.lamino_fbp(projections, geo, angles, nonneg=True).contiguous()
     return torch.tensor(np.load(init["source"]), dtype=torch.float32, device=device).contiguous()

@@ -106,6 +106,16 @@ By default there are no short-scan weights: a cone scan that covers less than a 
 pass) and takes w_i = gap_i, for scans of pi .. 2 pi.  A tilted
 (laminographic) scan is refused: its constant and filter direction are not verified here.
 
+Laminographic FBP (`lamino_fbp`, `lamino_fbp_weights`, `lamino_fbp_operators`) is that form for a parallel beam
+whose rotation axis is tilted by tau against the detector's rows, over a full turn.  The axis projects onto the detector's row
+direction, so the ramp still runs along the rows with tau_taps = du; every frequency outside the missing cone k_r < |k_z| tan(tau) is
+seen twice per turn and the Jacobian of (angle, row frequency) -> k carries cos(tau):
+
+    x_FBP = A^T y,   y_i = w_i * cos(tau) * (du dv / dV) * q_i,   sum w_i = pi over the full turn, no cosine weights
+
+`find_center_tilted` / `find_center_tilted_operators` are `find_center` for such a scan (`center.slices_tilted`): sharpness, maximised,
+on the slice z = 0; negativity is largest at the true centre there and is refused.
+
 The solvers are plain array code over callables and run on whatever arrays those take (torch tensors on any device, numpy
 arrays); only the operators bound by `sirt`, `asd_pocs` and `fdk`, and the whole of `os_sart`, `fista_tv` and `cgls`, are HIP kernels.
 
@@ -826,6 +836,114 @@ def fdk(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call
     return fdk_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=nonneg, short_scan=short_scan)
 
 
+def _check_lamino(geo, angles, who="lamino_fbp"):
+    """The scans laminographic FBP is derived for: a parallel beam tilted strictly between 0 and 90 degrees, at least two finite
+    view angles, a full turn."""
+    from . import filter as F
+    import numpy as np
+    if geo.mode != "parallel":
+        raise ValueError(f"{who}: mode must be 'parallel', got {geo.mode!r}: cone-beam laminography is not supported")
+    tilt = float(geo.tilt_angle)
+    if tilt == 0.0:
+        raise ValueError(f"{who}: tilt_angle is 0, which is plain parallel-beam CT: use fdk")
+    if not 0.0 < tilt < 90.0:
+        raise ValueError(f"{who}: tilt_angle must lie strictly between 0 and 90 degrees, got {geo.tilt_angle}")
+    a = np.asarray(angles, dtype=np.float64).reshape(-1)
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"{who}: the view angles must be finite")
+    if a.size < 2:
+        raise ValueError(f"{who}: at least two views are needed, got {a.size}")
+    covered = F.covered_range(a)
+    if covered < 2.0 * math.pi - 0.5 * covered / a.size:
+        ordered = np.sort(a)
+        gap = max(float(np.max(np.diff(ordered))), 2.0 * math.pi - float(ordered[-1] - ordered[0]))      # the wrap-around gap too
+        raise ValueError(f"{who}: {a.size} views cover {math.degrees(covered):.1f} degrees (largest gap {math.degrees(gap):.1f} degrees, the one across the turn's end included), "
+                         "less than a full turn: every frequency outside the missing cone must be seen twice, and no short-scan weights "
+                         "are derived for a tilted axis")
+    return math.radians(tilt)
+
+
+def lamino_fbp_weights(geo, angles, filter="ram-lak"):
+    """What `filter_rows` needs for a laminographic FBP of a tilted parallel-beam scan of `geo` at `angles`, as `fdk_weights` returns
+    it: (taps [W], None, None, view_scale [N]), float32 numpy arrays formed in float64 and rounded once.  The ramp runs along the
+    detector rows with tap spacing du, there are no cosine weights, and view_scale[i] = w_i cos(tilt) du dv / dV with sum w_i = pi over
+    the full turn (`filter.view_weights`); DESIGN.md section 35.  ValueError for a cone beam, tilt 0 (use `fdk`), a tilt outside
+    (0, 90) degrees, non-finite angles, fewer than two views and views that cover less than a full turn."""
+    from . import filter as F
+    import numpy as np
+    tau = _check_lamino(geo, angles)
+    du, dv = float(geo.dDetector[0]), float(geo.dDetector[1])
+    dV = float(np.prod(np.asarray(geo.dVoxel, dtype=np.float64)))
+    w = F.view_weights(angles) * (math.cos(tau) * du * dv / dV)
+    return F.ramp_taps(int(geo.nDetector[0]), du, filter), None, None, w.astype(np.float32)
+
+
+def lamino_fbp_operators(AT, filter_rows, b, geo, angles, filter="ram-lak", nonneg=False):
+    """Laminographic FBP over the transpose `AT` and a row filter `filter_rows(b, taps, pre, post, view_scale)`, as `fdk_operators`:
+    AT(filter_rows(b, *lamino_fbp_weights(...))), clamped at 0 if `nonneg`."""
+    if len(b.shape) != 3 or int(b.shape[0]) != len(angles):
+        raise ValueError(f"lamino_fbp: projections must be [N, H, W] with one view per angle, got {tuple(b.shape)} for {len(angles)} angles")
+    x = AT(filter_rows(b, *lamino_fbp_weights(geo, angles, filter)))
+    if nonneg:
+        x = _namespace(b)[1](x, 0, None)
+    return x
+
+
+def lamino_window(geo):
+    """How much of a tilted parallel-beam scan's volume the projector pair's near / far window holds -> (kept, reach), metres along
+    the rays from the rotation centre: `kept` is the smaller of the depths the window keeps behind and in front of it, `reach` the
+    depth of the volume's furthest corner.  `geometry.get_near_far` places the window about DSO and ignores the tilt, while the
+    beam's source plane stands at DSO / cos(tilt); where reach > kept, the voxels deeper than `kept` are cut out of some views' rays
+    by A and A^T alike."""
+    import numpy as np
+
+    from .geometry import get_near_far
+    tau = math.radians(float(geo.tilt_angle))
+    near, far = get_near_far(geo)
+    source = float(geo.DSO) / math.cos(tau)
+    half = 0.5 * np.asarray(geo.sVoxel, dtype=np.float64) + np.abs(np.asarray(geo.offOrigin, dtype=np.float64))
+    reach = math.cos(tau) * math.hypot(half[0], half[1]) + math.sin(tau) * float(half[2])
+    return min(float(far) - source, source - float(near)), reach
+
+
+def lamino_fbp(projections, geo, angles, filter="ram-lak", nonneg=False, views_per_call=None, deterministic=False, out=None):
+    """Filtered back-projection of a tilted-axis (laminographic) parallel-beam scan: `projections` [N, H, W] (float32, on the GPU)
+    taken with `geo` at `angles` over a full turn -> float32 volume of geo.nVoxel on the projections' device (`out`, if given).  One
+    pass of `filter.filter_rows` and one of `projector.backproject_scan`, as `fdk`; the frequencies inside the missing cone
+    k_r < |k_z| tan(tilt) are not measured and stay zero.  `deterministic=True` takes the atomic-free gather transpose, which accepts
+    the tilted beam: two runs return the same bits.  A voxel whose rays the scan's near / far window cuts (`geometry.get_near_far`
+    ignores the tilt) receives fewer views, as it does from every solver on this pair: a warning says how deep the window reaches
+    (`lamino_window`)."""
+    import warnings
+
+    import torch
+
+    from . import filter as F
+    from . import projector
+
+    def on_device(a):
+        return None if a is None else torch.tensor(a, device=projections.device)
+
+    def rows(b, taps, pre, post, view_scale):
+        return F.filter_rows(b, on_device(taps), on_device(pre), on_device(post), on_device(view_scale))
+
+    _check_lamino(geo, angles)
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError("lamino_fbp: projections must be a CUDA/HIP tensor (no CPU path)")
+    kept, reach = lamino_window(geo)
+    if reach > kept:
+        warnings.warn(f"lamino_fbp: the scan's near / far window keeps {kept * 1000:.1f} mm along the rays about the rotation centre "
+                      f"and the volume reaches {reach * 1000:.1f} mm: voxels deeper than that receive fewer views (the window is "
+                      "placed about DSO and ignores the tilt; a smaller DSO in the scan's geometry widens what it keeps)")
+    scan = projector.Scan(geo, angles, projections.device)
+
+    def AT(y):
+        return projector.backproject_scan(y, geo, angles, views_per_call=views_per_call, out=out, method=_method(deterministic), scan=scan)
+
+    x = lamino_fbp_operators(AT, rows, projections, geo, angles, filter=filter, nonneg=False)
+    return x.clamp_(min=0) if nonneg else x
+
+
 METAL_METHODS = ("li", "nmar")
 NMAR_EPS_FRACTION = 1e-3                # eps of the normalised in-painting, as a fraction of the prior sinogram's maximum
 
@@ -1096,3 +1214,96 @@ def recenter(data, offset_m):
     out["offDetector"] = off
     out["center_offset"] = float(data.get("center_offset", 0.0)) + offset_mm
     return out
+
+
+TILTED_CENTER_METRIC = "sharpness"
+
+
+def _check_tilted_metric(who, metric):
+    """A tilted-axis search is scored by sharpness, maximised.  The missing cone makes a focused laminogram negative beside every
+    edge, so negativity is LARGEST at the true centre and tilt: the rule of CT is not offered."""
+    if metric == "negativity":
+        raise ValueError(f"{who}: metric 'negativity' is not offered for a tilted axis: the missing cone makes a focused laminogram "
+                         "negative beside every edge, so negativity is largest at the true value; the score is 'sharpness', maximised")
+    if metric not in (None, TILTED_CENTER_METRIC):
+        raise ValueError(f"{who}: metric must be {TILTED_CENTER_METRIC!r} or None, got {metric!r}")
+
+
+def find_center_tilted_operators(filter_rows, slices, metrics, b, geo, angles, candidates, tilts=None, filter="ram-lak"):
+    """The centre (and tilt) search of a tilted-axis parallel-beam scan (center.py) as array code over
+    callables, on arrays of `b`'s kind ([N, H, W]; torch tensors on any device, numpy arrays).
+
+        filter_rows(b, taps, pre, post, view_scale)   the row filter of `fdk_operators`, on whole views
+        slices(q, offsets, tilts)   filtered views [N, H, W], K offsets in metres, K tilts in degrees or None -> the slice z = 0 for
+                                    every candidate, [1, K, n, n], each times its own cos(tilt)
+        metrics(f)                  slices -> [1, K, 2] = (negativity, sharpness)
+
+    q = the views filtered with view_scale[i] = w_i (`filter.view_weights`; the cosine of `lamino_fbp_weights` is the slices' own),
+    scores[k] = the sharpness of candidate k.  `candidates` are in pixels of the detector; `tilts` (degrees, one per candidate) None
+    takes the scan's own.  Returns scores [K], an array of the kind `metrics` returns.  The refusals are `lamino_fbp_weights`'."""
+    import numpy as np
+
+    from . import center
+    from . import filter as F
+    _check_lamino(geo, angles, "find_center_tilted")
+    center.tilted_scalars(geo)                                     # a square slice
+    if len(b.shape) != 3 or int(b.shape[0]) != len(angles):
+        raise ValueError(f"find_center_tilted: projections must be [N, H, W] with one view per angle, got {tuple(b.shape)} for "
+                         f"{len(angles)} angles")
+    cand = np.asarray(candidates, dtype=np.float64).reshape(-1)
+    if not 1 <= cand.size <= center.MAX_K:
+        raise ValueError(f"find_center_tilted: 1 .. {center.MAX_K} candidates are needed, got {cand.size}")
+    du = float(geo.dDetector[0])
+    q = filter_rows(b, F.ramp_taps(int(geo.nDetector[0]), du, filter), None, None, F.view_weights(angles).astype(np.float32))
+    score = metrics(slices(q, cand * du, tilts))
+    return score[0, :, CENTER_METRICS.index(TILTED_CENTER_METRIC)]
+
+
+def _tilted_search(who, projections, geo, angles, cand_px, tilts, radius, filter):
+    """`find_center_tilted_operators` on the kernels -> scores, float64 numpy [K]."""
+    import torch
+
+    from . import center
+    from . import filter as F
+    if not isinstance(projections, torch.Tensor) or not projections.is_cuda:
+        raise RuntimeError(f"{who}: projections must be a CUDA/HIP tensor (no CPU path)")
+    if projections.dtype != torch.float32:
+        raise TypeError(f"{who}: projections must be float32, got {projections.dtype}")
+
+    def on_device(a):
+        return None if a is None else torch.tensor(a, device=projections.device)
+
+    def filter_rows(b, taps, pre, post, view_scale):
+        return F.filter_rows(b.contiguous(), on_device(taps), on_device(pre), on_device(post), on_device(view_scale))
+
+    def slices(q, offsets, tilts):
+        return center.slices_tilted(q, geo, angles, offsets, tilts=tilts)
+
+    def scores_of(f):
+        return center.metrics(f, geo, radius)
+
+    return find_center_tilted_operators(filter_rows, slices, scores_of, projections, geo, angles, cand_px, tilts,
+                                        filter=filter).cpu().numpy()
+
+
+def find_center_tilted(projections, geo, angles, max_shift=8, step=0.5, metric=None, filter="ram-lak", refine=True):
+    """`find_center` for a tilted-axis (laminographic) parallel-beam scan over a full turn: the offset of the detector's column axis
+    that `geo.offDetector[0]` lacks, from `projections` [N, H, W] (float32, on the GPU).  The slice z = 0 is back-projected for every
+    candidate in +-`max_shift` pixels at `step` from views filtered once (`center.slices_tilted`), scored by sharpness
+    (`center.metrics`) and the maximum taken (`pick_center`).  Returns a dict: `offset_px`, `offset` (metres: `recenter` writes it
+    into a scan), `best_px`, `candidates` (pixels), `scores`, `metric` and `edge` (the best candidate is the first or the last: a
+    warning is issued and nothing is refined).  `metric="negativity"` raises ValueError: it is largest at the true centre here."""
+    import warnings
+
+    from . import center
+    who = "find_center_tilted"
+    _check_tilted_metric(who, metric)
+    cand = center.candidates(max_shift, step)
+    _check_lamino(geo, angles, who)
+    radius = center.tilted_mask_radius(geo, max_shift)
+    scores = _tilted_search(who, projections, geo, angles, cand, None, radius, filter)
+    offset_px, best, edge = pick_center(cand, scores, TILTED_CENTER_METRIC, refine=refine)
+    if edge:
+        warnings.warn(f"{who}: the best candidate ({cand[best]:+.2f} px) is at the edge of the search range; widen max_shift")
+    return {"offset_px": offset_px, "offset": offset_px * float(geo.dDetector[0]), "best_px": float(cand[best]), "candidates": cand,
+            "scores": scores, "metric": TILTED_CENTER_METRIC, "edge": edge}

@@ -3,10 +3,15 @@
 
     python tools/find_center.py --scan in.pickle --out out.pickle [--max-shift 8] [--step 0.5] [--metric negativity|sharpness]
                                 [--short-scan parker]
+    python tools/find_center.py --tilted --scan lamino.pickle --out out.pickle [--max-shift 8] [--step 0.5]
+
+`--tilted` is for a tilted-axis (laminographic) parallel-beam scan over a full turn, which the plain search refuses:
+reconstruct.find_center_tilted back-projects the slice z = 0 and takes the maximum of sharpness; negativity
+and --short-scan do not apply there.
 
 The output has the input's pickle schema with `offDetector[0]` corrected (`reconstruct.recenter`) and the search stored beside it
 as `center_search` (candidates in pixels, scores, metric, offset_px, edge).  With a ground truth (`image`) in the pickle the FDK
-`psnr_3d` / `ssim_3d` before and after are printed.
+`psnr_3d` / `ssim_3d` before and after are printed (with `--tilted`: those of the laminographic FBP, reconstruct.lamino_fbp).
 """
 import argparse
 import os
@@ -23,8 +28,13 @@ ap.add_argument("--step", type=float, default=0.5, help="candidate spacing in de
 ap.add_argument("--metric", choices=["negativity", "sharpness"], default=None, help="default: by the angular range of the scan")
 ap.add_argument("--short-scan", choices=["parker"], default=None)
 ap.add_argument("--no-refine", action="store_true", help="keep the best candidate of the grid, no parabola")
+ap.add_argument("--tilted", action="store_true",
+                help="a tilted-axis (laminographic) parallel-beam scan over a full turn: reconstruct.find_center_tilted (sharpness, "
+                     "maximised, on the slice z = 0; DESIGN.md section 35), scored with reconstruct.lamino_fbp")
 ap.add_argument("--device", default="cuda")
 args = ap.parse_args()
+if args.tilted and (args.metric == "negativity" or args.short_scan is not None):
+    ap.error("--tilted is scored by sharpness only (negativity is largest at the true centre of a laminogram) and has no short scan")
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -37,8 +47,11 @@ with open(args.scan, "rb") as handle:
 geo = ConeGeometry(data)
 angles = np.asarray(data["train"]["angles"], dtype=np.float64).reshape(-1)
 projections = torch.tensor(np.asarray(data["train"]["projections"]), dtype=torch.float32, device=args.device).contiguous()
-found = reconstruct.find_center(projections, geo, angles, max_shift=args.max_shift, step=args.step, metric=args.metric,
-                                short_scan=args.short_scan, refine=not args.no_refine)
+if args.tilted:
+    found = reconstruct.find_center_tilted(projections, geo, angles, max_shift=args.max_shift, step=args.step, refine=not args.no_refine)
+else:
+    found = reconstruct.find_center(projections, geo, angles, max_shift=args.max_shift, step=args.step, metric=args.metric,
+                                    short_scan=args.short_scan, refine=not args.no_refine)
 print(f"{args.scan}: offset {found['offset_px']:+.3f} px ({found['offset'] * 1000:+.4f} mm) by {found['metric']}, best candidate "
       f"{found['best_px']:+.2f} px of {len(found['candidates'])}" + ("  [at the edge of the search range]" if found["edge"] else ""))
 out = reconstruct.recenter(data, found["offset"])
@@ -47,8 +60,11 @@ out["center_search"] = {"candidates": found["candidates"], "scores": found["scor
 if data.get("image") is not None:
     truth = torch.tensor(np.asarray(data["image"]), dtype=torch.float32, device=args.device)
     for name, scan in (("before", data), ("after", out)):
-        x = reconstruct.fdk(projections, ConeGeometry(scan), angles, short_scan=args.short_scan)
-        print(f"FDK {name}: psnr_3d {float(utils.get_psnr_3d(x, truth)):.2f} dB, ssim_3d {metrics.ssim_3d(x, truth):.4f}")
+        if args.tilted:
+            x = reconstruct.lamino_fbp(projections, ConeGeometry(scan), angles)
+        else:
+            x = reconstruct.fdk(projections, ConeGeometry(scan), angles, short_scan=args.short_scan)
+        print(f"{'laminographic FBP' if args.tilted else 'FDK'} {name}: psnr_3d {float(utils.get_psnr_3d(x, truth)):.2f} dB, ssim_3d {metrics.ssim_3d(x, truth):.4f}")
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "wb") as handle:
     pickle.dump(out, handle, pickle.HIGHEST_PROTOCOL)

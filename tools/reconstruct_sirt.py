@@ -29,6 +29,9 @@ def start_volume(args, proj, geo, angles):
     FDK always runs on the interpolated pair, whatever `--projector` the solve takes: its weights are derived for that transpose."""
     if args.init == "zeros":
         return None
+    if args.init == "lamino-fbp":                       # a tilted-axis scan over a full turn, which fdk refuses (DESIGN.md section 35)
+        from neuralvolumetricreconstructionformedicalimages_amd.reconstruct import lamino_fbp
+        return lamino_fbp(proj, geo, angles, nonneg=True, deterministic=args.deterministic)
     from neuralvolumetricreconstructionformedicalimages_amd import fdk
     return fdk(proj, geo, angles, nonneg=True, deterministic=args.deterministic)
 
@@ -56,8 +59,9 @@ def main(argv=None, solve=_sirt, add_arguments=None, description=None, iterative
         ap.add_argument("--iters", type=int, required=True)
         ap.add_argument("--relax", type=float, default=1.0)
         ap.add_argument("--no-nonneg", action="store_true", help="do not clamp the volume at 0 after every iteration")
-        ap.add_argument("--init", choices=["zeros", "fdk"], default="zeros",
-                        help="start volume: zeros, or the FDK reconstruction of the same projections clamped at 0 (inside the timing)")
+        ap.add_argument("--init", choices=["zeros", "fdk", "lamino-fbp"], default="zeros",
+                        help="start volume: zeros, or the FDK reconstruction (lamino-fbp: the laminographic FBP of a tilted-axis scan) "
+                             "of the same projections clamped at 0 (inside the timing)")
     ap.add_argument("--out", default=None, help="write the volume here as .npy")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--deterministic", action="store_true",
